@@ -25,9 +25,16 @@ windows are cut from the requests' completion times (no drain between
 windows), and the run is "stable" when the 3 windows before the last (which
 holds the final drain) are within 10% of their mean (perf_analyzer's rule).  value = total
 images/s over all ranks (elapsed = MAX over ranks); p50/p90/p99 over every
-rank's requests.  After the timed bs=8 region: a bs=1 point (HIP shm, same
-server) and, unless ``--no-bf16`` (or on more than one GPU), the bf16 engine as a labelled
-reduced-precision operating point.
+rank's requests.  A plain run stops there: set-up, warm-up, the K timed steps,
+the JSON line (``ms_per_step`` = the time of one timed step).  ``--full`` adds,
+outside the timed region: one python-client sanity request before it; after
+it the per-slot output check, the p99-constrained probes, a bs=1 point (HIP
+shm, same server), on more than one GPU the fan-out timings, and, unless
+``--no-bf16`` (or on more than one GPU), the bf16 engine as a labelled
+reduced-precision operating point.  ``--dump-outputs DIR`` writes what the
+timed loop left in the output region (every concurrency slot's last fc6_1
+logits) to ``DIR/fc6_1.npy``; inputs and weights are seeded, so two builds
+can be compared output for output.
 
 ``--cpu`` runs the same pipeline with no GPU (CPU ``frontend_sink`` model,
 system shm, gloo): the multi-rank CPU test of the launch/aggregation path.
@@ -40,7 +47,9 @@ segment ids) and broadcast to every rank, then each rank sweeps
 windows of max(64, 8 x concurrency) requests, aggregated over ranks.  The
 JSON ``value`` is the aggregate infer/s at the highest concurrency; every
 point is listed under ``sweep``.  (``--cpu`` covers it on the CPU with the
-``bert_sink`` shape model.)
+``bert_sink`` shape model.)  ``--dump-outputs DIR`` writes the last point's
+``start_logits.npy`` / ``end_logits.npy`` ([concurrency, 384]); ``--full``
+changes nothing here.
 """
 
 import argparse
@@ -66,6 +75,15 @@ def parse_args(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed headline steps also run every secondary measurement and check: the "
+                         "python-client sanity request, the per-slot output check, the p99-constrained probes, the "
+                         "bs=1 point, the bf16 engine and (multi-GPU) the fan-out timings.  Off: set up, warm up, "
+                         "time --steps steps, print the result line")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps write what they computed last, the fc6_1 logits of every concurrency "
+                         "slot ([slots, batch, 1000] float32, at most 64 MB: the leading slots), to DIR/fc6_1.npy "
+                         "(rank 0; inputs are seeded, so two builds can be compared output for output)")
     ap.add_argument("--batch", type=int, default=8, help="images per request (densenet_onnx bs)")
     ap.add_argument("--concurrency", type=int, default=48, help="requests in flight per GPU")
     ap.add_argument("--window", type=int, default=16, help="requests per step = window x concurrency")
@@ -412,8 +430,16 @@ def main():
     else:
         model = "frontend_sink" if cpu else "densenet_onnx"
     bs, conc = args.batch, args.concurrency
-    log_dir = os.path.join(REPO, "gpurun_out")
-    os.makedirs(log_dir, exist_ok=True)
+    # server logs: next to the sources, or (read-only checkout) in a temp dir
+    log_dir = os.path.join(REPO, "bench_logs")
+    try:
+        os.makedirs(log_dir, exist_ok=True)
+        if not os.access(log_dir, os.W_OK):
+            raise PermissionError(log_dir)
+    except OSError:
+        import tempfile
+
+        log_dir = tempfile.mkdtemp(prefix="bench_logs_")
 
     # host placement BEFORE the server is spawned (the child inherits it): the
     # CPUs of this rank's GPU's NUMA node, split among the ranks sharing it
@@ -565,12 +591,20 @@ def main():
         method, in_total = make_input("data_0_in", bs * nslots)
         in_bytes = req_bytes
         in_list = ["data_0_in@%d" % (i * req_bytes) for i in range(nslots)] if nslots > 1 else "data_0_in"
-        out_list = None
+        out_list = ro = None
+        ob = bs * 1000 * 4
         if not cpu:
-            ob = bs * 1000 * 4
             ro = shmod.create_shared_memory_region("fc6_1_out", nslots * ob, dev)
             regions.append(ro)
             client.register_cuda_shared_memory("fc6_1_out", shmod.get_raw_handle(ro), dev, nslots * ob)
+        elif args.dump_outputs:
+            # the CPU pipeline keeps its outputs in the load generator's own
+            # regions; a dump needs them where this process can read them
+            key = "/fc6_1_out_r%d_%d" % (rank, os.getpid())
+            ro = shmod.create_shared_memory_region("fc6_1_out", key, nslots * ob)
+            regions.append(ro)
+            client.register_system_shared_memory("fc6_1_out", key, nslots * ob)
+        if ro is not None:
             out_list = ["fc6_1_out@%d" % (i * ob) for i in range(nslots)]
 
         def slots(c, lo=0):
@@ -578,7 +612,8 @@ def main():
                 ({"fc6_1": out_list[lo:c]} if out_list else None)
 
         fan = {"method": method, "replicas_verified": True, "bytes": in_total}
-        if not cpu and world > 1:
+        full = args.full
+        if full and not cpu and world > 1:
             # X1 (RCCL broadcast) vs X2 (xGMI one-hop star), once, on the headline input
             # region; a rehearsal on one GPU times p2p and host staging
             fan["timings"] = fanout.time_fanout(
@@ -591,7 +626,7 @@ def main():
             if "us" in t_used:
                 fan["fanout_us"] = t_used["us"]
             log("fan-out timings: %s" % fan["timings"])
-        if not cpu:
+        if full and not cpu:
             _sanity_check(client, shmod, bs, dev, regions)
 
         # ---- headline: bs=8 -------------------------------------------------------
@@ -630,92 +665,100 @@ def main():
         breakdown["compute_us_per_request_weighted"] = round(wc, 1)
         breakdown["unattributed_us_per_request"] = round(
             breakdown["server_us_per_request"] - breakdown["queue_us_per_request"] - wc, 1)
-        # every slot's output slice must be the logits of ITS images (checked
-        # against the same server running that request alone, outside the timing)
-        slot_check = None if (cpu or out_list is None) else _verify_slots(client, shmod, regions, nslots, bs, dev)
+        if args.dump_outputs and rank == 0:
+            # before anything below writes the output slices again
+            _dump_outputs(args.dump_outputs, shmod, ro, nslots, bs)
 
-        # ---- best throughput with p99 <= 10 ms (same server, lower concurrency) ---------
-        p99c = {"p99_target_us": 10000.0, "points": [
-            {"concurrency": args.concurrency, "infer_per_sec": round(value, 1),
-             "p50_latency_us": round(percentile_us(all_lat, 50), 1),
-             "p99_latency_us": round(percentile_us(all_lat, 99), 1)}]}
-        if not cpu:
-            for c in (32, 24, 16):
-                ins_c, outs_c = slots(c)
-                pc = Point(srv, model, bs, c, None, in_bytes, dev, cpu, inputs=ins_c, outputs=outs_c)
-                points.append(pc)
-                perc = 16 * c
-                lc_, _, elc, ((sp0, bp0), (sp1, bp1)) = measure(
-                    pc, perc, 4, perc, snap=lambda: (pc.s.server_stats(), batch_stats(client, model)))
-                lg = fanout.gather_arrays(lc_.astype(np.int64)).astype(np.float64)
-                row = {"concurrency": c, "infer_per_sec": round(world * 4 * perc * bs / elc, 1),
-                       "p50_latency_us": round(percentile_us(lg, 50), 1),
-                       "p99_latency_us": round(percentile_us(lg, 99), 1)}
-                # why a probe lands where it does: rows per executed batch
-                # (how the c x bs rows in flight split into batches over the
-                # instances), queueing and device time per batch (rank 0)
-                bdp = stats_delta(sp0, sp1)
-                bdp["batch_rows_histogram"] = {str(k): int(bp1[k][0] - bp0.get(k, (0,))[0]) for k in sorted(bp1)
-                                               if bp1[k][0] - bp0.get(k, (0,))[0] > 0}
-                row["breakdown_rank0"] = bdp
-                p99c["points"].append(row)
-                log("p99-constrained probe c%d: %.0f infer/s p99 %.0f us" % (c, row["infer_per_sec"],
-                                                                             row["p99_latency_us"]))
-            ok = [r for r in p99c["points"] if r["p99_latency_us"] <= p99c["p99_target_us"]]
-            if ok:
-                best = max(ok, key=lambda r: r["infer_per_sec"])
-                p99c.update({"concurrency": best["concurrency"], "infer_per_sec": best["infer_per_sec"],
-                             "p99_latency_us": best["p99_latency_us"]})
+        slot_check = p99c = bs1 = None
+        if full:
+            # every slot's output slice must be the logits of ITS images (checked
+            # against the same server running that request alone, outside the timing)
+            slot_check = None if (cpu or out_list is None) else _verify_slots(client, shmod, regions, nslots, bs, dev)
 
-        # ---- bs=1 on the same server -------------------------------------------------
-        bs1_rows = bs1_preferred_rows(args.bs1_preferred, args.bs1_concurrency, args.instance_count)
-        if bs1_rows and not cpu:
-            # a deployment tuned for this load: the batcher's preferred size
-            # (Triton's dynamic_batching.preferred_batch_size) = the closed
-            # loop's rows per instance, so the loop settles into one full group
-            # per instance instead of ~3 groups of ~21 rows; applied to the
-            # loaded model by a repository load with a config override
-            client.load_model(model, config=json.dumps({"dynamic_batching": {"preferred_batch_size": bs1_rows}}))
-            log("bs=1 point: preferred batch rows %s" % bs1_rows)
-        _, in1 = make_input("data_1_in", 1)
-        nl = max(1, args.bs1_lanes)
-        if args.bs1_concurrency % nl:
-            raise SystemExit("--bs1-concurrency must be a multiple of --bs1-lanes")
-        p1 = Lanes([Point(srv, model, 1, args.bs1_concurrency // nl, "data_1_in", in1, dev, cpu) for _ in range(nl)])
-        points.extend(p1.points)
-        n1 = 64 * args.bs1_concurrency  # ~0.2 s at 20k infer/s: the batch groups of a closed loop need time to settle
-        l1, e1, el1, ((s10, b10), (s11, b11)) = measure(
-            p1, n1 // 4, 4, n1 // 4, snap=lambda: (p1.s.server_stats(), batch_stats(client, model)))
-        bs1 = {"concurrency": args.bs1_concurrency, "client_lanes": nl, "infer_per_sec": round(world * n1 / el1, 1),
-               "preferred_batch_rows": args.preferred if cpu or not bs1_rows else ",".join(map(str, bs1_rows))}
-        # where a bs=1 request's latency goes at this concurrency: rows per
-        # batch, queueing, and the request-weighted device time of its batch
-        bd64 = stats_delta(s10, s11)
-        bd64["client_overhead_us_per_request"] = round(float(np.mean(l1)) / 1e3 - bd64["server_us_per_request"], 1)
-        wc1 = weighted_compute_us(b10, b11, 1)
-        bd64["compute_us_per_request_weighted"] = round(wc1, 1)
-        bd64["unattributed_us_per_request"] = round(
-            bd64["server_us_per_request"] - bd64["queue_us_per_request"] - wc1, 1)
-        # executed batches by rows (a closed loop of 64 settles into groups: ~2 of ~32 or ~3 of ~21)
-        bd64["batch_rows_histogram"] = {str(k): int(b11[k][0] - b10.get(k, (0,))[0]) for k in sorted(b11)
-                                        if b11[k][0] - b10.get(k, (0,))[0] > 0}
-        bs1["breakdown_rank0"] = bd64
-        l1g = fanout.gather_arrays(l1.astype(np.int64)).astype(np.float64)
-        bs1.update({"p50_latency_us": round(percentile_us(l1g, 50), 1),
-                    "p99_latency_us": round(percentile_us(l1g, 99), 1)})
-        pc1 = Point(srv, model, 1, 1, "data_1_in", in1, dev, cpu)
-        points.append(pc1)
-        pc1.run(20)
-        sc0 = pc1.s.server_stats()
-        lc, _, _ = pc1.run(200)
-        sc1 = pc1.s.server_stats()
-        lcg = fanout.gather_arrays(lc.astype(np.int64)).astype(np.float64)
-        bs1["concurrency1_p50_latency_us"] = round(percentile_us(lcg, 50), 1)
-        bs1["concurrency1_p99_latency_us"] = round(percentile_us(lcg, 99), 1)
-        # where one bs=1 request's latency goes (server-stat deltas over the 200 requests)
-        bd1 = stats_delta(sc0, sc1)
-        bd1["client_overhead_us_per_request"] = round(float(np.mean(lc)) / 1e3 - bd1["server_us_per_request"], 1)
-        bs1["concurrency1_breakdown_rank0"] = bd1
+            # ---- best throughput with p99 <= 10 ms (same server, lower concurrency) ---------
+            p99c = {"p99_target_us": 10000.0, "points": [
+                {"concurrency": args.concurrency, "infer_per_sec": round(value, 1),
+                 "p50_latency_us": round(percentile_us(all_lat, 50), 1),
+                 "p99_latency_us": round(percentile_us(all_lat, 99), 1)}]}
+            if not cpu:
+                for c in (32, 24, 16):
+                    ins_c, outs_c = slots(c)
+                    pc = Point(srv, model, bs, c, None, in_bytes, dev, cpu, inputs=ins_c, outputs=outs_c)
+                    points.append(pc)
+                    perc = 16 * c
+                    lc_, _, elc, ((sp0, bp0), (sp1, bp1)) = measure(
+                        pc, perc, 4, perc, snap=lambda: (pc.s.server_stats(), batch_stats(client, model)))
+                    lg = fanout.gather_arrays(lc_.astype(np.int64)).astype(np.float64)
+                    row = {"concurrency": c, "infer_per_sec": round(world * 4 * perc * bs / elc, 1),
+                           "p50_latency_us": round(percentile_us(lg, 50), 1),
+                           "p99_latency_us": round(percentile_us(lg, 99), 1)}
+                    # why a probe lands where it does: rows per executed batch
+                    # (how the c x bs rows in flight split into batches over the
+                    # instances), queueing and device time per batch (rank 0)
+                    bdp = stats_delta(sp0, sp1)
+                    bdp["batch_rows_histogram"] = {str(k): int(bp1[k][0] - bp0.get(k, (0,))[0]) for k in sorted(bp1)
+                                                   if bp1[k][0] - bp0.get(k, (0,))[0] > 0}
+                    row["breakdown_rank0"] = bdp
+                    p99c["points"].append(row)
+                    log("p99-constrained probe c%d: %.0f infer/s p99 %.0f us" % (c, row["infer_per_sec"],
+                                                                                 row["p99_latency_us"]))
+                ok = [r for r in p99c["points"] if r["p99_latency_us"] <= p99c["p99_target_us"]]
+                if ok:
+                    best = max(ok, key=lambda r: r["infer_per_sec"])
+                    p99c.update({"concurrency": best["concurrency"], "infer_per_sec": best["infer_per_sec"],
+                                 "p99_latency_us": best["p99_latency_us"]})
+
+            # ---- bs=1 on the same server -------------------------------------------------
+            bs1_rows = bs1_preferred_rows(args.bs1_preferred, args.bs1_concurrency, args.instance_count)
+            if bs1_rows and not cpu:
+                # a deployment tuned for this load: the batcher's preferred size
+                # (Triton's dynamic_batching.preferred_batch_size) = the closed
+                # loop's rows per instance, so the loop settles into one full group
+                # per instance instead of ~3 groups of ~21 rows; applied to the
+                # loaded model by a repository load with a config override
+                client.load_model(model, config=json.dumps({"dynamic_batching": {"preferred_batch_size": bs1_rows}}))
+                log("bs=1 point: preferred batch rows %s" % bs1_rows)
+            _, in1 = make_input("data_1_in", 1)
+            nl = max(1, args.bs1_lanes)
+            if args.bs1_concurrency % nl:
+                raise SystemExit("--bs1-concurrency must be a multiple of --bs1-lanes")
+            p1 = Lanes([Point(srv, model, 1, args.bs1_concurrency // nl, "data_1_in", in1, dev, cpu)
+                        for _ in range(nl)])
+            points.extend(p1.points)
+            # ~0.2 s at 20k infer/s: the batch groups of a closed loop need time to settle
+            n1 = 64 * args.bs1_concurrency
+            l1, e1, el1, ((s10, b10), (s11, b11)) = measure(
+                p1, n1 // 4, 4, n1 // 4, snap=lambda: (p1.s.server_stats(), batch_stats(client, model)))
+            bs1 = {"concurrency": args.bs1_concurrency, "client_lanes": nl, "infer_per_sec": round(world * n1 / el1, 1),
+                   "preferred_batch_rows": args.preferred if cpu or not bs1_rows else ",".join(map(str, bs1_rows))}
+            # where a bs=1 request's latency goes at this concurrency: rows per
+            # batch, queueing, and the request-weighted device time of its batch
+            bd64 = stats_delta(s10, s11)
+            bd64["client_overhead_us_per_request"] = round(float(np.mean(l1)) / 1e3 - bd64["server_us_per_request"], 1)
+            wc1 = weighted_compute_us(b10, b11, 1)
+            bd64["compute_us_per_request_weighted"] = round(wc1, 1)
+            bd64["unattributed_us_per_request"] = round(
+                bd64["server_us_per_request"] - bd64["queue_us_per_request"] - wc1, 1)
+            # executed batches by rows (a closed loop of 64 settles into groups: ~2 of ~32 or ~3 of ~21)
+            bd64["batch_rows_histogram"] = {str(k): int(b11[k][0] - b10.get(k, (0,))[0]) for k in sorted(b11)
+                                            if b11[k][0] - b10.get(k, (0,))[0] > 0}
+            bs1["breakdown_rank0"] = bd64
+            l1g = fanout.gather_arrays(l1.astype(np.int64)).astype(np.float64)
+            bs1.update({"p50_latency_us": round(percentile_us(l1g, 50), 1),
+                        "p99_latency_us": round(percentile_us(l1g, 99), 1)})
+            pc1 = Point(srv, model, 1, 1, "data_1_in", in1, dev, cpu)
+            points.append(pc1)
+            pc1.run(20)
+            sc0 = pc1.s.server_stats()
+            lc, _, _ = pc1.run(200)
+            sc1 = pc1.s.server_stats()
+            lcg = fanout.gather_arrays(lc.astype(np.int64)).astype(np.float64)
+            bs1["concurrency1_p50_latency_us"] = round(percentile_us(lcg, 50), 1)
+            bs1["concurrency1_p99_latency_us"] = round(percentile_us(lcg, 99), 1)
+            # where one bs=1 request's latency goes (server-stat deltas over the 200 requests)
+            bd1 = stats_delta(sc0, sc1)
+            bd1["client_overhead_us_per_request"] = round(float(np.mean(lc)) / 1e3 - bd1["server_us_per_request"], 1)
+            bs1["concurrency1_breakdown_rank0"] = bd1
 
         res = {
             "metric": METRIC,
@@ -732,6 +775,7 @@ def main():
             "data": ("synthetic (host normal, fanned out by %s), no model weights (CPU frontend_sink)" % method if cpu
                      else "synthetic (K1 Philox normal on device: %d distinct images, %d per concurrency slot, "
                           "fanned out by %s), random-init weights" % (nslots * bs, bs, method)),
+            "full": full,  # False: p99_constrained, bs1, the bf16 engine and the output check were not run
             "config": {
                 "model": model,
                 "global_batch": world * conc * bs,
@@ -773,7 +817,7 @@ def main():
 
         # ---- bf16 engine: labelled reduced-precision operating point -------------------
         # (one GPU only: a multi-GPU scaling run stays on the headline engine)
-        if not cpu and not args.no_bf16 and args.engine == "fp32" and world == 1:
+        if full and not cpu and not args.no_bf16 and args.engine == "fp32" and world == 1:
             client.unregister_cuda_shared_memory()
             client.close()
             state["client"] = None
@@ -870,10 +914,30 @@ def bert_sweep(args, srv, model, client, shmod, regions, points, measure, fanout
         if not fanout.verify_replicas(regions[0], nbytes, over_cpu=method == fanout.LOCAL_FALLBACK):
             raise RuntimeError("fan-out replicas differ across ranks after the fan-out timing")
     sweep = []
+    concs = [int(v) for v in args.sweep.split(",") if v]
+    out_regs = {}
+    if args.dump_outputs:
+        # caller-owned output regions, one [384] fp32 slice per concurrency slot,
+        # so the last point's logits can be read back after the sweep
+        for name in ("start_logits", "end_logits"):
+            reg, size = "bert_%s_out" % name, max(concs) * nbytes
+            if cpu:
+                key = "/%s_r%d_%d" % (reg, rank, os.getpid())
+                r = shmod.create_shared_memory_region(reg, key, size)
+                client.register_system_shared_memory(reg, key, size)
+            else:
+                r = shmod.create_shared_memory_region(reg, size, local_rank)
+                client.register_cuda_shared_memory(reg, shmod.get_raw_handle(r), local_rank, size)
+            regions.append(r)
+            out_regs[name] = (reg, r)
+
+    def out_slots(lo, hi):
+        return {n: ["%s@%d" % (reg, s * nbytes) for s in range(lo, hi)] for n, (reg, _) in out_regs.items()} or None
+
     bert_max_batch = 64
     if not cpu:
         bert_max_batch = int(client.get_model_config(model, as_json=True)["config"].get("max_batch_size", 64))
-    for c in [int(v) for v in args.sweep.split(",") if v]:
+    for c in concs:
         # the batcher's preferred size for this load: one equal group per
         # instance (e.g. c16 on 2 instances ran as 5- and 11-row batches)
         n_inst = max(1, args.bert_instance_count)
@@ -888,10 +952,12 @@ def bert_sweep(args, srv, model, client, shmod, regions, points, measure, fanout
         nl = max(1, args.bert_lanes)
         if nl > 1 and c % nl == 0 and c >= 8 * nl:  # read-only input regions: the lanes may share them
             pt = Lanes([Point(srv, model, 1, c // nl, None, nbytes, local_rank, cpu, inputs=inputs,
-                              out_bytes=BERT_SEQ * 4) for _ in range(nl)])
+                              out_bytes=BERT_SEQ * 4, outputs=out_slots(i * c // nl, (i + 1) * c // nl))
+                        for i in range(nl)])
             points.extend(pt.points)
         else:
-            pt = Point(srv, model, 1, c, None, nbytes, local_rank, cpu, inputs=inputs, out_bytes=BERT_SEQ * 4)
+            pt = Point(srv, model, 1, c, None, nbytes, local_rank, cpu, inputs=inputs, out_bytes=BERT_SEQ * 4,
+                       outputs=out_slots(0, c))
         if isinstance(pt, Point):
             points.append(pt)
         per = max(64, 8 * c)
@@ -911,6 +977,13 @@ def bert_sweep(args, srv, model, client, shmod, regions, points, measure, fanout
         sweep.append(row)
         log("bert c%d: %.1f infer/s p99 %.0f us" % (c, row["infer_per_sec"], row["p99_latency_us"]))
     top = sweep[-1]
+    if out_regs and rank == 0:
+        # the headline point ran last: its slots' logits are what the regions hold
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, (_, r) in out_regs.items():
+            a = np.ascontiguousarray(shmod.get_contents_as_numpy(r, np.float32, [top["concurrency"], BERT_SEQ]))
+            np.save(os.path.join(args.dump_outputs, "%s.npy" % name), a)
+            log("wrote %s.npy %s" % (os.path.join(args.dump_outputs, name), list(a.shape)))
     res = {
         "metric": BERT_METRIC,
         "value": top["infer_per_sec"],
@@ -948,6 +1021,26 @@ def bert_sweep(args, srv, model, client, shmod, regions, points, measure, fanout
     if rank == 0:
         print(json.dumps(res), flush=True)
     return 0
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def _dump_outputs(out_dir, shm, region, nslots, bs):
+    """--dump-outputs: the output region as the timed loop left it.  Slice s
+    holds the fc6_1 logits of the last request concurrency slot s completed
+    (its own bs images, the same in every run), i.e. what a client of the
+    timed path reads back.  [slots, bs, 1000] float32; more than 64 MB is cut
+    to the leading slots."""
+    import numpy as np
+
+    keep = max(1, min(nslots, DUMP_LIMIT_BYTES // (bs * 1000 * 4)))
+    out = np.ascontiguousarray(shm.get_contents_as_numpy(region, np.float32, [nslots, bs, 1000])[:keep],
+                               dtype=np.float32)
+    os.makedirs(out_dir, exist_ok=True)
+    path = os.path.join(out_dir, "fc6_1.npy")
+    np.save(path, out)
+    log("wrote %s %s" % (path, list(out.shape)))
 
 
 def _verify_slots(client, hipshm, regions, nslots, bs, dev):

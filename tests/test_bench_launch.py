@@ -36,7 +36,7 @@ def _bench(*args, timeout=240):
 
 @pytest.mark.parametrize("gpus", [1, 2])
 def test_bench_spawns_ranks_and_aggregates(gpus):
-    res, err = _bench("--gpus", str(gpus), "--steps", "5")
+    res, err = _bench("--gpus", str(gpus), "--steps", "5", "--full")
     assert res["n_gpus"] == gpus
     assert res["world_size_reported_by_process_group"] == gpus
     assert res["config"]["parallelism"] == "dp%d" % gpus
@@ -58,11 +58,45 @@ def test_bench_bs1_over_two_client_lanes():
     """--lanes 2 / --bs1-lanes 2: the headline and bs=1 concurrencies split over
     two client connections / worker threads (disjoint concurrency slots); the
     JSON says so and the breakdowns still read the server's statistics."""
-    res, _ = _bench("--steps", "2", "--bs1-lanes", "2", "--lanes", "2")
+    res, _ = _bench("--steps", "2", "--bs1-lanes", "2", "--lanes", "2", "--full")
     assert res["bs1"]["client_lanes"] == 2 and res["bs1"]["concurrency"] == 4
     assert res["config"]["client_lanes"] == 2 and res["value"] > 0 and len(res["window_infer_per_sec_rank0"]) == 2
     assert res["bs1"]["infer_per_sec"] > 0 and res["bs1"]["p99_latency_us"] >= res["bs1"]["p50_latency_us"] > 0
     assert res["bs1"]["breakdown_rank0"]["avg_rows_per_batch"] >= 1
+
+
+def test_bench_plain_run_is_lean_and_dumps_its_outputs(tmp_path):
+    """Without --full only the headline is measured (the secondary points are
+    absent from the JSON), ``ms_per_step`` is the time of one of the --steps
+    timed steps, and --dump-outputs writes each concurrency slot's last fc6_1
+    logits: the same file from run to run (seeded inputs; frontend_sink
+    broadcasts each image's first value over its 1000 outputs)."""
+    import numpy as np
+
+    dumps = []
+    for d in ("a", "b"):
+        res, _ = _bench("--steps", "3", "--dump-outputs", str(tmp_path / d))
+        assert res["full"] is False and res["bs1"] is None and res["p99_constrained"] is None
+        assert res["steps"] == 3 and len(res["window_infer_per_sec_rank0"]) == 3
+        # value = images of the 3 timed steps / their time: 16 x 4 requests of 8 images per step
+        assert res["value"] * res["ms_per_step"] / 1e3 == pytest.approx(16 * 4 * 8, rel=1e-3)
+        assert os.listdir(tmp_path / d) == ["fc6_1.npy"]
+        dumps.append(np.load(tmp_path / d / "fc6_1.npy"))
+    a, b = dumps
+    assert a.dtype == np.float32 and a.shape == (4, 8, 1000)
+    assert np.array_equal(a, b)
+    x = np.random.default_rng(1234).standard_normal(4 * 8 * 3 * 224 * 224, dtype=np.float32)
+    assert np.array_equal(a, np.repeat(x.reshape(4, 8, -1)[:, :, :1], 1000, axis=2))
+
+
+def test_bench_bert_sweep_dumps_the_top_point(tmp_path):
+    res, _ = _bench("--steps", "2", "--model", "bert_large", "--sweep", "1,4", "--dump-outputs", str(tmp_path))
+    import numpy as np
+
+    assert res["sweep"][-1]["concurrency"] == 4 and res["ms_per_step"] == res["sweep"][-1]["ms_per_step"]
+    # bert_sink: start = the (all-ones) mask as float, end = its negation
+    assert np.array_equal(np.load(tmp_path / "start_logits.npy"), np.ones((4, 384), np.float32))
+    assert np.array_equal(np.load(tmp_path / "end_logits.npy"), -np.ones((4, 384), np.float32))
 
 
 @pytest.mark.slow

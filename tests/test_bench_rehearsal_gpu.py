@@ -29,7 +29,7 @@ def test_bench_two_ranks_rehearsed_on_one_gpu():
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--rehearse", "--steps", "2",
            "--warmup", "1", "--window", "4", "--no-bf16", "--instance-count", "2", "--max-batch-size", "32",
-           "--preferred", "32", "--bs1-concurrency", "8"]
+           "--preferred", "32", "--bs1-concurrency", "8", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=850, env=env, cwd=REPO)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -51,6 +51,31 @@ def test_bench_two_ranks_rehearsed_on_one_gpu():
     # every p99-constrained probe says how its rows split into batches
     for p in res["p99_constrained"]["points"][1:]:
         assert sum(p["breakdown_rank0"]["batch_rows_histogram"].values()) > 0
+
+
+@pytest.mark.timeout(300)
+def test_bench_plain_run_dumps_served_logits(tmp_path):
+    """A plain one-GPU run (no --full): the headline only, and --dump-outputs
+    reads the HIP shm output region back: every concurrency slot's logits for
+    its own images, finite, and different from slot to slot."""
+    np = pytest.importorskip("numpy")
+    torch = pytest.importorskip("torch")
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
+    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+           "--window", "4", "--concurrency", "6", "--max-batch-size", "32", "--preferred", "32",
+           "--dump-outputs", str(tmp_path)]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=280, env=env, cwd=REPO)
+    assert r.returncode == 0, r.stderr[-3000:]
+    res = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
+    assert res["full"] is False and res["bs1"] is None and "bf16_engine_infer_per_sec" not in res
+    assert res["ms_per_step"] > 0 and res["value"] * res["ms_per_step"] / 1e3 == pytest.approx(4 * 6 * 8, rel=1e-3)
+    out = np.load(tmp_path / "fc6_1.npy")
+    assert out.dtype == np.float32 and out.shape == (6, 8, 1000) and np.isfinite(out).all()
+    rows = out.reshape(48, 1000)
+    assert np.linalg.norm(rows.astype(np.float64), axis=1).min() > 0
+    assert len({row.tobytes() for row in rows}) == 48
 
 
 @pytest.mark.timeout(900)

@@ -8,7 +8,7 @@
 # time limit, and the script stops at the first failing step (no retries).
 #   tests [pytest args...]     GPU suite (e.g. "tests -k executor")   -> gpurun_out/gpu_tests.log
 #   smoke                      __graft_entry__.smoke()                 -> gpurun_out/smoke.log
-#   bench [bench.py args...]   bench.py (JSON line on stdout)          -> gpurun_out/bench<N>.log/.err
+#   bench [bench.py args...]   bench.py (JSON line on stdout; "bench --full" adds the bs=1 / p99 / bf16 points) -> bench<N>.log/.err
 #   bert [bench.py args...]    bench.py --model bert_large             -> gpurun_out/bench_bert.log
 #   py <script> [args...]      python tools/<script> (probes, kbench)  -> gpurun_out/py_<script>.log
 #   prof <tag> <cmd...>        rocprofv3 --kernel-trace --stats on <cmd> -> gpurun_out/prof_<tag>/

@@ -2865,6 +2865,21 @@ int tcamd_x3_small_tiles(int imgs, int W) {
   return o[n - 1];
 }
 
+// ... when `streams` concurrent streams (a server's model instances) share
+// the chip.  A K14x workgroup holds a whole CU (128 KB of LDS) and at 7x7 its
+// cost is mostly fixed, not proportional to its pixels (bs128: whole images
+// 10.2-20.2 us a layer on 128 workgroups, halves 9.2-18.0 us on 256), so once
+// this stream's images alone fill its share of the CUs, whole images (1 tile)
+// cost the least CU-time and leave the other CUs to the other streams: bs128
+// x 2 streams +3 % (profiles/r7_k14x_whole.md).  Not at 14x14: two streams
+// there are bound by the bytes of X, not by CU-time (a whole-image kernel
+// measured the same as halves).  One stream, and fewer images: the rule above.
+int tcamd_x3_small_tiles_shared(int imgs, int W, int streams) {
+  const int padded = (imgs + 7) / 8 * 8;
+  if (W == 7 && streams >= 2 && padded >= cu_count() / streams) return 1;
+  return tcamd_x3_small_tiles(imgs, W);
+}
+
 // K14x: one dense layer of the 14x14 or 7x7 block in one kernel, `tiles`
 // tiles per image (14x14: 2, 4 or 7, 7x7: 1, 2, 4 or 7; <= 0: the chip-filling
 // default above); w1 in x3_w1_fragments, w2 in x3_w3f_fragments.  K a

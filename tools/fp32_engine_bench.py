@@ -101,6 +101,8 @@ def main():
                     ms = 1000 * dt / args.iters
                     r = {"engine": name, "variant": vname, "batch": b, "streams": ns, "ms_per_round": round(ms, 3),
                          "img_per_s": round(ns * b * args.iters / dt, 1)}
+                    if args.rounds > 1:  # every round, in run order: the spread an A/B has to clear
+                        r["img_per_s_rounds"] = [round(ns * b * args.iters / t, 1) for t in ts[vname]]
                     rows.append(r)
                     print(json.dumps(r), flush=True)
             graphs = None

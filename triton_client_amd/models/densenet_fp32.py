@@ -148,6 +148,11 @@ class FusedDenseNetFP32:
         self.concurrent_streams = 1
         # tiles per image for K14x: 0 = the library's chip-filling choice
         self.smallf_tiles = int(os.environ.get("TCAMD_X3_SMALLF_TILES", "0"))
+        # ... 1: whole 7x7 images once this stream's batch alone fills its share
+        # of the CUs (concurrent_streams >= 2; x3_small_tiles_shared): bs128 on
+        # two streams, +3 %; 0 = the one-stream choice on every stream (A/B
+        # runs; profiles/r7_k14x_whole.md)
+        self.smallf_shared = int(os.environ.get("TCAMD_X3_SMALLF_SHARED", "1"))
         self._alloc(max_batch)
 
     def _alloc(self, n):
@@ -309,10 +314,14 @@ class FusedDenseNetFP32:
         """K14x row tiles per image: TCAMD_X3_SMALLF_TILES, else the native
         chip-filling choice, except that the 7-tile split of small 14x14 batches
         must fit one round of this stream's share of the CUs (on 2 streams at
-        bs32 it oversubscribes them: -5.6 %, profiles/r5_k14x_tiles.md)."""
+        bs32 it oversubscribes them: -5.6 %, profiles/r5_k14x_tiles.md), and
+        that a 7x7 batch that fills this stream's share of the CUs by itself
+        runs whole images (x3_small_tiles_shared; TCAMD_X3_SMALLF_SHARED=0: not)."""
         if self.smallf_tiles:
             return self.smallf_tiles
-        return stream_share_tiles(hip.x3_small_tiles(b, hw), b, _cu_count(self.device), self.concurrent_streams)
+        streams = self.concurrent_streams if self.smallf_shared else 1
+        return stream_share_tiles(hip.x3_small_tiles_shared(b, hw, streams), b, _cu_count(self.device),
+                                  self.concurrent_streams)
 
     def _small_fused(self, b, hw):
         thr = self.smallf_min_blocks

@@ -224,6 +224,7 @@ _SIGS = {
         ctypes.c_int,
     ),
     "tcamd_x3_small_tiles": ([ctypes.c_int, ctypes.c_int], ctypes.c_int),
+    "tcamd_x3_small_tiles_shared": ([ctypes.c_int, ctypes.c_int, ctypes.c_int], ctypes.c_int),
     "tcamd_x3_dense_fused_ws": (
         [
             ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
@@ -830,6 +831,13 @@ def x3_dense_small(x, ldx, imgs, H, W, K, s1, t1, w1f_hi, w1f_lo, b1, w2_hi, w2_
 def x3_small_tiles(imgs, W):
     """The tiles per image K14x picks for ``imgs`` images of side ``W``."""
     return int(_load().tcamd_x3_small_tiles(int(imgs), int(W)))
+
+
+def x3_small_tiles_shared(imgs, W, streams):
+    """:func:`x3_small_tiles` for one of ``streams`` concurrent streams: whole
+    7x7 images (1 tile) once this stream's images alone fill its share of the
+    CUs; on one stream, below that, and at 14x14 the same answer."""
+    return int(_load().tcamd_x3_small_tiles_shared(int(imgs), int(W), int(streams)))
 
 
 def x3_dense_fused3(x, ldx, imgs, H, W, K, s1, t1, w1_hi, w1_lo, b1, w2_hi, w2_lo, y, ldy, stream=None):

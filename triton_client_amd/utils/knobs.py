@@ -62,6 +62,10 @@ KNOBS = [
     Knob("TCAMD_X3_SMALLF_TILES", "python", 0, "FP32DenseNet.smallf_tiles",
          "K14x row tiles per image; 0 = the chip-filling choice (x3_small_tiles)",
          _DF + "test_fp32_engine_routing_knobs"),
+    Knob("TCAMD_X3_SMALLF_SHARED", "python", 1, "FP32DenseNet.smallf_shared",
+         "K14x whole 7x7 images when a batch fills its stream's share of the CUs (server instances >= 2); "
+         "0 = the one-stream tiling on every stream",
+         "tests/test_k14x_whole_gpu.py::test_engine_tiles_follow_the_shared_rule"),
     # ---- python: BERT ----
     Knob("TC_BERT_FUSED", "python", 1, "models/bert.py FUSED",
          "K11 / K12 fused kernels on the GPU; 0 = plain torch ops", "tests/test_bert_kernels_gpu.py::test_bert_fused_layers_match_torch_ops"),

@@ -23,7 +23,7 @@ $(CSHM): csrc/cshm/cshm.cc
 	@mkdir -p $(dir $@)
 	$(CXX) $(CXXFLAGS) -shared -o $@ $< -lrt
 
-build/%.o: csrc/%.hip $(wildcard csrc/kernels/*.h) $(wildcard csrc/hipshm/*.h) csrc/cpp/server/tcserve.h
+build/%.o: csrc/%.hip $(wildcard csrc/kernels/*.h) $(wildcard csrc/hipshm/*.h) csrc/cpp/server/tcserve.h csrc/cpp/server/classify.h
 	@mkdir -p $(dir $@)
 	$(HIPCC) $(HIPFLAGS) -Icsrc -c -o $@ $<
 

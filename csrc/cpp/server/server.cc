@@ -35,6 +35,7 @@
 #include "net.h"
 #include "tcserve.h"
 #include "batch_policy.h"
+#include "classify.h"
 #include "trace.h"
 
 namespace tcserve {
@@ -121,6 +122,12 @@ struct PendingReq {
   std::vector<std::string> out_region;
   std::vector<int64_t> out_region_bytes, out_region_offset;
   std::vector<std::string> host_out;  // host output buffers (non-shm)
+  // classification extension, per output: class_k = min(requested k, classes), 0 = raw tensor;
+  // class_pairs: the executor fills host_out with {score, index} pairs (top-K capable model)
+  // instead of the raw tensor; class_shm_ptr: system-shm destination of the serialized strings
+  std::vector<int32_t> class_k;
+  std::vector<bool> class_pairs;
+  std::vector<uint64_t> class_shm_ptr;
   std::string body;                   // request message; raw inputs point into it
   std::vector<std::pair<int, size_t>> host_in_off;  // (input index, offset of its bytes in body)
   std::vector<std::shared_ptr<int>> pins;            // shm regions this request reads/writes
@@ -150,6 +157,10 @@ struct NativeModel {
   std::vector<TensorDef> inputs, outputs;
   tcserve_exec_fn fn = nullptr;
   void* user = nullptr;
+  // classification extension (under mu): the executor honours tcserve_batch::class_counts;
+  // labels per output (null = none)
+  bool topk_capable = false;
+  std::vector<std::shared_ptr<const std::vector<std::string>>> labels;
   // batcher
   std::mutex mu;
   std::condition_variable cv;
@@ -341,6 +352,9 @@ class Server {
   void Worker(std::shared_ptr<NativeModel> m, int instance);
   void Execute(const std::shared_ptr<NativeModel>& ms, int instance, std::vector<std::unique_ptr<PendingReq>>& batch);
   static std::string HttpInferResponse(NativeModel* m, PendingReq* pr);
+  static void FinishClassification(NativeModel* m, PendingReq* pr,
+                                   const std::vector<std::shared_ptr<const std::vector<std::string>>>& labels,
+                                   std::string* err);
 
   int port_ = 0, http_port_ = 0;
   std::string up_host_, up_http_host_;
@@ -1267,6 +1281,11 @@ bool Server::TryNativeHttp(Loop* loop, uint64_t conn_id, uint64_t seq, bool clos
     m = it->second;
   }
   if (!version.empty() && version != m->version) return false;
+  bool topk_capable;
+  {
+    std::lock_guard<std::mutex> lk(m->mu);
+    topk_capable = m->topk_capable;
+  }
   namespace js = tc::json;
   js::Value root;
   std::string perr;
@@ -1384,6 +1403,9 @@ bool Server::TryNativeHttp(Loop* loop, uint64_t conn_id, uint64_t seq, bool clos
   pr->out_region_bytes.assign(no, 0);
   pr->out_region_offset.assign(no, 0);
   pr->host_out.resize(no);
+  pr->class_k.assign(no, 0);
+  pr->class_pairs.assign(no, false);
+  pr->class_shm_ptr.assign(no, 0);
   const js::Value* outputs = root.Find("outputs");
   pr->out_requested.assign(no, !outputs || outputs->Size() == 0);
   if (!outputs || outputs->Size() == 0) {
@@ -1399,7 +1421,8 @@ bool Server::TryNativeHttp(Loop* loop, uint64_t conn_id, uint64_t seq, bool clos
       pr->out_requested[idx] = true;
       std::string region;
       int64_t rbytes = 0, roff = 0;
-      bool has_shm = false, binary = binary_out_default;
+      bool has_shm = false, binary = binary_out_default, has_class = false;
+      int64_t class_k = 0;
       if (const js::Value* op = o.Find("parameters")) {
         for (const auto& kv : op->Members()) {
           if (kv.first == "shared_memory_region") {
@@ -1411,19 +1434,28 @@ bool Server::TryNativeHttp(Loop* loop, uint64_t conn_id, uint64_t seq, bool clos
             roff = kv.second.AsInt();
           } else if (kv.first == "binary_data") {
             binary = kv.second.AsBool();
+          } else if (kv.first == "classification") {
+            has_class = true;
+            class_k = kv.second.AsInt();
           } else {
-            return false;  // classification
+            return false;
           }
         }
       }
+      // classification: FP32 outputs with k >= 1 only; the rest is the Python server's
+      if (has_class && (class_k < 1 || m->outputs[idx].dtype != "FP32")) return false;
       const uint64_t need = static_cast<uint64_t>(pr->rows) * m->outputs[idx].sample_bytes;
       if (has_shm) {
         ShmEntry e;
         const int kind = lookup(region, &e);
         if (kind < 0) return fail("Unable to find shared memory region: '" + region + "'");
+        if (has_class && kind != 0) return false;  // strings into a device region: Python server
         if (!ShmRangeOk(roff, rbytes, e.bytes))
           return fail("Invalid offset + byte size for shared memory region: '" + region + "'");
-        if (static_cast<uint64_t>(rbytes) < need)
+        if (has_class) {
+          // the serialized size is known after the batch ran: checked in Execute
+          pr->class_shm_ptr[idx] = e.ptr + roff;
+        } else if (static_cast<uint64_t>(rbytes) < need)
           return fail("shared memory size specified with the request for output '" + m->outputs[idx].name + "' (" +
                       std::to_string(rbytes) + " bytes) should be at least " + std::to_string(need) + " bytes");
         pr->out[idx] = tcserve_ref{kind, e.device, e.ptr + roff, need};
@@ -1435,11 +1467,19 @@ bool Server::TryNativeHttp(Loop* loop, uint64_t conn_id, uint64_t seq, bool clos
       } else if (!binary) {
         return false;  // JSON output data: Python server
       }
+      if (has_class)
+        pr->class_k[idx] = static_cast<int32_t>(
+            std::min<int64_t>(class_k, static_cast<int64_t>(m->outputs[idx].sample_bytes / 4)));
     }
   }
   for (size_t k = 0; k < no; ++k) {
-    if (pr->out_requested[k] && !pr->out_shm[k]) {
-      const uint64_t need = static_cast<uint64_t>(pr->rows) * m->outputs[k].sample_bytes;
+    if (pr->out_requested[k] && (!pr->out_shm[k] || pr->class_k[k])) {
+      uint64_t need = static_cast<uint64_t>(pr->rows) * m->outputs[k].sample_bytes;
+      if (pr->class_k[k] && topk_capable) {
+        // the executor selects: {score, index} pairs instead of the raw tensor
+        pr->class_pairs[k] = true;
+        need = static_cast<uint64_t>(pr->rows) * static_cast<uint64_t>(pr->class_k[k]) * sizeof(ClassPair);
+      }
       pr->host_out[k].resize(need);
       pr->out[k] = tcserve_ref{0, 0, reinterpret_cast<uint64_t>(&pr->host_out[k][0]), need};
     }
@@ -1478,15 +1518,19 @@ std::string Server::HttpInferResponse(NativeModel* m, PendingReq* pr)
     js += first ? "{\"name\":" : ",{\"name\":";
     first = false;
     tc::json::AppendEscapedString(&js, d.name);
-    js += ",\"datatype\":\"" + d.dtype + "\",\"shape\":[";
+    js += ",\"datatype\":\"" + (pr->class_k[k] ? std::string("BYTES") : d.dtype) + "\",\"shape\":[";
     bool fd = true;
     if (m->max_batch > 0) {
       js += std::to_string(pr->rows);
       fd = false;
     }
-    for (auto dim : d.dims) {
-      js += (fd ? "" : ",") + std::to_string(dim);
-      fd = false;
+    if (pr->class_k[k]) {
+      js += (fd ? "" : ",") + std::to_string(pr->class_k[k]);
+    } else {
+      for (auto dim : d.dims) {
+        js += (fd ? "" : ",") + std::to_string(dim);
+        fd = false;
+      }
     }
     js += "],\"parameters\":{";
     if (pr->out_shm[k]) {
@@ -1808,6 +1852,11 @@ bool Server::TryNative(Conn* c, Stream* st, const char* msg, size_t len, std::st
     m = it->second;
   }
   if (!req.model_version().empty() && req.model_version() != m->version) return false;
+  bool topk_capable;
+  {
+    std::lock_guard<std::mutex> lk(m->mu);
+    topk_capable = m->topk_capable;
+  }
   // features the fast path leaves to the Python server
   for (const auto& kv : req.parameters())
     if (kv.first != "triton_enable_empty_final_response" && kv.first != "priority" && kv.first != "timeout")
@@ -1913,6 +1962,9 @@ bool Server::TryNative(Conn* c, Stream* st, const char* msg, size_t len, std::st
   pr->out_region_bytes.assign(no, 0);
   pr->out_region_offset.assign(no, 0);
   pr->host_out.resize(no);
+  pr->class_k.assign(no, 0);
+  pr->class_pairs.assign(no, false);
+  pr->class_shm_ptr.assign(no, 0);
   for (int i = 0; i < req.outputs_size(); ++i) {
     const auto& o = req.outputs(i);
     int idx = -1;
@@ -1922,7 +1974,8 @@ bool Server::TryNative(Conn* c, Stream* st, const char* msg, size_t len, std::st
     pr->out_requested[idx] = true;
     std::string region;
     int64_t rbytes = 0, roff = 0;
-    bool has_shm = false;
+    bool has_shm = false, has_class = false;
+    int64_t class_k = 0;
     for (const auto& kv : o.parameters()) {
       if (kv.first == "shared_memory_region") {
         region = kv.second.string_param();
@@ -1932,10 +1985,15 @@ bool Server::TryNative(Conn* c, Stream* st, const char* msg, size_t len, std::st
       } else if (kv.first == "shared_memory_offset") {
         roff = kv.second.int64_param();
       } else if (kv.first == "binary_data") {
+      } else if (kv.first == "classification") {
+        has_class = true;
+        class_k = kv.second.int64_param();
       } else {
-        return false;  // classification etc.
+        return false;
       }
     }
+    // classification: FP32 outputs with k >= 1 only; the rest is the Python server's
+    if (has_class && (class_k < 1 || m->outputs[idx].dtype != "FP32")) return false;
     const uint64_t need = static_cast<uint64_t>(pr->rows) * m->outputs[idx].sample_bytes;
     if (has_shm) {
       ShmEntry e;
@@ -1951,9 +2009,13 @@ bool Server::TryNative(Conn* c, Stream* st, const char* msg, size_t len, std::st
         }
       }
       if (kind < 0) return fail("Unable to find shared memory region: '" + region + "'");
+      if (has_class && kind != 0) return false;  // strings into a device region: Python server
       if (!ShmRangeOk(roff, rbytes, e.bytes))
         return fail("Invalid offset + byte size for shared memory region: '" + region + "'");
-      if (static_cast<uint64_t>(rbytes) < need)
+      if (has_class) {
+        // the serialized size is known after the batch ran: checked in Execute
+        pr->class_shm_ptr[idx] = e.ptr + roff;
+      } else if (static_cast<uint64_t>(rbytes) < need)
         return fail("shared memory size specified with the request for output '" + m->outputs[idx].name + "' (" +
                     std::to_string(rbytes) + " bytes) should be at least " + std::to_string(need) + " bytes");
       pr->out[idx] = tcserve_ref{kind, e.device, e.ptr + roff, need};
@@ -1963,10 +2025,18 @@ bool Server::TryNative(Conn* c, Stream* st, const char* msg, size_t len, std::st
       pr->out_region_bytes[idx] = rbytes;
       pr->out_region_offset[idx] = roff;
     }
+    if (has_class)
+      pr->class_k[idx] = static_cast<int32_t>(
+          std::min<int64_t>(class_k, static_cast<int64_t>(m->outputs[idx].sample_bytes / 4)));
   }
   for (size_t k = 0; k < no; ++k) {
-    if (pr->out_requested[k] && !pr->out_shm[k]) {
-      const uint64_t need = static_cast<uint64_t>(pr->rows) * m->outputs[k].sample_bytes;
+    if (pr->out_requested[k] && (!pr->out_shm[k] || pr->class_k[k])) {
+      uint64_t need = static_cast<uint64_t>(pr->rows) * m->outputs[k].sample_bytes;
+      if (pr->class_k[k] && topk_capable) {
+        // the executor selects: {score, index} pairs instead of the raw tensor
+        pr->class_pairs[k] = true;
+        need = static_cast<uint64_t>(pr->rows) * static_cast<uint64_t>(pr->class_k[k]) * sizeof(ClassPair);
+      }
       pr->host_out[k].resize(need);
       pr->out[k] = tcserve_ref{0, 0, reinterpret_cast<uint64_t>(&pr->host_out[k][0]), need};
     }
@@ -2061,6 +2131,47 @@ void Server::Worker(std::shared_ptr<NativeModel> m, int instance)
   }
 }
 
+// After a successful batch: turn each classification output of `pr` into the
+// serialized "score:index[:label]" strings.  host_out holds either the pairs
+// a top-K capable executor wrote or the raw tensor (selected here); the
+// strings replace it, or go to the request's system-shm region.
+void Server::FinishClassification(NativeModel* m, PendingReq* pr,
+                                  const std::vector<std::shared_ptr<const std::vector<std::string>>>& labels,
+                                  std::string* err)
+{
+  for (size_t k = 0; k < m->outputs.size(); ++k) {
+    const int64_t ck = pr->class_k[k];
+    if (!ck) continue;
+    const int64_t C = static_cast<int64_t>(m->outputs[k].sample_bytes / 4);
+    const int64_t count = static_cast<int64_t>(pr->rows) * ck;
+    std::vector<ClassPair> sel;
+    const ClassPair* pairs;
+    if (pr->class_pairs[k]) {
+      pairs = reinterpret_cast<const ClassPair*>(pr->host_out[k].data());
+    } else {
+      sel.resize(static_cast<size_t>(count));
+      const float* raw = reinterpret_cast<const float*>(pr->host_out[k].data());
+      for (int64_t r = 0; r < pr->rows; ++r) TopKRow(raw + r * C, C, ck, sel.data() + r * ck);
+      pairs = sel.data();
+    }
+    std::string ser;
+    ser.reserve(static_cast<size_t>(count) * 24);
+    SerializeClasses(pairs, count, k < labels.size() ? labels[k].get() : nullptr, &ser);
+    if (pr->out_shm[k]) {
+      if (static_cast<uint64_t>(pr->out_region_bytes[k]) < ser.size()) {
+        *err = "shared memory size specified with the request for output '" + m->outputs[k].name + "' (" +
+               std::to_string(pr->out_region_bytes[k]) + " bytes) should be at least " + std::to_string(ser.size()) +
+               " bytes";
+        return;
+      }
+      memcpy(reinterpret_cast<void*>(pr->class_shm_ptr[k]), ser.data(), ser.size());
+      pr->host_out[k].clear();
+    } else {
+      pr->host_out[k] = std::move(ser);
+    }
+  }
+}
+
 void Server::Execute(const std::shared_ptr<NativeModel>& ms, int instance,
                      std::vector<std::unique_ptr<PendingReq>>& batch)
 {
@@ -2069,12 +2180,21 @@ void Server::Execute(const std::shared_ptr<NativeModel>& ms, int instance,
   const size_t ni = m->inputs.size(), no = m->outputs.size();
   std::vector<int32_t> rows(n);
   std::vector<tcserve_ref> ins(n * ni), outs(n * no);
+  std::vector<int32_t> class_counts;  // filled only when a request wants pairs from the executor
+  bool any_class = false;
   int total = 0;
   for (int r = 0; r < n; ++r) {
     rows[r] = batch[r]->rows;
     total += rows[r];
     for (size_t k = 0; k < ni; ++k) ins[r * ni + k] = batch[r]->in[k];
-    for (size_t k = 0; k < no; ++k) outs[r * no + k] = batch[r]->out[k];
+    for (size_t k = 0; k < no; ++k) {
+      outs[r * no + k] = batch[r]->out[k];
+      if (batch[r]->class_k[k]) any_class = true;
+      if (batch[r]->class_pairs[k]) {
+        if (class_counts.empty()) class_counts.assign(n * no, 0);
+        class_counts[r * no + k] = batch[r]->class_k[k];
+      }
+    }
   }
   uint64_t timing[3] = {0, 0, 0};
   tcserve_batch b;
@@ -2086,6 +2206,7 @@ void Server::Execute(const std::shared_ptr<NativeModel>& ms, int instance,
   b.n_outputs = static_cast<int32_t>(no);
   b.outputs = outs.data();
   b.timing_ns = timing;
+  b.class_counts = class_counts.empty() ? nullptr : class_counts.data();
   char err[1024] = {0};
   const uint64_t t_exec = NowNs();
   int rc;
@@ -2094,6 +2215,18 @@ void Server::Execute(const std::shared_ptr<NativeModel>& ms, int instance,
     snprintf(tag, sizeof(tag), "tcserve.batch %s inst=%d requests=%d rows=%d", m->name.c_str(), instance, n, total);
     triton::client::trace::Range range(tag);
     rc = m->fn(m->user, instance, &b, err, sizeof(err));
+  }
+  // classification outputs: select on the host where the executor did not,
+  // format, and put the BYTES wire form where the raw tensor would have gone
+  std::vector<std::string> class_err(n);
+  if (rc == 0 && any_class) {
+    std::vector<std::shared_ptr<const std::vector<std::string>>> labels;
+    {
+      std::lock_guard<std::mutex> lk(m->mu);
+      labels = m->labels;
+    }
+    for (int r = 0; r < n; ++r)
+      FinishClassification(m, batch[r].get(), labels, &class_err[r]);
   }
   const uint64_t t_done = NowNs();
   {
@@ -2116,8 +2249,9 @@ void Server::Execute(const std::shared_ptr<NativeModel>& ms, int instance,
     m->last_inference_ms =
         std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::system_clock::now().time_since_epoch())
             .count();
-    for (auto& pr : batch) {
-      Stat& s = rc == 0 ? m->success : m->fail;
+    for (int r = 0; r < n; ++r) {
+      auto& pr = batch[r];
+      Stat& s = rc == 0 && class_err[r].empty() ? m->success : m->fail;
       s.count++;
       s.ns += t_done - pr->t_arrive;
       if (rc == 0) {
@@ -2126,9 +2260,14 @@ void Server::Execute(const std::shared_ptr<NativeModel>& ms, int instance,
       }
     }
   }
-  for (auto& pr : batch) {
+  for (int r = 0; r < n; ++r) {
+    auto& pr = batch[r];
     if (rc != 0) {
       FailPending(pr.get(), kInternal, 500, err);
+      continue;
+    }
+    if (!class_err[r].empty()) {
+      FailPending(pr.get(), kInvalidArgument, 400, class_err[r]);
       continue;
     }
     if (pr->http) {
@@ -2158,9 +2297,15 @@ void Server::Execute(const std::shared_ptr<NativeModel>& ms, int instance,
       const int k = order[j];
       auto* o = resp.add_outputs();
       o->set_name(m->outputs[k].name);
-      o->set_datatype(m->outputs[k].dtype);
-      if (m->max_batch > 0) o->add_shape(pr->rows);
-      for (auto d : m->outputs[k].dims) o->add_shape(d);
+      if (pr->class_k[k]) {
+        o->set_datatype("BYTES");
+        if (m->max_batch > 0) o->add_shape(pr->rows);
+        o->add_shape(pr->class_k[k]);
+      } else {
+        o->set_datatype(m->outputs[k].dtype);
+        if (m->max_batch > 0) o->add_shape(pr->rows);
+        for (auto d : m->outputs[k].dims) o->add_shape(d);
+      }
       if (pr->out_shm[k]) {
         (*o->mutable_parameters())["shared_memory_region"].set_string_param(pr->out_region[k]);
         (*o->mutable_parameters())["shared_memory_byte_size"].set_int64_param(pr->out_region_bytes[k]);
@@ -2578,6 +2723,60 @@ int32_t tcserve_set_preferred(void* server, const char* name, const int32_t* siz
   std::sort(v.begin(), v.end());
   std::lock_guard<std::mutex> lk(m->mu);
   m->preferred = std::move(v);
+  return 0;
+}
+
+int32_t tcserve_set_topk_capable(void* server, const char* name, int32_t on)
+{
+  Server* s = static_cast<Server*>(server);
+  std::shared_ptr<NativeModel> m;
+  {
+    std::lock_guard<std::mutex> lk(s->models_mu);
+    auto it = s->models.find(name);
+    if (it == s->models.end()) return 1;
+    m = it->second;
+  }
+  std::lock_guard<std::mutex> lk(m->mu);
+  m->topk_capable = on != 0;
+  return 0;
+}
+
+int32_t tcserve_set_labels(void* server, const char* name, int32_t output_index, const char** labels, int32_t n)
+{
+  Server* s = static_cast<Server*>(server);
+  std::shared_ptr<NativeModel> m;
+  {
+    std::lock_guard<std::mutex> lk(s->models_mu);
+    auto it = s->models.find(name);
+    if (it == s->models.end()) return 1;
+    m = it->second;
+  }
+  if (output_index < 0 || output_index >= static_cast<int32_t>(m->outputs.size()) || n < 0 || (n && !labels)) return 1;
+  std::shared_ptr<std::vector<std::string>> v;
+  if (n) {
+    v = std::make_shared<std::vector<std::string>>();
+    for (int32_t i = 0; i < n; ++i) v->emplace_back(labels[i] ? labels[i] : "");
+  }
+  std::lock_guard<std::mutex> lk(m->mu);
+  m->labels.resize(m->outputs.size());
+  m->labels[output_index] = v;
+  return 0;
+}
+
+int32_t tcserve_classify_rows(const float* x, int32_t rows, int32_t C, int32_t k, const char** labels,
+                              int32_t n_labels, char* out, uint64_t cap, uint64_t* used)
+{
+  if (rows < 0 || C < 1 || k < 1 || !used || (rows && !x) || n_labels < 0 || (n_labels && !labels)) return 1;
+  std::vector<std::string> lab;
+  for (int32_t i = 0; i < n_labels; ++i) lab.emplace_back(labels[i] ? labels[i] : "");
+  const int64_t kk = std::min<int64_t>(k, C);
+  std::vector<tcserve::ClassPair> sel(static_cast<size_t>(rows) * kk);
+  for (int64_t r = 0; r < rows; ++r) tcserve::TopKRow(x + r * C, C, kk, sel.data() + r * kk);
+  std::string ser;
+  tcserve::SerializeClasses(sel.data(), static_cast<int64_t>(sel.size()), labels ? &lab : nullptr, &ser);
+  *used = ser.size();
+  if (ser.size() > cap || (ser.size() && !out)) return 2;
+  memcpy(out, ser.data(), ser.size());
   return 0;
 }
 

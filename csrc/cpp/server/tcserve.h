@@ -11,6 +11,12 @@
 //     batcher with one worker per model instance, and ONE call per batch into
 //     the model's executor (a Python callback that launches HIP work and
 //     drops the GIL while the GPU runs), then response encode and send;
+//   * the `classification` extension (InferRequestedOutput(name, class_count=k))
+//     of FP32 outputs stays on that path: the response carries BYTES strings
+//     "score:index[:label]" (classify.h).  A model registered as top-K capable
+//     gets tcserve_batch::class_counts and returns {score, index} pairs (its
+//     executor selects on the device, K19 topk_rows); for any other model
+//     tcserve selects from the raw tensor on the host;
 //   * every other RPC (control plane, streaming, non-native models, requests
 //     using features the fast path does not cover) is proxied verbatim over
 //     HTTP/2 to the Python grpc.aio server on an internal loopback port.
@@ -41,6 +47,10 @@ struct tcserve_batch {
   int32_t n_outputs;
   const tcserve_ref* outputs;       // [n_requests][n_outputs]; ptr 0 = output not requested
   uint64_t* timing_ns;              // out: compute_input, compute_infer, compute_output
+  // Only set for models registered with tcserve_set_topk_capable.  k > 0: the output ref of (r, o) is a
+  // host buffer (kind 0) of rows[r] * k * 8 bytes that the executor fills, row-major, with the k best
+  // {float score; int32 index} pairs of each row (k <= classes; ordering contract: classify.h).
+  const int32_t* class_counts;      // [n_requests][n_outputs]; NULL or 0 = raw tensor
 };
 
 /// Executor: return 0 on success, else write a message into err.
@@ -86,6 +96,16 @@ int32_t tcserve_batch_policy_sim_closed(int32_t max_batch, uint64_t delay_ns, co
                                         uint64_t resp_spacing_ns, uint64_t exec_base_ns, uint64_t exec_per_row_ns,
                                         uint64_t horizon_ns, uint64_t* out_start_ns, int32_t* out_rows,
                                         int32_t* out_instance, int32_t max_batches);
+/// The model's executor honours tcserve_batch::class_counts (default off: it always gets raw host buffers
+/// and tcserve selects the top K itself).
+int32_t tcserve_set_topk_capable(void* server, const char* name, int32_t on);
+/// Class labels of output `output_index` for classification strings (n = 0 clears).
+int32_t tcserve_set_labels(void* server, const char* name, int32_t output_index, const char** labels, int32_t n);
+/// The host classification routine, for tests: the min(k, C) best classes of each of `rows` fp32 rows of C
+/// values as BYTES wire form ("score:index[:label]", each behind a 4-byte little-endian length) into out.
+/// *used gets the serialized size; returns 0, 1 on bad arguments, 2 if cap is too small.
+int32_t tcserve_classify_rows(const float* x, int32_t rows, int32_t C, int32_t k, const char** labels,
+                              int32_t n_labels, char* out, uint64_t cap, uint64_t* used);
 /// Mirror of the Python shared-memory registries; kind 0 = system (ptr = host mapping), 1 = device.
 int32_t tcserve_shm_add(void* server, const char* name, int32_t kind, uint64_t ptr, uint64_t bytes, int32_t device);
 /// Unregister (name "" = all of kind).  Never blocks: returns how many of the removed regions

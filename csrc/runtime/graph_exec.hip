@@ -14,6 +14,13 @@
 //           host outputs -> event; the worker thread waits on that event and
 //           copies host outputs into the request buffers.
 //
+// Classification (tcserve_batch::class_counts, the KServe `classification`
+// extension): after the graph, outside of it, the batch's k_row table goes
+// H2D, one K19 topk_rows launch selects each such row's k best logits on the
+// device and only the {score, index} pairs come back (k <= 64; a larger k
+// takes the full-logits D2H and the host routine of classify.h).  A batch
+// without classification enqueues exactly the sequence above.
+//
 // tcserve (csrc/cpp/server) calls tcamd_pgx_execute as the model's
 // tcserve_exec_fn with `user` = the executor; worker thread i always passes
 // instance i, and each instance owns its stream, graphs and staging buffers.
@@ -36,12 +43,17 @@
 #include <string>
 #include <vector>
 
+#include "cpp/server/classify.h"
 #include "cpp/server/tcserve.h"
 
 extern "C" int tcamd_batched_copy(const void* const* srcs, void* const* dsts, const uint64_t* bytes, int count,
                                   void* stream);
+extern "C" int tcamd_topk_rows(const float* x, uint64_t row_stride_bytes, int32_t rows, int32_t C,
+                               const int32_t* k_row, int32_t kmax, void* pairs, hipStream_t s);
 
 namespace {
+
+constexpr int kTopKMax = 64;  // TCAMD_TOPK_KMAX of csrc/kernels/topk.hip
 
 uint64_t MonoNs()
 {
@@ -62,6 +74,10 @@ struct Instance {
   uint64_t out_dev = 0;               // device [max_rows * out_row] (graph output)
   uint8_t* out_host = nullptr;        // pinned [max_rows * out_row]
   std::vector<uint64_t> pad;          // [max_rows] finite padding sources
+  int32_t* krow_host = nullptr;       // pinned [max_rows] per-row k of the batch (0 = raw / padding)
+  int32_t* krow_dev = nullptr;        // device [max_rows]
+  uint8_t* pair_host = nullptr;       // pinned [max_rows][kTopKMax] {score, index}
+  uint8_t* pair_dev = nullptr;        // device twin
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
 };
 
@@ -102,6 +118,12 @@ void FreeInstance(Instance* in)
   if (in->tbl_host) (void)hipHostFree(in->tbl_host);
   if (in->stage_host) (void)hipHostFree(in->stage_host);
   if (in->out_host) (void)hipHostFree(in->out_host);
+  if (in->krow_host) (void)hipHostFree(in->krow_host);
+  if (in->pair_host) (void)hipHostFree(in->pair_host);
+  if (in->krow_dev) (void)hipFree(in->krow_dev);
+  if (in->pair_dev) (void)hipFree(in->pair_dev);
+  in->krow_host = in->krow_dev = nullptr;
+  in->pair_host = in->pair_dev = nullptr;
   for (auto& e : in->ev)
     if (e) (void)hipEventDestroy(e);
   in->tbl_host = nullptr;
@@ -175,6 +197,11 @@ int32_t tcamd_pgx_set_instance(void* xp, int32_t i, void* stream, const uint64_t
             "hipHostMalloc");
   PGX_CHECK(hipHostMalloc(reinterpret_cast<void**>(&in->out_host), rows * x->out_row, hipHostMallocDefault),
             "hipHostMalloc");
+  PGX_CHECK(hipHostMalloc(reinterpret_cast<void**>(&in->krow_host), rows * 4, hipHostMallocDefault), "hipHostMalloc");
+  PGX_CHECK(hipHostMalloc(reinterpret_cast<void**>(&in->pair_host), rows * kTopKMax * 8, hipHostMallocDefault),
+            "hipHostMalloc");
+  PGX_CHECK(hipMalloc(reinterpret_cast<void**>(&in->krow_dev), rows * 4), "hipMalloc");
+  PGX_CHECK(hipMalloc(reinterpret_cast<void**>(&in->pair_dev), rows * kTopKMax * 8), "hipMalloc");
   for (auto& e : in->ev) PGX_CHECK(hipEventCreate(&e), "hipEventCreate");
   in->ready = true;
   return 0;
@@ -250,11 +277,33 @@ int tcamd_pgx_execute(void* user, int32_t instance, const tcserve_batch* b, char
   std::vector<void*> c_dst;
   std::vector<uint64_t> c_n;
   bool host_out = false;
+  // classification: rows whose k fits the kernel go into the k_row table; a
+  // larger k takes the full-logits D2H and TopKRow on the host
+  const int64_t classes = static_cast<int64_t>(out_row / 4);
+  int dev_kmax = 0, pair_first = 0, pair_end = 0;  // rows [pair_first, pair_end) hold every K19 row
+  bool any_class = false;
   row = 0;
   for (int r = 0; r < b->n_requests; ++r) {
     const int n = b->rows[r];
     const tcserve_ref& ref = b->outputs[r * b->n_outputs];
-    if (ref.ptr) {
+    const int32_t ck = b->class_counts && ref.ptr ? b->class_counts[r * b->n_outputs] : 0;
+    if (ck > 0) {
+      if (ref.kind != 0 || ref.bytes < static_cast<uint64_t>(n) * static_cast<uint64_t>(ck) * 8) {
+        SetErr(err, errlen, "classification output needs a host buffer of rows * k pairs");
+        (void)hipStreamSynchronize(s);
+        return 1;
+      }
+      if (!any_class) memset(in->krow_host, 0, static_cast<size_t>(total) * 4);
+      any_class = true;
+      if (ck <= kTopKMax) {
+        for (int k = 0; k < n; ++k) in->krow_host[row + k] = ck;
+        if (!dev_kmax) pair_first = row;
+        pair_end = row + n;
+        if (ck > dev_kmax) dev_kmax = ck;
+      } else {
+        host_out = true;
+      }
+    } else if (ref.ptr) {
       if (ref.bytes < static_cast<uint64_t>(n) * out_row) {
         SetErr(err, errlen, "output buffer too small for the batch rows");
         (void)hipStreamSynchronize(s);
@@ -278,20 +327,45 @@ int tcamd_pgx_execute(void* user, int32_t instance, const tcserve_batch* b, char
     PGX_CHECK(hipMemcpyAsync(in->out_host, reinterpret_cast<void*>(in->out_dev), static_cast<size_t>(total) * out_row,
                              hipMemcpyDeviceToHost, s),
               "hipMemcpyAsync(out)");
+  if (dev_kmax) {
+    PGX_CHECK(hipMemcpyAsync(in->krow_dev, in->krow_host, static_cast<size_t>(total) * 4, hipMemcpyHostToDevice, s),
+              "hipMemcpyAsync(k_row)");
+    int rc = tcamd_topk_rows(reinterpret_cast<const float*>(in->out_dev), out_row, total,
+                             static_cast<int32_t>(classes), in->krow_dev, dev_kmax, in->pair_dev, s);
+    if (rc != 0) return Fail(err, errlen, "topk_rows", static_cast<hipError_t>(rc));
+    const size_t pair_off = static_cast<size_t>(pair_first) * dev_kmax * 8;
+    PGX_CHECK(hipMemcpyAsync(in->pair_host + pair_off, in->pair_dev + pair_off,
+                             static_cast<size_t>(pair_end - pair_first) * dev_kmax * 8, hipMemcpyDeviceToHost, s),
+              "hipMemcpyAsync(pairs)");
+  }
   PGX_CHECK(hipEventRecord(in->ev[3], s), "hipEventRecord");
   const uint64_t t2 = MonoNs();
   PGX_CHECK(hipEventSynchronize(in->ev[3]), "hipEventSynchronize");
   const uint64_t t3 = MonoNs();
 
   // ---- host outputs, GPU phase times
-  if (host_out) {
+  if (host_out || any_class) {
     row = 0;
     for (int r = 0; r < b->n_requests; ++r) {
       const int n = b->rows[r];
       const tcserve_ref& ref = b->outputs[r * b->n_outputs];
-      if (ref.ptr && ref.kind != 1)
+      const int32_t ck = b->class_counts && ref.ptr ? b->class_counts[r * b->n_outputs] : 0;
+      if (ck > 0) {
+        // rows x ck pairs, row-major; a row holds min(ck, classes) of them
+        auto* dst = reinterpret_cast<tcserve::ClassPair*>(ref.ptr);
+        const size_t take = static_cast<size_t>(ck < classes ? ck : classes);
+        for (int k = 0; k < n; ++k) {
+          if (ck <= kTopKMax)
+            memcpy(dst + static_cast<size_t>(k) * ck,
+                   in->pair_host + (static_cast<size_t>(row + k) * dev_kmax) * 8, take * 8);
+          else
+            tcserve::TopKRow(reinterpret_cast<const float*>(in->out_host + static_cast<size_t>(row + k) * out_row),
+                             classes, ck, dst + static_cast<size_t>(k) * ck);
+        }
+      } else if (ref.ptr && ref.kind != 1) {
         memcpy(reinterpret_cast<void*>(ref.ptr), in->out_host + static_cast<size_t>(row) * out_row,
                static_cast<size_t>(n) * out_row);
+      }
       row += n;
     }
   }

@@ -9,6 +9,7 @@ events, peer access.  Kernels (csrc/kernels/*.hip, gfx950):
 * :func:`batched_copy`    K7 one-launch gather/concat/scatter of byte ranges
 * :func:`pack_bytes`      K2 BYTES serialisation (LDS block scan + scatter)
 * :func:`index_bytes`     K3 BYTES index walk through an LDS window
+* :func:`topk_rows`       K19 per-row top-K {score, index} pairs (classification)
 
 Pointers are plain ints (device addresses).  ``stream`` is a hipStream_t as an
 int (``torch.cuda.current_stream().cuda_stream`` works) or None for the
@@ -109,6 +110,13 @@ _SIGS = {
         [
             ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_uint64),
             ctypes.c_int, ctypes.c_void_p,
+        ],
+        ctypes.c_int,
+    ),
+    "tcamd_topk_rows": (
+        [
+            ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32,
+            ctypes.c_void_p, ctypes.c_void_p,
         ],
         ctypes.c_int,
     ),
@@ -643,6 +651,19 @@ def batched_copy(srcs, dsts, sizes, stream=None):
     d = (ctypes.c_void_p * n)(*[int(p) for p in dsts])
     b = (ctypes.c_uint64 * n)(*[int(x) for x in sizes])
     _check(_load().tcamd_batched_copy(s, d, b, n, _vp(stream)), "batched_copy")
+
+
+TOPK_KMAX = 64  # TCAMD_TOPK_KMAX (csrc/kernels/topk.hip)
+
+
+def topk_rows(x_ptr, row_stride_bytes, rows, C, k_row_ptr, kmax, pairs_ptr, stream=None):
+    """K19: the ``min(k_row[r], C)`` best entries of each fp32 row (``C`` values, rows
+    ``row_stride_bytes`` apart) as ``{float32 score, int32 index}`` pairs at
+    ``pairs[r][:kmax]``, ordered like ``np.argsort(-row, kind="stable")``.  ``k_row`` is a
+    device int32 array, 0 skips the row; slots past a row's count are left untouched.
+    ``kmax`` above :data:`TOPK_KMAX` raises (hipErrorInvalidValue) without a launch."""
+    _check(_load().tcamd_topk_rows(_vp(x_ptr), int(row_stride_bytes), int(rows), int(C), _vp(k_row_ptr), int(kmax),
+                                   _vp(pairs_ptr), _vp(stream)), "topk_rows")
 
 
 def dn_conv1x1(x, ldx, M, K, in_scale, in_bias, w, N, out_bias, relu_out, y, ldy, pool=0, H=0, W=0, stream=None,

@@ -136,6 +136,12 @@ class DensenetOnnx(Model):
             return None
         return self._pgx.fn_address, self._pgx.handle
 
+    @property
+    def native_topk(self):
+        """The C++ executor answers classification requests with device-selected
+        pairs (TcBatch.class_counts); the Python execute_native does not."""
+        return getattr(self, "_pgx", None) is not None
+
     def executor_stats(self):
         return None if self._pgx is None else self._pgx.stats()
 

@@ -32,7 +32,9 @@ class TcBatch(ctypes.Structure):
     _fields_ = [("n_requests", ctypes.c_int32), ("total_rows", ctypes.c_int32),
                 ("rows", ctypes.POINTER(ctypes.c_int32)), ("n_inputs", ctypes.c_int32),
                 ("inputs", ctypes.POINTER(TcRef)), ("n_outputs", ctypes.c_int32),
-                ("outputs", ctypes.POINTER(TcRef)), ("timing_ns", ctypes.POINTER(ctypes.c_uint64))]
+                ("outputs", ctypes.POINTER(TcRef)), ("timing_ns", ctypes.POINTER(ctypes.c_uint64)),
+                # last, so the 8-value positional constructor keeps working (NULL = raw outputs)
+                ("class_counts", ctypes.POINTER(ctypes.c_int32))]
 
 
 EXEC_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_int32, ctypes.POINTER(TcBatch), ctypes.c_void_p,
@@ -66,6 +68,14 @@ def _load():
         lib.tcserve_set_idle_dispatch.restype = ctypes.c_int32
         lib.tcserve_set_preferred.argtypes = [ctypes.c_void_p, cp, ctypes.POINTER(ctypes.c_int32), ctypes.c_int32]
         lib.tcserve_set_preferred.restype = ctypes.c_int32
+        lib.tcserve_set_topk_capable.argtypes = [ctypes.c_void_p, cp, ctypes.c_int32]
+        lib.tcserve_set_topk_capable.restype = ctypes.c_int32
+        lib.tcserve_set_labels.argtypes = [ctypes.c_void_p, cp, ctypes.c_int32, ctypes.POINTER(cp), ctypes.c_int32]
+        lib.tcserve_set_labels.restype = ctypes.c_int32
+        lib.tcserve_classify_rows.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                              ctypes.POINTER(cp), ctypes.c_int32, ctypes.c_void_p, ctypes.c_uint64,
+                                              ctypes.POINTER(ctypes.c_uint64)]
+        lib.tcserve_classify_rows.restype = ctypes.c_int32
         lib.tcserve_remove_model.argtypes = [ctypes.c_void_p, cp]
         lib.tcserve_remove_model.restype = ctypes.c_int32
         lib.tcserve_shm_add.argtypes = [ctypes.c_void_p, cp, ctypes.c_int32, ctypes.c_uint64, ctypes.c_uint64,
@@ -92,6 +102,24 @@ def _load():
 
 def _strs(xs):
     return (ctypes.c_char_p * max(1, len(xs)))(*[x.encode() for x in xs])
+
+
+def classify_rows(x, k, labels=None):
+    """tcserve's host classification routine (csrc/cpp/server/classify.h) on a 2-D
+    float32 array: the serialized BYTES tensor of shape [rows, min(k, C)]."""
+    import numpy as np
+
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    rows, C = x.shape
+    lab = _strs(list(labels)) if labels is not None else None
+    n_lab = len(labels) if labels is not None else 0
+    cap = rows * min(int(k), C) * (64 + max([len(s.encode()) for s in labels or [""]])) + 16
+    out = ctypes.create_string_buffer(cap)
+    used = ctypes.c_uint64(0)
+    rc = _load().tcserve_classify_rows(x.ctypes.data, rows, C, int(k), lab, n_lab, out, cap, ctypes.byref(used))
+    if rc != 0:
+        raise RuntimeError("tcserve_classify_rows failed (%d)" % rc)
+    return out.raw[: used.value]
 
 
 class NativeFrontend:
@@ -216,6 +244,16 @@ class NativeFrontend:
             cb, user, err, 512)
         if rc != 0:
             raise RuntimeError("tcserve: %s" % err.value.decode(errors="replace"))
+        labels = getattr(inst, "labels", None)
+        if labels:
+            # the output that carries label_filename; a model that names none labels
+            # every output, as core.classify does
+            tagged = [k for k, spec in enumerate(outs) if getattr(spec, "label_filename", None)]
+            for k in tagged or range(len(outs)):
+                _load().tcserve_set_labels(self._h, name.encode(), k, _strs(list(labels)), len(labels))
+        if native is not None and getattr(inst, "native_topk", False):
+            # the executor honours TcBatch.class_counts (device top-K, K19)
+            _load().tcserve_set_topk_capable(self._h, name.encode(), 1)
         pref = [int(x) for x in (db_cfg or {}).get("preferred", [])]
         if pref:
             self.set_preferred(name, pref)

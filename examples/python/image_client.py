@@ -108,6 +108,9 @@ def main():
     ap.add_argument("-i", "--protocol", default="HTTP", choices=["HTTP", "gRPC", "http", "grpc"])
     ap.add_argument("--device-preprocess", action="store_true",
                     help="scale/transpose/convert on the GPU with the K6 layout_pack kernel (FP32/FP16 models)")
+    ap.add_argument("--device-resize", action="store_true",
+                    help="upload the raw uint8 images and resize/scale/transpose/convert them on the GPU with the K20 "
+                         "resize_pack kernel (FP32/FP16 models)")
     ap.add_argument("image_filename")
     a = ap.parse_args()
     protocol = a.protocol.lower()
@@ -143,6 +146,12 @@ def main():
                 img = img.mean(axis=2, keepdims=True)
             resized.append(resize_bilinear(img.astype(np.float32), h, w))
         packed = preprocess_batch_device(resized, a.scaling, fmt, dtype)
+        if packed is not None:
+            images = list(packed)
+    elif a.device_resize:
+        from triton_client_amd.utils.image import preprocess_raw_batch_device
+
+        packed = preprocess_raw_batch_device([load_image(f) for f in files], c, h, w, a.scaling, fmt, dtype)
         if packed is not None:
             images = list(packed)
     if images is None:

@@ -1,0 +1,180 @@
+"""Closed-loop raw-image load on preprocess_inception_ensemble, and K20's own time.
+
+    python tools/ensemble_bench.py                # served: bs 1, one 640x480 image, concurrency 1 and 8, gRPC
+    python tools/ensemble_bench.py --kernel       # K20 resize_pack alone: 8 images 640x480 -> 224x224, HIP events
+
+The served mode starts the bench server (densenet_onnx, preprocess_inception
+and the ensemble, 2 instances) as a child process, keeps ``--concurrency``
+gRPC ``async_infer`` requests in flight, each one raw TCIMG blob (BYTES
+[1, 1]), and prints one JSON line per concurrency: infer/s, p50/p99 request
+latency and the server's time per preprocess_inception request.  It uses only
+the public client API, so it runs unchanged on a tree whose
+preprocess_inception is the numpy model.
+"""
+
+import argparse
+import json
+import os
+import sys
+import threading
+import time
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if REPO not in sys.path:
+    sys.path.insert(0, REPO)
+
+
+def kernel_time(n, h, w, iters):
+    import numpy as np
+    import torch
+
+    from triton_client_amd.ops import hip
+    from triton_client_amd.utils import image
+
+    torch.cuda.set_device(0)
+    rng = np.random.default_rng(0)
+    imgs = [rng.integers(0, 256, (h, w, 3), dtype=np.uint8) for _ in range(n)]
+    src = torch.from_numpy(np.stack(imgs)).cuda()
+    dst = torch.zeros(n, 3, 224, 224, device="cuda")
+    s = torch.cuda.current_stream().cuda_stream
+    srcs = [src[i].data_ptr() for i in range(n)]
+    dsts = [dst[i].data_ptr() for i in range(n)]
+    sizes = [(h, w, 3)] * n
+
+    def launch():
+        hip.resize_pack(srcs, sizes, dsts, "FP32", "NCHW", 3, 224, 224, scale=[1 / 127.5] * 3, bias=[-1.0] * 3,
+                        stream=s)
+
+    for _ in range(10):
+        launch()
+    torch.cuda.synchronize()
+    times = []
+    for _ in range(iters):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        launch()
+        b.record()
+        b.synchronize()
+        times.append(a.elapsed_time(b) * 1e3)
+    ref = image.preprocess(imgs[n - 1], 3, 224, 224, "INCEPTION", "NCHW", np.float64)
+    err = float(np.abs(dst[n - 1].cpu().numpy().astype(np.float64) - ref).max())
+    t0 = time.perf_counter()
+    image.inception_preprocess(imgs[0], 224, 224, "NCHW")
+    host_ms = (time.perf_counter() - t0) * 1e3
+    moved = n * (h * w * 3 + 3 * 224 * 224 * 4)
+    print(json.dumps({"kernel": "K20 resize_pack", "images": n, "src": [h, w, 3], "dst": [3, 224, 224],
+                      "launches": iters, "mean_us": round(float(np.mean(times)), 2),
+                      "min_us": round(float(np.min(times)), 2), "max_us": round(float(np.max(times)), 2),
+                      "bytes_read_plus_written": moved, "gb_per_s_at_min": round(moved / np.min(times) / 1e3, 1),
+                      "max_abs_err_vs_float64": err, "numpy_host_ms_per_image": round(host_ms, 3)}))
+
+
+def closed_loop(c, grpcclient, inp, conc, warmup, seconds):
+    lock = threading.Lock()
+    done = threading.Event()
+    state = {"lat": [], "errors": 0, "stop": False, "inflight": conc, "measure": False}
+
+    def send():
+        t0 = time.perf_counter()
+
+        def cb(result, error):
+            t1 = time.perf_counter()
+            with lock:
+                if error is not None:
+                    state["errors"] += 1
+                elif state["measure"]:
+                    state["lat"].append(t1 - t0)
+                again = not state["stop"]
+                if not again:
+                    state["inflight"] -= 1
+                    if state["inflight"] == 0:
+                        done.set()
+            if again:
+                send()
+
+        c.async_infer("preprocess_inception_ensemble", [inp], callback=cb)
+
+    def pre_stats():
+        s = c.get_inference_statistics("preprocess_inception", as_json=True)["model_stats"][0]
+        ok = s["inference_stats"]["success"]
+        return int(ok.get("count", 0)), int(ok.get("ns", 0))
+
+    for _ in range(conc):
+        send()
+    time.sleep(warmup)
+    n0, ns0 = pre_stats()
+    with lock:
+        state["measure"] = True
+        state["lat"] = []
+    t0 = time.perf_counter()
+    time.sleep(seconds)
+    with lock:
+        lat = list(state["lat"])
+        state["measure"] = False
+    dt = time.perf_counter() - t0
+    n1, ns1 = pre_stats()
+    with lock:
+        state["stop"] = True
+    done.wait(30)
+    lat.sort()
+    n = len(lat)
+    return {
+        "model": "preprocess_inception_ensemble", "batch": 1, "concurrency": conc, "seconds": round(dt, 2),
+        "requests": n, "errors": state["errors"], "infer_per_s": round(n / dt, 1),
+        "p50_ms": round(lat[n // 2] * 1e3, 3) if n else None,
+        "p99_ms": round(lat[min(n - 1, int(n * 0.99))] * 1e3, 3) if n else None,
+        "preprocess_us_per_request": round((ns1 - ns0) / 1e3 / max(1, n1 - n0), 1),
+    }
+
+
+def served(args):
+    import numpy as np
+
+    import tritonclient.grpc as grpcclient
+    from triton_client_amd.perf.harness import ServerProcess
+    from triton_client_amd.utils.image import encode_raw
+
+    log = os.path.abspath(args.server_log) if args.server_log else None
+    if log:
+        os.makedirs(os.path.dirname(log), exist_ok=True)
+    srv = ServerProcess(device=0, models="densenet_onnx,preprocess_inception,preprocess_inception_ensemble",
+                        log_path=log, extra_args=["--instance-count", "2"])
+    try:
+        srv.wait_ready(timeout=900, model="preprocess_inception_ensemble")
+        img = np.random.default_rng(0).integers(0, 256, (args.height, args.width, 3), dtype=np.uint8)
+        data = np.array([encode_raw(img)], dtype=np.object_).reshape(1, 1)
+        c = grpcclient.InferenceServerClient(srv.grpc_url)
+        inp = grpcclient.InferInput("INPUT", [1, 1], "BYTES")
+        inp.set_data_from_numpy(data)
+        first = c.infer("preprocess_inception_ensemble", [inp]).as_numpy("OUTPUT")
+        assert first.shape == (1, 1000), first.shape
+        kind = c.get_model_config("preprocess_inception", as_json=True)["config"]["instance_group"][0]["kind"]
+        for conc in args.concurrency:
+            res = closed_loop(c, grpcclient, inp, conc, args.warmup, args.seconds)
+            res.update(image=[args.height, args.width, 3], preprocess_kind=kind, top1=int(first[0].argmax()))
+            print(json.dumps(res), flush=True)
+        c.close()
+    finally:
+        srv.stop()
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--kernel", action="store_true", help="time K20 alone instead of the served loop")
+    ap.add_argument("--concurrency", type=int, nargs="+", default=[1, 8])
+    ap.add_argument("--height", type=int, default=480)
+    ap.add_argument("--width", type=int, default=640)
+    ap.add_argument("--seconds", type=float, default=10.0)
+    ap.add_argument("--warmup", type=float, default=3.0)
+    ap.add_argument("--images", type=int, default=8, help="--kernel: images per launch")
+    ap.add_argument("--iters", type=int, default=50, help="--kernel: timed launches (after 10 warm-up)")
+    ap.add_argument("--server-log", default="", metavar="PATH", help="keep the server's log in this file")
+    args = ap.parse_args()
+    if args.kernel:
+        kernel_time(args.images, args.height, args.width, args.iters)
+    else:
+        served(args)
+
+
+if __name__ == "__main__":
+    main()

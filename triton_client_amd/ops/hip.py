@@ -106,6 +106,15 @@ _SIGS = {
         ],
         ctypes.c_int,
     ),
+    "tcamd_resize_pack": (
+        [
+            ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32),
+            ctypes.POINTER(ctypes.c_int32), ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, ctypes.c_int,
+            ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float),
+            ctypes.c_int, ctypes.c_void_p,
+        ],
+        ctypes.c_int,
+    ),
     "tcamd_batched_copy": (
         [
             ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_uint64),
@@ -639,6 +648,40 @@ def layout_pack(srcs, src_dtype, src_layout, dst, dst_dtype, dst_layout, C, H, W
             LAYOUTS[dst_layout], C, H, W, sc, bi, 0 if rounding == "trunc" else 1, _vp(stream),
         ),
         "layout_pack",
+    )
+
+
+RESIZE_MAX_DIM = 16384  # csrc/kernels/resize.hip: the integer source coordinates fit 32 bits up to here
+
+
+def resize_pack(srcs, sizes, dsts, dst_dtype, dst_layout, C, H, W, scale=None, bias=None, rounding="rne",
+                stream=None):
+    """K20: bilinear-resize (half-pixel centres, clamped, no antialiasing) the uint8
+    HWC image at device pointer ``srcs[i]`` (any alignment) of ``sizes[i] = (h, w, c)``,
+    c 1 or 3, to ``C x H x W`` outputs of ``dst_dtype`` (FP32 / FP16 / BF16) in
+    ``dst_layout`` at its own device pointer ``dsts[i]``, with channel adapt
+    (3->1 mean, 1->3 repeat) and per-channel ``x*scale[c]+bias[c]``:
+    ``utils.image.preprocess`` on the device.  A dimension above
+    :data:`RESIZE_MAX_DIM` or a channel count outside {1, 3} raises
+    (hipErrorInvalidValue) without a launch."""
+    n = len(srcs)
+    if len(sizes) != n or len(dsts) != n:
+        raise ValueError("resize_pack: srcs, sizes and dsts must have one entry per image")
+    s = (ctypes.c_void_p * max(n, 1))(*[int(p) for p in srcs])
+    d = (ctypes.c_void_p * max(n, 1))(*[int(p) for p in dsts])
+    hs = (ctypes.c_int32 * max(n, 1))(*[int(z[0]) for z in sizes])
+    ws = (ctypes.c_int32 * max(n, 1))(*[int(z[1]) for z in sizes])
+    cs = (ctypes.c_int32 * max(n, 1))(*[int(z[2]) for z in sizes])
+    sc = (ctypes.c_float * len(scale))(*scale) if scale is not None else None
+    bi = (ctypes.c_float * len(bias))(*bias) if bias is not None else None
+    if (sc is not None and len(scale) < C) or (bi is not None and len(bias) < C):
+        raise ValueError("resize_pack: scale / bias need C entries")
+    _check(
+        _load().tcamd_resize_pack(
+            s, hs, ws, cs, n, d, dtypes.code(dst_dtype), LAYOUTS[dst_layout], int(C), int(H), int(W), sc, bi,
+            0 if rounding == "trunc" else 1, _vp(stream),
+        ),
+        "resize_pack",
     )
 
 

@@ -818,14 +818,19 @@ class InferenceServer:
         from .types import InferRequest, InputTensor
 
         tensors = {t.name: t for t in request.inputs}
+        held = []  # step responses: a device output's owning tensor lives until the ensemble finishes
         for step_model, imap, omap in inst.ensemble_steps:
             sub = InferRequest(model_name=step_model, id=request.id)
+            # a step's outputs feed other models in this process: a GPU step may leave them in
+            # device memory (OutputTensor.data = DeviceView, e.g. gpu_models.PreprocessInception)
+            sub.accepts_device_outputs = True
             for model_in, ens_name in imap.items():
                 t = tensors.get(ens_name)
                 if t is None:
                     raise ServerError("ensemble tensor '%s' is not available" % ens_name)
                 sub.inputs.append(InputTensor(model_in, t.datatype, list(t.shape), t.data))
             resp = await self.infer(sub)
+            held.append(resp)
             for o, _ in resp.outputs:
                 if o.name in omap:
                     ens = omap[o.name]
@@ -835,7 +840,8 @@ class InferenceServer:
             t = tensors.get(spec.name)
             if t is None:
                 raise internal("ensemble output '%s' was not produced" % spec.name)
-            outs.append(OutputTensor(spec.name, t.datatype, list(t.shape), t.data))
+            # an ensemble output that a step left on the device goes to the client from the host
+            outs.append(OutputTensor(spec.name, t.datatype, list(t.shape), t.numpy() if t.on_device else t.data))
         resp = InferResponse(request.model_name, request.model_version, request.id)
         resp.outputs = self.finalize_outputs(request, inst, outs)
         return resp

@@ -479,6 +479,169 @@ class DensenetOnnx(Model):
         return self._server.shm_target(region, nbytes, offset)
 
 
+class PreprocessInception(Model):
+    """``preprocess_inception`` on the GPU: the same I/O contract as the CPU
+    model of that name (BYTES PPM / PGM / TCIMG blobs in, INCEPTION-scaled
+    FP32 NCHW [3,224,224] out), which it replaces on a ``--gpu`` server.
+
+    Per batch the host only parses each blob's header and copies its uint8
+    pixels into a pinned staging area; one H2D copy and one K20 ``resize_pack``
+    launch per 64 images (csrc/kernels/resize.hip) resample, scale and pack
+    them into a device fp32 [rows, 3, 224, 224] tensor.  A request that the
+    server marked as an ensemble step (``accepts_device_outputs`` on the
+    internal request, core._infer_ensemble) gets its rows back as a
+    ``DeviceView`` with the owning tensor attached, so ``densenet_onnx`` puts
+    them straight into its pointer table; a direct request gets them copied to
+    the host.  Blobs that do not fit the staging area or exceed K20's size
+    limit take the numpy routine.  ``TCAMD_DEVICE_PREPROCESS=0`` (read at
+    load) runs the numpy step for everything."""
+
+    name = "preprocess_inception"
+    max_batch_size = 8
+    inputs = (TensorSpec("INPUT", "BYTES", [1]),)
+    outputs = (TensorSpec("OUTPUT", "FP32", [3, 224, 224]),)
+    dynamic_batching = {"preferred": [], "max_queue_delay_us": 100}
+    instance_kind = "KIND_GPU"
+    instance_count = 2
+    gpus = (0,)
+
+    C, H, W = 3, 224, 224
+    STAGE_BYTES = 32 << 20  # pinned + device uint8 staging per instance (8 images of 1280x1024x3)
+
+    def __init__(self, version=1, device_id=0, **kw):
+        super().__init__(version, **kw)
+        self.device_id = int(kw.get("device", device_id))
+        self._slots = []
+        self._free = []
+        self._cv = threading.Condition()
+        self._host = None
+
+    def load(self):
+        from .cpu_models import PreprocessInception as HostPreprocess
+
+        self._host = HostPreprocess(self.version)
+        self.device_path = os.environ.get("TCAMD_DEVICE_PREPROCESS", "1") != "0"
+        if not self.device_path:
+            return
+        import torch
+
+        from triton_client_amd.ops import hip
+
+        if not torch.cuda.is_available():
+            raise ServerError("preprocess_inception (GPU) requires a GPU")
+        hip.lib()  # fail loudly if the native kernels are missing
+        self.torch = torch
+        dev = torch.device("cuda", self.device_id)
+        for _ in range(max(1, self.instance_count)):
+            host = hip.host_alloc(self.STAGE_BYTES)
+            self._slots.append({
+                "stream": torch.cuda.Stream(device=dev),
+                "stage_host": host,
+                "stage_np": np.ctypeslib.as_array((np.ctypeslib.ctypes.c_uint8 * self.STAGE_BYTES).from_address(host)),
+                "stage_dev": torch.empty(self.STAGE_BYTES, device=dev, dtype=torch.uint8),
+            })
+        self._free = list(range(len(self._slots)))
+
+    def unload(self):
+        from triton_client_amd.ops import hip
+
+        for s in self._slots:
+            s.pop("stage_np", None)
+            try:
+                hip.host_free(s["stage_host"])
+            except Exception:
+                pass
+        self._slots = []
+        self._free = []
+
+    def _acquire(self):
+        with self._cv:
+            while not self._free:
+                self._cv.wait()
+            return self._free.pop()
+
+    def _release(self, i):
+        with self._cv:
+            self._free.append(i)
+            self._cv.notify()
+
+    def _host_one(self, r):
+        try:
+            return self._host.execute([r])[0]
+        except Exception as e:  # noqa: BLE001 - per-request failure, the CPU model's own error
+            return e
+
+    def execute(self, requests):
+        if not self.device_path:
+            return [self._host_one(r) for r in requests]
+        from triton_client_amd.ops import hip
+        from triton_client_amd.utils.image import decode_image, inception_preprocess
+
+        img_bytes = self.C * self.H * self.W * 4
+        plan = []  # per request: (first_row, n_rows), or its exception
+        dev_jobs, host_jobs = [], []  # (row, image, staging offset) / (row, image)
+        rows = used = 0
+        for r in requests:
+            try:
+                imgs = [decode_image(b) for b in r.input("INPUT").numpy().reshape(-1)]
+            except Exception as e:  # noqa: BLE001 - an undecodable blob fails its own request
+                plan.append(e)
+                continue
+            plan.append((rows, len(imgs)))
+            for img in imgs:
+                h, w, c = img.shape
+                if 1 <= h <= hip.RESIZE_MAX_DIM and 1 <= w <= hip.RESIZE_MAX_DIM and c in (1, 3) \
+                        and used + img.size <= self.STAGE_BYTES:
+                    dev_jobs.append((rows, img, used))
+                    used += img.size
+                else:
+                    host_jobs.append((rows, img))
+                rows += 1
+        if rows == 0:
+            return plan
+        torch = self.torch
+        i = self._acquire()
+        slot = self._slots[i]
+        try:
+            stream = slot["stream"]
+            sh = stream.cuda_stream
+            with roctx.range("preprocess_inception rows=%d" % rows), torch.cuda.stream(stream):
+                out = torch.empty((rows, self.C, self.H, self.W), device=stream.device, dtype=torch.float32)
+                base = out.data_ptr()
+                if dev_jobs:
+                    stage = slot["stage_np"]
+                    for _, img, off in dev_jobs:
+                        stage[off:off + img.size] = img.reshape(-1)
+                    src = slot["stage_dev"].data_ptr()
+                    hip.memcpy_async(src, slot["stage_host"], used, sh)
+                    hip.resize_pack([src + off for _, _, off in dev_jobs], [img.shape for _, img, _ in dev_jobs],
+                                    [base + row * img_bytes for row, _, _ in dev_jobs], "FP32", "NCHW",
+                                    self.C, self.H, self.W, scale=[1.0 / 127.5] * 3, bias=[-1.0] * 3, stream=sh)
+                for row, img in host_jobs:
+                    out[row].copy_(torch.from_numpy(inception_preprocess(img, self.H, self.W, "NCHW")))
+                want_host = any(not isinstance(p, Exception) and not getattr(r, "accepts_device_outputs", False)
+                                for r, p in zip(requests, plan))
+                host_all = out.cpu().numpy() if want_host else None  # synchronises the stream
+                hip.stream_synchronize(sh)
+        finally:
+            self._release(i)
+        res = []
+        for r, p in zip(requests, plan):
+            if isinstance(p, Exception):
+                res.append(p)
+                continue
+            first, n = p
+            shape = [n, self.C, self.H, self.W]
+            if getattr(r, "accepts_device_outputs", False):
+                o = OutputTensor("OUTPUT", "FP32", shape, DeviceView(base + first * img_bytes, n * img_bytes,
+                                                                     self.device_id))
+                o.owner = out  # keeps the device memory alive while the ensemble holds the tensor
+            else:
+                o = OutputTensor("OUTPUT", "FP32", shape, host_all[first:first + n])
+            res.append([o])
+        return res
+
+
 class PreprocessInceptionEnsemble(Model):
     """Ensemble: raw image bytes -> preprocess_inception -> densenet_onnx
     (the model the reference's ensemble_image_client drives,
@@ -808,7 +971,7 @@ class BertLargeFP32(BertLarge):
         return bert.prepare_x3(bert.build(device=dev, dtype=torch.float32, layers=self.layers))
 
 
-GPU_MODELS = [DensenetOnnx, PreprocessInceptionEnsemble, BertLarge]
+GPU_MODELS = [DensenetOnnx, PreprocessInception, PreprocessInceptionEnsemble, BertLarge]
 # loaded only when --models names them: bert_large_fp32 adds ~2 GB of bf16x3
 # weights and 28 captured HIP graphs per instance (round-5 advisor finding)
 OPT_IN_GPU_MODELS = [BertLargeFP32]

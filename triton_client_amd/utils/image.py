@@ -69,6 +69,26 @@ def resize_bilinear(img, h, w):
     return top * (1 - wy) + bot * wy
 
 
+def resize_axis_table(n_out, n_in):
+    """``(i0, i1, frac_num, den)`` of ``resize_bilinear`` along one axis, in
+    integers: output index ``i`` blends source ``i0[i]`` and ``i1[i]`` with
+    weight ``frac_num[i] / den`` on ``i1``.  The written contract of K20
+    ``resize_pack`` (csrc/kernels/resize.hip), which computes the same terms
+    per thread: ``num = (2i+1)*n_in - n_out``, ``den = 2*n_out``,
+    ``floor(num/den)`` clamped to the source, weight 0 before the first sample
+    and 1 past the last.  No fp32 coordinate is formed, so the weights are
+    exact ratios at any size (up to 16384 ``num`` fits 32 bits)."""
+    i = np.arange(n_out, dtype=np.int64)
+    den = 2 * int(n_out)
+    num = (2 * i + 1) * int(n_in) - int(n_out)
+    f = num // den  # numpy floors toward -inf
+    frac = num - f * den
+    frac = np.where(f < 0, 0, np.where(f > n_in - 1, den, frac))
+    i0 = np.clip(f, 0, n_in - 1)
+    i1 = np.clip(i0 + 1, 0, n_in - 1)
+    return i0, i1, frac, den
+
+
 def preprocess(img, c, h, w, scaling="INCEPTION", fmt="NCHW", dtype=np.float32):
     if c == 1 and img.shape[2] == 3:
         img = img.mean(axis=2, keepdims=True)
@@ -126,4 +146,41 @@ def preprocess_batch_device(resized, scaling="INCEPTION", fmt="NCHW", dtype="FP3
         n = min(64, len(imgs) - i0)
         hip.layout_pack([src[i].data_ptr() for i in range(i0, i0 + n)], "FP32", "NHWC", dst.data_ptr() + i0 * per,
                         dtype, fmt, c, h, w, scale=scale, bias=bias, stream=stream)
+    return dst.cpu().numpy()
+
+
+def preprocess_raw_batch_device(images, c, h, w, scaling="INCEPTION", fmt="NCHW", dtype="FP32", device=0):
+    """``preprocess`` of a batch of decoded uint8 HWC images of any sizes on
+    the GPU: the raw pixels go up in ONE uint8 host->device copy (a quarter of
+    the bytes of the resized fp32 images, and no host resize), K20
+    ``resize_pack`` launches (64 images each) resample, adapt the channels,
+    scale, convert and pack them, and the [n, C, H, W] (or [n, H, W, C]) batch
+    comes back as numpy.  Returns None when the datatype has no device path
+    (integer models)."""
+    if dtype not in _DEVICE_DTYPES:
+        return None
+    import torch
+
+    from triton_client_amd.ops import hip
+
+    imgs = []
+    for im in images:
+        im = np.ascontiguousarray(im, dtype=np.uint8)
+        imgs.append(im[:, :, None] if im.ndim == 2 else im)
+    if any(max(im.shape[:2]) > hip.RESIZE_MAX_DIM or im.shape[2] not in (1, 3) for im in imgs):
+        return None
+    dev = torch.device("cuda", device)
+    offs = np.cumsum([0] + [im.size for im in imgs])
+    raw = np.empty(int(offs[-1]), dtype=np.uint8)
+    for im, o in zip(imgs, offs):
+        raw[o:o + im.size] = im.reshape(-1)
+    src = torch.from_numpy(raw).to(dev, non_blocking=False)
+    shape = (len(imgs), c, h, w) if fmt == "NCHW" else (len(imgs), h, w, c)
+    dst = torch.empty(shape, device=dev, dtype=torch.float32 if dtype == "FP32" else torch.float16)
+    scale, bias = _SCALE_BIAS[scaling](c)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    per = c * h * w * dst.element_size()
+    hip.resize_pack([src.data_ptr() + int(o) for o in offs[:-1]], [im.shape for im in imgs],
+                    [dst.data_ptr() + i * per for i in range(len(imgs))], dtype, fmt, c, h, w,
+                    scale=scale, bias=bias, stream=stream)
     return dst.cpu().numpy()

@@ -83,6 +83,9 @@ KNOBS = [
     Knob("TCAMD_NATIVE_EXEC", "python", 1, "server/gpu_models.py",
          "native C++ batch executor for graph models; 0 = the Python executor",
          "tests/test_executor_gpu.py::test_native_executor_matches_python_path"),
+    Knob("TCAMD_DEVICE_PREPROCESS", "python", 1, "server/gpu_models.py",
+         "GPU preprocess_inception: K20 resize_pack on the device; 0 = the numpy step",
+         "tests/test_preprocess_device_gpu.py::test_knob_off_is_the_numpy_step"),
     Knob("TCAMD_BYTES_HOST_MAX", "python", 8192, "tritonclient/utils/hip_shared_memory",
          "BYTES set with bytes_path=auto: host codec up to this many elements, K2 above",
          "tests/test_knobs.py::test_bytes_auto_path_knobs"),

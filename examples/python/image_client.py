@@ -66,12 +66,12 @@ def parse_model(metadata, config, protocol):
     return max_batch, in_name, out_name, c, h, w, fmt, in_dt
 
 
-def preprocess(img, fmt, dtype, c, h, w, scaling):
-    from triton_client_amd.utils.image import resize_bilinear
+def preprocess(img, fmt, dtype, c, h, w, scaling, antialias=False):
+    from triton_client_amd.utils.image import resize_area, resize_bilinear
 
     if c == 1:
         img = img.mean(axis=2, keepdims=True)
-    img = resize_bilinear(img.astype(np.float32), h, w)
+    img = resize_area(img, h, w) if antialias else resize_bilinear(img.astype(np.float32), h, w)
     npdt = triton_to_np_dtype(dtype)
     if scaling == "INCEPTION":
         img = img / 127.5 - 1.0
@@ -111,6 +111,10 @@ def main():
     ap.add_argument("--device-resize", action="store_true",
                     help="upload the raw uint8 images and resize/scale/transpose/convert them on the GPU with the K20 "
                          "resize_pack kernel (FP32/FP16 models)")
+    ap.add_argument("--antialias", action="store_true",
+                    help="resize with the antialiased triangle filter (support scaled by the downscale ratio, as "
+                         "Pillow's BILINEAR resize) instead of 2x2-tap bilinear; with --device-resize it runs the K21 "
+                         "resize_pack_aa kernel")
     ap.add_argument("image_filename")
     a = ap.parse_args()
     protocol = a.protocol.lower()
@@ -137,25 +141,26 @@ def main():
         files = [a.image_filename]
     images = None
     if a.device_preprocess:
-        from triton_client_amd.utils.image import preprocess_batch_device, resize_bilinear
+        from triton_client_amd.utils.image import preprocess_batch_device, resize_area, resize_bilinear
 
         resized = []
         for f in files:
             img = load_image(f)
             if c == 1:
                 img = img.mean(axis=2, keepdims=True)
-            resized.append(resize_bilinear(img.astype(np.float32), h, w))
+            resized.append(resize_area(img, h, w) if a.antialias else resize_bilinear(img.astype(np.float32), h, w))
         packed = preprocess_batch_device(resized, a.scaling, fmt, dtype)
         if packed is not None:
             images = list(packed)
     elif a.device_resize:
         from triton_client_amd.utils.image import preprocess_raw_batch_device
 
-        packed = preprocess_raw_batch_device([load_image(f) for f in files], c, h, w, a.scaling, fmt, dtype)
+        packed = preprocess_raw_batch_device([load_image(f) for f in files], c, h, w, a.scaling, fmt, dtype,
+                                             antialias=a.antialias)
         if packed is not None:
             images = list(packed)
     if images is None:
-        images = [preprocess(load_image(f), fmt, dtype, c, h, w, a.scaling) for f in files]
+        images = [preprocess(load_image(f), fmt, dtype, c, h, w, a.scaling, a.antialias) for f in files]
     # batches (cycling over the images to fill the last batch)
     requests, batched_names = [], []
     idx = 0

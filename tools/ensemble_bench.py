@@ -2,6 +2,7 @@
 
     python tools/ensemble_bench.py                # served: bs 1, one 640x480 image, concurrency 1 and 8, gRPC
     python tools/ensemble_bench.py --kernel       # K20 resize_pack alone: 8 images 640x480 -> 224x224, HIP events
+    python tools/ensemble_bench.py --antialias    # either mode with the antialiased resize (K21 resize_pack_aa)
 
 The served mode starts the bench server (densenet_onnx, preprocess_inception
 and the ensemble, 2 instances) as a child process, keeps ``--concurrency``
@@ -9,7 +10,9 @@ gRPC ``async_infer`` requests in flight, each one raw TCIMG blob (BYTES
 [1, 1]), and prints one JSON line per concurrency: infer/s, p50/p99 request
 latency and the server's time per preprocess_inception request.  It uses only
 the public client API, so it runs unchanged on a tree whose
-preprocess_inception is the numpy model.
+preprocess_inception is the numpy model.  ``--antialias`` sends the request
+parameter ``antialias=true`` with every request (served) or times K21 in
+place of K20 (``--kernel``).
 """
 
 import argparse
@@ -24,7 +27,7 @@ if REPO not in sys.path:
     sys.path.insert(0, REPO)
 
 
-def kernel_time(n, h, w, iters):
+def kernel_time(n, h, w, iters, antialias=False):
     import numpy as np
     import torch
 
@@ -43,7 +46,7 @@ def kernel_time(n, h, w, iters):
 
     def launch():
         hip.resize_pack(srcs, sizes, dsts, "FP32", "NCHW", 3, 224, 224, scale=[1 / 127.5] * 3, bias=[-1.0] * 3,
-                        stream=s)
+                        stream=s, **({"antialias": True} if antialias else {}))
 
     for _ in range(10):
         launch()
@@ -56,20 +59,22 @@ def kernel_time(n, h, w, iters):
         b.record()
         b.synchronize()
         times.append(a.elapsed_time(b) * 1e3)
-    ref = image.preprocess(imgs[n - 1], 3, 224, 224, "INCEPTION", "NCHW", np.float64)
+    ref = image.preprocess(imgs[n - 1], 3, 224, 224, "INCEPTION", "NCHW", np.float64,
+                           **({"antialias": True} if antialias else {}))
     err = float(np.abs(dst[n - 1].cpu().numpy().astype(np.float64) - ref).max())
     t0 = time.perf_counter()
-    image.inception_preprocess(imgs[0], 224, 224, "NCHW")
+    image.inception_preprocess(imgs[0], 224, 224, "NCHW", **({"antialias": True} if antialias else {}))
     host_ms = (time.perf_counter() - t0) * 1e3
     moved = n * (h * w * 3 + 3 * 224 * 224 * 4)
-    print(json.dumps({"kernel": "K20 resize_pack", "images": n, "src": [h, w, 3], "dst": [3, 224, 224],
+    print(json.dumps({"kernel": "K21 resize_pack_aa" if antialias else "K20 resize_pack", "images": n,
+                      "src": [h, w, 3], "dst": [3, 224, 224],
                       "launches": iters, "mean_us": round(float(np.mean(times)), 2),
                       "min_us": round(float(np.min(times)), 2), "max_us": round(float(np.max(times)), 2),
                       "bytes_read_plus_written": moved, "gb_per_s_at_min": round(moved / np.min(times) / 1e3, 1),
                       "max_abs_err_vs_float64": err, "numpy_host_ms_per_image": round(host_ms, 3)}))
 
 
-def closed_loop(c, grpcclient, inp, conc, warmup, seconds):
+def closed_loop(c, grpcclient, inp, conc, warmup, seconds, params=None):
     lock = threading.Lock()
     done = threading.Event()
     state = {"lat": [], "errors": 0, "stop": False, "inflight": conc, "measure": False}
@@ -92,7 +97,7 @@ def closed_loop(c, grpcclient, inp, conc, warmup, seconds):
             if again:
                 send()
 
-        c.async_infer("preprocess_inception_ensemble", [inp], callback=cb)
+        c.async_infer("preprocess_inception_ensemble", [inp], callback=cb, parameters=params)
 
     def pre_stats():
         s = c.get_inference_statistics("preprocess_inception", as_json=True)["model_stats"][0]
@@ -146,12 +151,14 @@ def served(args):
         c = grpcclient.InferenceServerClient(srv.grpc_url)
         inp = grpcclient.InferInput("INPUT", [1, 1], "BYTES")
         inp.set_data_from_numpy(data)
-        first = c.infer("preprocess_inception_ensemble", [inp]).as_numpy("OUTPUT")
+        params = {"antialias": True} if args.antialias else None
+        first = c.infer("preprocess_inception_ensemble", [inp], parameters=params).as_numpy("OUTPUT")
         assert first.shape == (1, 1000), first.shape
         kind = c.get_model_config("preprocess_inception", as_json=True)["config"]["instance_group"][0]["kind"]
         for conc in args.concurrency:
-            res = closed_loop(c, grpcclient, inp, conc, args.warmup, args.seconds)
-            res.update(image=[args.height, args.width, 3], preprocess_kind=kind, top1=int(first[0].argmax()))
+            res = closed_loop(c, grpcclient, inp, conc, args.warmup, args.seconds, params)
+            res.update(antialias=args.antialias, image=[args.height, args.width, 3], preprocess_kind=kind,
+                       top1=int(first[0].argmax()))
             print(json.dumps(res), flush=True)
         c.close()
     finally:
@@ -161,6 +168,8 @@ def served(args):
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--kernel", action="store_true", help="time K20 alone instead of the served loop")
+    ap.add_argument("--antialias", action="store_true",
+                    help="the antialiased resize: request parameter antialias=true (served), K21 (--kernel)")
     ap.add_argument("--concurrency", type=int, nargs="+", default=[1, 8])
     ap.add_argument("--height", type=int, default=480)
     ap.add_argument("--width", type=int, default=640)
@@ -171,7 +180,7 @@ def main():
     ap.add_argument("--server-log", default="", metavar="PATH", help="keep the server's log in this file")
     args = ap.parse_args()
     if args.kernel:
-        kernel_time(args.images, args.height, args.width, args.iters)
+        kernel_time(args.images, args.height, args.width, args.iters, args.antialias)
     else:
         served(args)
 

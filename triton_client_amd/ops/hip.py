@@ -6,6 +6,7 @@ events, peer access.  Kernels (csrc/kernels/*.hip, gfx950):
 * :func:`synth_fill`      K1 Philox synthetic data (random/zero/constant/normal)
 * :func:`convert`         K4/K5 FP32 <-> BF16 (trunc|RNE) / FP16 / FP8 e4m3,e5m2
 * :func:`layout_pack`     K6 fused gather + NCHW<->NHWC + convert + scale/bias
+* :func:`resize_pack`     K20 bilinear / K21 antialiased resize + adapt + scale/bias + pack of uint8 images
 * :func:`batched_copy`    K7 one-launch gather/concat/scatter of byte ranges
 * :func:`pack_bytes`      K2 BYTES serialisation (LDS block scan + scatter)
 * :func:`index_bytes`     K3 BYTES index walk through an LDS window
@@ -107,6 +108,15 @@ _SIGS = {
         ctypes.c_int,
     ),
     "tcamd_resize_pack": (
+        [
+            ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32),
+            ctypes.POINTER(ctypes.c_int32), ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, ctypes.c_int,
+            ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float),
+            ctypes.c_int, ctypes.c_void_p,
+        ],
+        ctypes.c_int,
+    ),
+    "tcamd_resize_pack_aa": (
         [
             ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32),
             ctypes.POINTER(ctypes.c_int32), ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, ctypes.c_int,
@@ -655,13 +665,17 @@ RESIZE_MAX_DIM = 16384  # csrc/kernels/resize.hip: the integer source coordinate
 
 
 def resize_pack(srcs, sizes, dsts, dst_dtype, dst_layout, C, H, W, scale=None, bias=None, rounding="rne",
-                stream=None):
+                stream=None, antialias=False):
     """K20: bilinear-resize (half-pixel centres, clamped, no antialiasing) the uint8
     HWC image at device pointer ``srcs[i]`` (any alignment) of ``sizes[i] = (h, w, c)``,
     c 1 or 3, to ``C x H x W`` outputs of ``dst_dtype`` (FP32 / FP16 / BF16) in
     ``dst_layout`` at its own device pointer ``dsts[i]``, with channel adapt
     (3->1 mean, 1->3 repeat) and per-channel ``x*scale[c]+bias[c]``:
-    ``utils.image.preprocess`` on the device.  A dimension above
+    ``utils.image.preprocess`` on the device.  K20 reads 2x2 source pixels per
+    output at any ratio; ``antialias=True`` runs K21 ``resize_pack_aa`` instead,
+    the triangle filter widened by the downscale ratio
+    (``utils.image.resize_area``; equal to the bilinear result on an upscaled
+    axis), with the same arguments.  A dimension above
     :data:`RESIZE_MAX_DIM` or a channel count outside {1, 3} raises
     (hipErrorInvalidValue) without a launch."""
     n = len(srcs)
@@ -676,8 +690,9 @@ def resize_pack(srcs, sizes, dsts, dst_dtype, dst_layout, C, H, W, scale=None, b
     bi = (ctypes.c_float * len(bias))(*bias) if bias is not None else None
     if (sc is not None and len(scale) < C) or (bi is not None and len(bias) < C):
         raise ValueError("resize_pack: scale / bias need C entries")
+    fn = _load().tcamd_resize_pack_aa if antialias else _load().tcamd_resize_pack
     _check(
-        _load().tcamd_resize_pack(
+        fn(
             s, hs, ws, cs, n, d, dtypes.code(dst_dtype), LAYOUTS[dst_layout], int(C), int(H), int(W), sc, bi,
             0 if rounding == "trunc" else 1, _vp(stream),
         ),

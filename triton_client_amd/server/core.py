@@ -749,6 +749,10 @@ class InferenceServer:
         for k, v in request.parameters.items():
             if k not in self._RESERVED_PARAMS:  # custom request parameters, by name / type / value
                 self.wire_stats["param:%s:%s:%s" % (k, type(v).__name__, v)] += 1
+        return await self._dispatch(request)
+
+    async def _dispatch(self, request):
+        """``infer`` past the wire counters: also the entry of an ensemble's sub-requests."""
         entry, version, inst = self.get_instance(request.model_name, request.model_version)
         if inst.decoupled:
             raise ServerError(
@@ -819,8 +823,10 @@ class InferenceServer:
 
         tensors = {t.name: t for t in request.inputs}
         held = []  # step responses: a device output's owning tensor lives until the ensemble finishes
+        # the request's custom parameters reach every step (preprocess_inception reads "antialias")
+        custom = {k: v for k, v in request.parameters.items() if k not in self._RESERVED_PARAMS}
         for step_model, imap, omap in inst.ensemble_steps:
-            sub = InferRequest(model_name=step_model, id=request.id)
+            sub = InferRequest(model_name=step_model, id=request.id, parameters=dict(custom))
             # a step's outputs feed other models in this process: a GPU step may leave them in
             # device memory (OutputTensor.data = DeviceView, e.g. gpu_models.PreprocessInception)
             sub.accepts_device_outputs = True
@@ -829,7 +835,7 @@ class InferenceServer:
                 if t is None:
                     raise ServerError("ensemble tensor '%s' is not available" % ens_name)
                 sub.inputs.append(InputTensor(model_in, t.datatype, list(t.shape), t.data))
-            resp = await self.infer(sub)
+            resp = await self._dispatch(sub)
             held.append(resp)
             for o, _ in resp.outputs:
                 if o.name in omap:

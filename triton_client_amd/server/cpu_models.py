@@ -232,12 +232,18 @@ class RepeatInt32(Model):
 
 class PreprocessInception(Model):
     """Decode a raw image (BYTES: PPM/PGM or raw HxWx3 uint8 with a header) and
-    produce INCEPTION-scaled FP32 NCHW [3,224,224]."""
+    produce INCEPTION-scaled FP32 NCHW [3,224,224].  The custom request
+    parameter ``antialias`` (bool, default false) resizes with
+    ``utils.image.resize_area`` instead of ``resize_bilinear``."""
 
     name = "preprocess_inception"
     max_batch_size = 8
     inputs = (TensorSpec("INPUT", "BYTES", [1]),)
     outputs = (TensorSpec("OUTPUT", "FP32", [3, 224, 224]),)
+
+    @staticmethod
+    def wants_antialias(request):
+        return bool(request.parameters.get("antialias", False))
 
     def execute(self, requests):
         from triton_client_amd.utils.image import decode_image, inception_preprocess
@@ -245,10 +251,11 @@ class PreprocessInception(Model):
         res = []
         for r in requests:
             blobs = r.input("INPUT").numpy().reshape(-1)
+            aa = self.wants_antialias(r)
             outs = []
             for b in blobs:
                 img = decode_image(b)
-                outs.append(inception_preprocess(img, 224, 224, "NCHW"))
+                outs.append(inception_preprocess(img, 224, 224, "NCHW", antialias=aa))
             res.append([self.out("OUTPUT", np.stack(outs).astype(np.float32))])
         return res
 

@@ -494,7 +494,13 @@ class PreprocessInception(Model):
     them straight into its pointer table; a direct request gets them copied to
     the host.  Blobs that do not fit the staging area or exceed K20's size
     limit take the numpy routine.  ``TCAMD_DEVICE_PREPROCESS=0`` (read at
-    load) runs the numpy step for everything."""
+    load) runs the numpy step for everything.
+
+    The custom request parameter ``antialias`` (bool, default false) selects
+    the antialiased resize for that request's images: the batch's device jobs
+    are split by the flag into at most one K20 and one K21 ``resize_pack``
+    call, both on the slot's stream, and the host fallbacks use
+    ``utils.image.resize_area``."""
 
     name = "preprocess_inception"
     max_batch_size = 8
@@ -579,7 +585,8 @@ class PreprocessInception(Model):
 
         img_bytes = self.C * self.H * self.W * 4
         plan = []  # per request: (first_row, n_rows), or its exception
-        dev_jobs, host_jobs = [], []  # (row, image, staging offset) / (row, image)
+        dev_jobs = {False: [], True: []}  # by the request's antialias flag: (row, image, staging offset)
+        host_jobs = []  # (row, image, antialias)
         rows = used = 0
         for r in requests:
             try:
@@ -588,14 +595,15 @@ class PreprocessInception(Model):
                 plan.append(e)
                 continue
             plan.append((rows, len(imgs)))
+            aa = self._host.wants_antialias(r)
             for img in imgs:
                 h, w, c = img.shape
                 if 1 <= h <= hip.RESIZE_MAX_DIM and 1 <= w <= hip.RESIZE_MAX_DIM and c in (1, 3) \
                         and used + img.size <= self.STAGE_BYTES:
-                    dev_jobs.append((rows, img, used))
+                    dev_jobs[aa].append((rows, img, used))
                     used += img.size
                 else:
-                    host_jobs.append((rows, img))
+                    host_jobs.append((rows, img, aa))
                 rows += 1
         if rows == 0:
             return plan
@@ -608,17 +616,21 @@ class PreprocessInception(Model):
             with roctx.range("preprocess_inception rows=%d" % rows), torch.cuda.stream(stream):
                 out = torch.empty((rows, self.C, self.H, self.W), device=stream.device, dtype=torch.float32)
                 base = out.data_ptr()
-                if dev_jobs:
+                if used:
                     stage = slot["stage_np"]
-                    for _, img, off in dev_jobs:
-                        stage[off:off + img.size] = img.reshape(-1)
+                    for jobs in dev_jobs.values():
+                        for _, img, off in jobs:
+                            stage[off:off + img.size] = img.reshape(-1)
                     src = slot["stage_dev"].data_ptr()
                     hip.memcpy_async(src, slot["stage_host"], used, sh)
-                    hip.resize_pack([src + off for _, _, off in dev_jobs], [img.shape for _, img, _ in dev_jobs],
-                                    [base + row * img_bytes for row, _, _ in dev_jobs], "FP32", "NCHW",
-                                    self.C, self.H, self.W, scale=[1.0 / 127.5] * 3, bias=[-1.0] * 3, stream=sh)
-                for row, img in host_jobs:
-                    out[row].copy_(torch.from_numpy(inception_preprocess(img, self.H, self.W, "NCHW")))
+                    for aa, jobs in dev_jobs.items():
+                        if jobs:
+                            hip.resize_pack([src + off for _, _, off in jobs], [img.shape for _, img, _ in jobs],
+                                            [base + row * img_bytes for row, _, _ in jobs], "FP32", "NCHW",
+                                            self.C, self.H, self.W, scale=[1.0 / 127.5] * 3, bias=[-1.0] * 3,
+                                            stream=sh, antialias=aa)
+                for row, img, aa in host_jobs:
+                    out[row].copy_(torch.from_numpy(inception_preprocess(img, self.H, self.W, "NCHW", antialias=aa)))
                 want_host = any(not isinstance(p, Exception) and not getattr(r, "accepts_device_outputs", False)
                                 for r, p in zip(requests, plan))
                 host_all = out.cpu().numpy() if want_host else None  # synchronises the stream

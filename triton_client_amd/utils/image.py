@@ -89,12 +89,66 @@ def resize_axis_table(n_out, n_in):
     return i0, i1, frac, den
 
 
-def preprocess(img, c, h, w, scaling="INCEPTION", fmt="NCHW", dtype=np.float32):
+def area_axis_table(n_out, n_in):
+    """``(first, count, t, total)`` of the antialiased resize along one axis,
+    in integers: output index ``i`` is
+    ``sum_k t[i, k] * src[first[i] + k] / total[i]`` over ``k < count[i]``,
+    with ``D = 2 * max(n_in, n_out)`` and
+    ``t = D - |(2j+1)*n_out - (2i+1)*n_in|`` at source index ``j``: the triangle
+    filter with half-pixel centres and support ``max(1, n_in/n_out)``,
+    renormalised at the borders (the coefficients of Pillow's BILINEAR
+    ``resize``, kept as exact ratios).  Only taps with ``t > 0`` are listed;
+    ``t`` is zero past ``count[i]``.  For ``n_in <= n_out`` these are the two
+    taps and weights of :func:`resize_axis_table`.  The written contract of K21
+    ``resize_pack_aa`` (csrc/kernels/resize.hip), which walks the same taps;
+    up to 16384 every term fits 32 bits signed.  The table has
+    ``n_out * max(count)`` entries, about ``2 * max(n_in, n_out)``."""
+    n_out, n_in = int(n_out), int(n_in)
+    i = np.arange(n_out, dtype=np.int64)
+    big = 2 * max(n_in, n_out)
+    den = 2 * n_out
+    c = (2 * i + 1) * n_in
+    # t > 0  <=>  c - big < (2j+1)*n_out < c + big
+    first = np.maximum((c - big - n_out) // den + 1, 0)
+    last = np.minimum((c + big - n_out - 1) // den, n_in - 1)
+    count = last - first + 1
+    j = first[:, None] + np.arange(int(count.max()), dtype=np.int64)[None, :]
+    t = big - np.abs((2 * j + 1) * n_out - c[:, None])
+    t = np.where(j <= last[:, None], t, 0)
+    return first, count, t, t.sum(axis=1)
+
+
+def _area_axis(x, n_out):
+    """Antialiased resize of float64 ``x`` along axis 0, one pass per tap."""
+    n_in = x.shape[0]
+    first, count, t, total = area_axis_table(n_out, n_in)
+    tail = (1,) * (x.ndim - 1)
+    out = np.zeros((n_out,) + x.shape[1:], dtype=np.float64)
+    for k in range(t.shape[1]):
+        rows = np.nonzero(count > k)[0]
+        out[rows] += (t[rows, k] / total[rows]).reshape((-1,) + tail) * x[first[rows] + k]
+    return out
+
+
+def resize_area(img, h, w):
+    """Antialiased (support-scaled triangle filter) resize of an HWC image to
+    ``h x w`` in float64: :func:`area_axis_table` along x, then along y.  A
+    downscaled axis averages every source pixel under the widened filter; an
+    upscaled axis is :func:`resize_bilinear`.  Banded: the work is
+    ``n_out * taps`` per axis, never an ``n_out x n_in`` matrix."""
+    x = np.asarray(img, dtype=np.float64)
+    x = _area_axis(x.transpose(1, 0, 2), w).transpose(1, 0, 2)
+    return _area_axis(x, h)
+
+
+def preprocess(img, c, h, w, scaling="INCEPTION", fmt="NCHW", dtype=np.float32, antialias=False):
+    """``antialias`` resizes with :func:`resize_area` instead of
+    :func:`resize_bilinear`; everything else is the same."""
     if c == 1 and img.shape[2] == 3:
         img = img.mean(axis=2, keepdims=True)
     elif c == 3 and img.shape[2] == 1:
         img = np.repeat(img, 3, axis=2)
-    x = resize_bilinear(img, h, w)
+    x = resize_area(img, h, w) if antialias else resize_bilinear(img, h, w)
     if scaling == "INCEPTION":
         x = x / 127.5 - 1.0
     elif scaling == "VGG":
@@ -106,8 +160,8 @@ def preprocess(img, c, h, w, scaling="INCEPTION", fmt="NCHW", dtype=np.float32):
     return np.ascontiguousarray(x)
 
 
-def inception_preprocess(img, h, w, fmt="NCHW"):
-    return preprocess(img, 3, h, w, "INCEPTION", fmt)
+def inception_preprocess(img, h, w, fmt="NCHW", antialias=False):
+    return preprocess(img, 3, h, w, "INCEPTION", fmt, antialias=antialias)
 
 
 _SCALE_BIAS = {
@@ -149,14 +203,16 @@ def preprocess_batch_device(resized, scaling="INCEPTION", fmt="NCHW", dtype="FP3
     return dst.cpu().numpy()
 
 
-def preprocess_raw_batch_device(images, c, h, w, scaling="INCEPTION", fmt="NCHW", dtype="FP32", device=0):
+def preprocess_raw_batch_device(images, c, h, w, scaling="INCEPTION", fmt="NCHW", dtype="FP32", device=0,
+                                antialias=False):
     """``preprocess`` of a batch of decoded uint8 HWC images of any sizes on
     the GPU: the raw pixels go up in ONE uint8 host->device copy (a quarter of
     the bytes of the resized fp32 images, and no host resize), K20
     ``resize_pack`` launches (64 images each) resample, adapt the channels,
     scale, convert and pack them, and the [n, C, H, W] (or [n, H, W, C]) batch
-    comes back as numpy.  Returns None when the datatype has no device path
-    (integer models)."""
+    comes back as numpy.  ``antialias`` runs K21 ``resize_pack_aa`` (the
+    device form of :func:`resize_area`) instead of K20.  Returns None when the
+    datatype has no device path (integer models)."""
     if dtype not in _DEVICE_DTYPES:
         return None
     import torch
@@ -182,5 +238,5 @@ def preprocess_raw_batch_device(images, c, h, w, scaling="INCEPTION", fmt="NCHW"
     per = c * h * w * dst.element_size()
     hip.resize_pack([src.data_ptr() + int(o) for o in offs[:-1]], [im.shape for im in imgs],
                     [dst.data_ptr() + i * per for i in range(len(imgs))], dtype, fmt, c, h, w,
-                    scale=scale, bias=bias, stream=stream)
+                    scale=scale, bias=bias, stream=stream, antialias=antialias)
     return dst.cpu().numpy()

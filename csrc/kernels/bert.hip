@@ -874,6 +874,33 @@ int tcamd_embed_layernorm(const int64_t* ids, const int64_t* types, const void* 
   return hipGetLastError();
 }
 
+// K12's launch plan: one block per (sequence, head) with a wave per 32
+// queries; small batches split a head's queries over 3 or 2 blocks (each
+// staging the head's K/V) as long as that still fits one block per CU
+// (bs1/4/8 x 384: 13/14/~16 us vs torch SDPA 17/17/22 unmasked).  *splits
+// blocks per head (grid.y) of *waves waves each.  Host only: the tests ask it
+// which path a shape takes.
+int tcamd_attention_plan(int seqs, int S, int heads, int* splits, int* waves) {
+  if (seqs <= 0 || S <= 0 || S % 64 || S > kAMaxS || heads <= 0 || !splits || !waves) return hipErrorInvalidValue;
+  const int nw = S / 32;
+  int sp1 = 1;
+  for (int sp : {3, 2})
+    if (sp1 == 1 && nw % sp == 0 && nw / sp >= 2 && seqs * heads * sp <= 256) sp1 = sp;
+  *splits = sp1;
+  *waves = nw / sp1;
+  return hipSuccess;
+}
+
+// K12x's launch plan: *waves = 8 (128 queries per block: half the K / V
+// staging per query; bs64 x 384: 331 -> 248 us) once that still gives every
+// CU a block, else 4 (bs1 keeps 64 queries: 20.5 vs 21.2 us;
+// profiles/r6_bert_fp32/k12x_ab*.log).  Host only.
+int tcamd_attention_f32_plan(int seqs, int S, int heads, int* waves) {
+  if (seqs <= 0 || S <= 0 || S % 64 || heads <= 0 || !waves) return hipErrorInvalidValue;
+  *waves = (S % 128 == 0 && seqs * heads * (S / 128) >= 256) ? 8 : 4;
+  return hipSuccess;
+}
+
 // K12: multi-head attention over qkv [seqs * S][3 * heads * 64] bf16 (the fused
 // QKV projection's output: q | k | v, each [heads][64]) -> out [seqs * S][heads *
 // 64] bf16.  mask: int32 [seqs][S] key-padding mask (0 = padded) or null.
@@ -898,16 +925,9 @@ int tcamd_attention_bias(const void* qkv, const void* qkv_bias, const int* mask,
   // (a streamed variant — 4-wave blocks, K/V in double-buffered 64-key chunks,
   // 35 KB of LDS — measured slower: 98-105 us vs 93 us at bs64 x 384; the
   // kernel is bound by the softmax VALU work, not by staging)
-  // one block per (sequence, head) with a wave per 32 queries; small batches
-  // split a head's queries over 3 or 2 blocks (each staging the head's K/V)
-  // as long as that still fits one block per CU (bs1/4/8 x 384: 13/14/~16 us
-  // vs torch SDPA 17/17/22 unmasked)
-  const int nw = S / 32;
-  int splits = 1;
-  for (int sp : {3, 2})
-    if (splits == 1 && nw % sp == 0 && nw / sp >= 2 && seqs * heads * sp <= 256) splits = sp;
-  const int qw = nw / splits;
-  const dim3 grid(seqs * heads, S / (32 * qw)), block(64 * qw);
+  int splits = 1, qw = S / 32;
+  if (const int e = tcamd_attention_plan(seqs, S, heads, &splits, &qw)) return e;
+  const dim3 grid(seqs * heads, splits), block(64 * qw);
   if (mask)
     hipLaunchKernelGGL(attention_kernel<true>, grid, block, lds, (hipStream_t)stream, (const uint16_t*)qkv, mask,
                        (uint16_t*)out, S, heads, scale, (const uint16_t*)qkv_bias);
@@ -936,10 +956,9 @@ int tcamd_attention_f32(const float* qkv, const int* mask, void* out, int seqs, 
     }
     attr.store(true, std::memory_order_release);
   }
-  // 128 queries per block (half the K / V staging per query; bs64 x 384: 331
-  // -> 248 us) once that still gives every CU a block (bs1 keeps 64: 20.5 vs
-  // 21.2 us; profiles/r6_bert_fp32/k12x_ab*.log)
-  if (S % 128 == 0 && seqs * heads * (S / 128) >= 256)
+  int waves = 4;
+  if (const int e = tcamd_attention_f32_plan(seqs, S, heads, &waves)) return e;
+  if (waves == 8)
     hipLaunchKernelGGL(attention_x3_kernel<8>, dim3(seqs * heads, S / 128), dim3(512), kLdsAX, (hipStream_t)stream,
                        qkv, mask, o32, o3, S, heads, scale);
   else

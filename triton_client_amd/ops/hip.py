@@ -352,6 +352,13 @@ _SIGS = {
          ctypes.c_void_p],
         ctypes.c_int,
     ),
+    "tcamd_attention_plan": (
+        [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)],
+        ctypes.c_int,
+    ),
+    "tcamd_attention_f32_plan": (
+        [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int)], ctypes.c_int,
+    ),
     # native batch executor for pointer-table graph models (csrc/runtime/graph_exec.hip)
     "tcamd_pgx_create": (
         [ctypes.c_int32, ctypes.c_int32, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int32,
@@ -788,6 +795,22 @@ def attention_f32(qkv, mask, out, seqs, S, heads, scale, stream=None, x3=False):
     reference) or None.  S % 64 == 0."""
     _check(_load().tcamd_attention_f32(qkv, _vp(mask), out, int(seqs), int(S), int(heads), float(scale),
                                        1 if x3 else 0, _vp(stream)), "attention_f32")
+
+
+def attention_plan(seqs, S, heads):
+    """(splits, waves) of K12's launch for this shape: blocks per (sequence,
+    head) and waves of 32 queries per block.  Host only, no launch."""
+    sp, w = ctypes.c_int(0), ctypes.c_int(0)
+    _check(_load().tcamd_attention_plan(int(seqs), int(S), int(heads), ctypes.byref(sp), ctypes.byref(w)),
+           "attention_plan")
+    return sp.value, w.value
+
+
+def attention_f32_plan(seqs, S, heads):
+    """Waves per block (4 or 8, 16 queries each) of K12x's launch for this shape.  Host only, no launch."""
+    w = ctypes.c_int(0)
+    _check(_load().tcamd_attention_f32_plan(int(seqs), int(S), int(heads), ctypes.byref(w)), "attention_f32_plan")
+    return w.value
 
 
 def x3_conv1x1_ws_bytes(M, K, N=128):

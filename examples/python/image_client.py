@@ -5,7 +5,10 @@ Reads model metadata/config to find the input layout, preprocesses images
 (NONE / INCEPTION / VGG scaling, NCHW or NHWC), sends batches over HTTP or
 gRPC (sync, async, or gRPC streaming) and prints the top-k classes returned
 by the server's classification extension.  Images are decoded with PIL when
-available, else with the framework's PPM/raw decoder.
+available, else with the framework's PPM/raw/JPEG decoder.  With
+``--device-resize`` a JPEG file is not decoded here at all: its bytes go to
+``preprocess_raw_batch_device``, which Huffman-decodes on the host and leaves
+the rest to the K22 jpeg_decode kernel.
 """
 import argparse
 import os
@@ -31,6 +34,15 @@ def load_image(path):
 
         with open(path, "rb") as f:
             return decode_image(f.read())
+
+
+def load_for_device(path):
+    """A JPEG file's bytes as they are (the device decodes them), any other image decoded."""
+    with open(path, "rb") as f:
+        if f.read(2) == b"\xff\xd8":
+            f.seek(0)
+            return f.read()
+    return load_image(path)
 
 
 def completion_callback(user_data, result, error):
@@ -110,7 +122,8 @@ def main():
                     help="scale/transpose/convert on the GPU with the K6 layout_pack kernel (FP32/FP16 models)")
     ap.add_argument("--device-resize", action="store_true",
                     help="upload the raw uint8 images and resize/scale/transpose/convert them on the GPU with the K20 "
-                         "resize_pack kernel (FP32/FP16 models)")
+                         "resize_pack kernel (FP32/FP16 models); JPEG files go up as Huffman-decoded coefficients and "
+                         "the K22 jpeg_decode kernel makes the pixels")
     ap.add_argument("--antialias", action="store_true",
                     help="resize with the antialiased triangle filter (support scaled by the downscale ratio, as "
                          "Pillow's BILINEAR resize) instead of 2x2-tap bilinear; with --device-resize it runs the K21 "
@@ -155,7 +168,7 @@ def main():
     elif a.device_resize:
         from triton_client_amd.utils.image import preprocess_raw_batch_device
 
-        packed = preprocess_raw_batch_device([load_image(f) for f in files], c, h, w, a.scaling, fmt, dtype,
+        packed = preprocess_raw_batch_device([load_for_device(f) for f in files], c, h, w, a.scaling, fmt, dtype,
                                              antialias=a.antialias)
         if packed is not None:
             images = list(packed)

@@ -3,6 +3,8 @@
     python tools/ensemble_bench.py                # served: bs 1, one 640x480 image, concurrency 1 and 8, gRPC
     python tools/ensemble_bench.py --kernel       # K20 resize_pack alone: 8 images 640x480 -> 224x224, HIP events
     python tools/ensemble_bench.py --antialias    # either mode with the antialiased resize (K21 resize_pack_aa)
+    python tools/ensemble_bench.py --jpeg         # served: the committed 640x480 JPEG fixture instead of a TCIMG blob
+    python tools/ensemble_bench.py --kernel --jpeg  # K22 jpeg_decode alone: 8 copies of that fixture, HIP events
 
 The served mode starts the bench server (densenet_onnx, preprocess_inception
 and the ensemble, 2 instances) as a child process, keeps ``--concurrency``
@@ -12,7 +14,10 @@ latency and the server's time per preprocess_inception request.  It uses only
 the public client API, so it runs unchanged on a tree whose
 preprocess_inception is the numpy model.  ``--antialias`` sends the request
 parameter ``antialias=true`` with every request (served) or times K21 in
-place of K20 (``--kernel``).
+place of K20 (``--kernel``).  ``--jpeg`` sends tests/golden/jpeg's 640x480
+4:2:0 file, which the server Huffman-decodes on the host and finishes with K22
+(``TCAMD_DEVICE_PREPROCESS=0`` in the environment: decodes on the host);
+``--kernel --jpeg`` also times the host's entropy decode and full decode.
 """
 
 import argparse
@@ -72,6 +77,71 @@ def kernel_time(n, h, w, iters, antialias=False):
                       "min_us": round(float(np.min(times)), 2), "max_us": round(float(np.max(times)), 2),
                       "bytes_read_plus_written": moved, "gb_per_s_at_min": round(moved / np.min(times) / 1e3, 1),
                       "max_abs_err_vs_float64": err, "numpy_host_ms_per_image": round(host_ms, 3)}))
+
+
+def jpeg_fixture():
+    import glob
+
+    (path,) = glob.glob(os.path.join(REPO, "tests", "golden", "jpeg", "b01_*.jpg"))
+    with open(path, "rb") as f:
+        return f.read()
+
+
+def jpeg_kernel_time(n, iters):
+    import numpy as np
+    import torch
+
+    from triton_client_amd.ops import hip, host_codec
+
+    torch.cuda.set_device(0)
+    hc = host_codec.load()
+    blob = jpeg_fixture()
+    info = hc.jpeg_parse(blob)
+    coef = np.empty(info.coef_bytes, dtype=np.uint8)
+    host = {}
+    for what, fn in (("entropy_decode", lambda: hc.jpeg_entropy_decode(blob, coef)),
+                     ("full_decode", lambda: hc.jpeg_decode(blob))):
+        fn()
+        ts = []
+        for _ in range(20):
+            t0 = time.perf_counter()
+            fn()
+            ts.append((time.perf_counter() - t0) * 1e3)
+        host[what] = ts
+    want = hc.jpeg_decode(blob)
+    stride = -(-info.coef_bytes // 128) * 128
+    src = torch.from_numpy(np.concatenate([np.pad(coef, (0, stride - coef.size))] * n)).cuda()
+    dst = torch.zeros(n, info.pixel_bytes, device="cuda", dtype=torch.uint8)
+    s = torch.cuda.current_stream().cuda_stream
+    srcs = [src.data_ptr() + i * stride for i in range(n)]
+    dsts = [dst[i].data_ptr() for i in range(n)]
+
+    def launch():
+        hip.jpeg_decode(srcs, [info] * n, dsts, stream=s)
+
+    for _ in range(10):
+        launch()
+    torch.cuda.synchronize()
+    times = []
+    for _ in range(iters):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        launch()
+        b.record()
+        b.synchronize()
+        times.append(a.elapsed_time(b) * 1e3)
+    equal = bool((dst.cpu().numpy().reshape((n,) + want.shape) == want).all())
+    moved = n * (info.coef_bytes + info.pixel_bytes)
+    print(json.dumps({"kernel": "K22 jpeg_decode", "images": n, "image": list(info.shape),
+                      "sampling": [info.hs, info.vs], "jpeg_bytes": len(blob), "coef_bytes": int(info.coef_bytes),
+                      "launches": iters, "mean_us": round(float(np.mean(times)), 2),
+                      "min_us": round(float(np.min(times)), 2), "max_us": round(float(np.max(times)), 2),
+                      "bytes_read_plus_written": moved, "gb_per_s_at_min": round(moved / np.min(times) / 1e3, 1),
+                      "equals_host_decode": equal,
+                      "host_entropy_decode_ms_min_mean": [round(float(np.min(host["entropy_decode"])), 3),
+                                                          round(float(np.mean(host["entropy_decode"])), 3)],
+                      "host_full_decode_ms_min_mean": [round(float(np.min(host["full_decode"])), 3),
+                                                       round(float(np.mean(host["full_decode"])), 3)]}))
 
 
 def closed_loop(c, grpcclient, inp, conc, warmup, seconds, params=None):
@@ -147,7 +217,7 @@ def served(args):
     try:
         srv.wait_ready(timeout=900, model="preprocess_inception_ensemble")
         img = np.random.default_rng(0).integers(0, 256, (args.height, args.width, 3), dtype=np.uint8)
-        data = np.array([encode_raw(img)], dtype=np.object_).reshape(1, 1)
+        data = np.array([jpeg_fixture() if args.jpeg else encode_raw(img)], dtype=np.object_).reshape(1, 1)
         c = grpcclient.InferenceServerClient(srv.grpc_url)
         inp = grpcclient.InferInput("INPUT", [1, 1], "BYTES")
         inp.set_data_from_numpy(data)
@@ -158,6 +228,8 @@ def served(args):
         for conc in args.concurrency:
             res = closed_loop(c, grpcclient, inp, conc, args.warmup, args.seconds, params)
             res.update(antialias=args.antialias, image=[args.height, args.width, 3], preprocess_kind=kind,
+                       encoding="JPEG" if args.jpeg else "TCIMG",
+                       device_preprocess=os.environ.get("TCAMD_DEVICE_PREPROCESS", "1") != "0",
                        top1=int(first[0].argmax()))
             print(json.dumps(res), flush=True)
         c.close()
@@ -170,6 +242,8 @@ def main():
     ap.add_argument("--kernel", action="store_true", help="time K20 alone instead of the served loop")
     ap.add_argument("--antialias", action="store_true",
                     help="the antialiased resize: request parameter antialias=true (served), K21 (--kernel)")
+    ap.add_argument("--jpeg", action="store_true",
+                    help="the committed 640x480 JPEG fixture: as the request's blob (served), K22 alone (--kernel)")
     ap.add_argument("--concurrency", type=int, nargs="+", default=[1, 8])
     ap.add_argument("--height", type=int, default=480)
     ap.add_argument("--width", type=int, default=640)
@@ -179,7 +253,9 @@ def main():
     ap.add_argument("--iters", type=int, default=50, help="--kernel: timed launches (after 10 warm-up)")
     ap.add_argument("--server-log", default="", metavar="PATH", help="keep the server's log in this file")
     args = ap.parse_args()
-    if args.kernel:
+    if args.kernel and args.jpeg:
+        jpeg_kernel_time(args.images, args.iters)
+    elif args.kernel:
         kernel_time(args.images, args.height, args.width, args.iters, args.antialias)
     else:
         served(args)

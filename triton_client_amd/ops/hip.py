@@ -7,6 +7,7 @@ events, peer access.  Kernels (csrc/kernels/*.hip, gfx950):
 * :func:`convert`         K4/K5 FP32 <-> BF16 (trunc|RNE) / FP16 / FP8 e4m3,e5m2
 * :func:`layout_pack`     K6 fused gather + NCHW<->NHWC + convert + scale/bias
 * :func:`resize_pack`     K20 bilinear / K21 antialiased resize + adapt + scale/bias + pack of uint8 images
+* :func:`jpeg_decode`     K22 dequantise + IDCT + chroma upsample + YCbCr->RGB of entropy-decoded JPEG coefficients
 * :func:`batched_copy`    K7 one-launch gather/concat/scatter of byte ranges
 * :func:`pack_bytes`      K2 BYTES serialisation (LDS block scan + scatter)
 * :func:`index_bytes`     K3 BYTES index walk through an LDS window
@@ -122,6 +123,14 @@ _SIGS = {
             ctypes.POINTER(ctypes.c_int32), ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, ctypes.c_int,
             ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float),
             ctypes.c_int, ctypes.c_void_p,
+        ],
+        ctypes.c_int,
+    ),
+    "tcamd_jpeg_decode": (
+        [
+            ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32),
+            ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32),
+            ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.c_void_p,
         ],
         ctypes.c_int,
     ),
@@ -705,6 +714,26 @@ def resize_pack(srcs, sizes, dsts, dst_dtype, dst_layout, C, H, W, scale=None, b
         ),
         "resize_pack",
     )
+
+
+def jpeg_decode(srcs, infos, dsts, stream=None):
+    """K22: the device half of a baseline JPEG decode.  ``srcs[i]`` is a device
+    pointer, 16-byte aligned, to the coefficient buffer the host entropy decoder
+    wrote for image i (``ops.host_codec.HostCodec.jpeg_entropy_decode``:
+    quantisation tables, then int16 blocks); ``infos[i]`` is its parse, anything
+    with ``h, w, ncomp, hs, vs`` (``host_codec.JpegInfo``); ``dsts[i]`` is a
+    device pointer of any alignment that receives its ``h*w*ncomp`` uint8 HWC
+    pixels, bitwise those of the host decode.  Images of mixed sizes and
+    samplings share a launch, 64 at a time.  A dimension outside
+    [1, :data:`RESIZE_MAX_DIM`], an unsupported component count or sampling or a
+    misaligned source raises (hipErrorInvalidValue) without a launch."""
+    n = len(srcs)
+    if len(infos) != n or len(dsts) != n:
+        raise ValueError("jpeg_decode: srcs, infos and dsts must have one entry per image")
+    s = (ctypes.c_void_p * max(n, 1))(*[int(p) for p in srcs])
+    d = (ctypes.c_void_p * max(n, 1))(*[int(p) for p in dsts])
+    cols = [(ctypes.c_int32 * max(n, 1))(*[int(getattr(i, f)) for i in infos]) for f in ("h", "w", "ncomp", "hs", "vs")]
+    _check(_load().tcamd_jpeg_decode(s, *cols, n, d, _vp(stream)), "jpeg_decode")
 
 
 def batched_copy(srcs, dsts, sizes, stream=None):

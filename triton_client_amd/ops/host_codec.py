@@ -1,4 +1,4 @@
-"""ctypes binding of libtcamd_host.so (BYTES pack / scan on the host)."""
+"""ctypes binding of libtcamd_host.so (BYTES pack / scan and baseline JPEG on the host)."""
 import ctypes
 import os
 
@@ -7,9 +7,37 @@ import numpy as np
 _PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libtcamd_host.so")
 
 
+class JpegInfo(ctypes.Structure):
+    """TcamdJpegInfo of csrc/host/jpeg.h: the image and the layout of its
+    coefficient buffer (uint16 q[ncomp][64], then component c's ``bw[c] x
+    bh[c]`` blocks of 64 int16 at ``coef_off[c]``)."""
+
+    _fields_ = [("h", ctypes.c_int32), ("w", ctypes.c_int32), ("ncomp", ctypes.c_int32), ("hs", ctypes.c_int32),
+                ("vs", ctypes.c_int32), ("bw", ctypes.c_int32 * 3), ("bh", ctypes.c_int32 * 3),
+                ("coef_off", ctypes.c_uint64 * 3), ("coef_bytes", ctypes.c_uint64)]
+
+    @property
+    def shape(self):
+        return (self.h, self.w, self.ncomp)
+
+    @property
+    def pixel_bytes(self):
+        return self.h * self.w * self.ncomp
+
+
+_JPEG_KIND = {1: "unsupported JPEG: ", 2: "malformed JPEG: "}
+
+
 class HostCodec:
     def __init__(self, lib):
         self._lib = lib
+        lib.tcamd_host_jpeg_parse.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(JpegInfo), ctypes.c_char_p,
+                                         ctypes.c_int]
+        lib.tcamd_host_jpeg_parse.restype = ctypes.c_int
+        for fn in (lib.tcamd_host_jpeg_entropy_decode, lib.tcamd_host_jpeg_decode):
+            fn.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_char_p,
+                           ctypes.c_int]
+            fn.restype = ctypes.c_int
         lib.tcamd_host_pack_bytes.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]
         lib.tcamd_host_pack_bytes.restype = ctypes.c_int
         lib.tcamd_host_count_bytes.argtypes = [ctypes.c_void_p, ctypes.c_uint64]
@@ -50,6 +78,37 @@ class HostCodec:
         n = self._lib.tcamd_host_scan_bytes_prefix(arr.ctypes.data, arr.size, offs.ctypes.data, lens.ctypes.data,
                                                    cap, ctypes.byref(consumed))
         return int(n), int(consumed.value)
+
+
+    # -- baseline JPEG (csrc/host/jpeg.cc) ---------------------------------------------
+    @staticmethod
+    def _jpeg_check(rc, msg):
+        if rc:
+            raise ValueError(_JPEG_KIND.get(rc, "JPEG: ") + msg.value.decode())
+
+    def jpeg_parse(self, blob):
+        """The :class:`JpegInfo` of a JPEG blob; ``ValueError`` ("unsupported
+        JPEG: ..." / "malformed JPEG: ...") when it cannot be decoded."""
+        info = JpegInfo()
+        msg = ctypes.create_string_buffer(96)
+        self._jpeg_check(self._lib.tcamd_host_jpeg_parse(blob, len(blob), ctypes.byref(info), msg, len(msg)), msg)
+        return info
+
+    def jpeg_entropy_decode(self, blob, out):
+        """Huffman-decode ``blob`` into the uint8 array ``out`` (at least
+        ``coef_bytes`` of its parse, 16-byte aligned): quantisation tables,
+        then the de-zigzagged int16 coefficients, not dequantised."""
+        msg = ctypes.create_string_buffer(96)
+        self._jpeg_check(self._lib.tcamd_host_jpeg_entropy_decode(blob, len(blob), out.ctypes.data, out.size, msg,
+                                                             len(msg)), msg)
+
+    def jpeg_decode(self, blob):
+        """Blob -> uint8 [H, W, 1 or 3], entirely on the host."""
+        info = self.jpeg_parse(blob)
+        out = np.empty(info.shape, dtype=np.uint8)
+        msg = ctypes.create_string_buffer(96)
+        self._jpeg_check(self._lib.tcamd_host_jpeg_decode(blob, len(blob), out.ctypes.data, out.size, msg, len(msg)), msg)
+        return out
 
 
 _INSTANCE = None

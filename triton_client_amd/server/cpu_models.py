@@ -231,7 +231,9 @@ class RepeatInt32(Model):
 
 
 class PreprocessInception(Model):
-    """Decode a raw image (BYTES: PPM/PGM or raw HxWx3 uint8 with a header) and
+    """Decode an image (BYTES: PPM/PGM, raw HxWx3 uint8 with a header, or a
+    baseline JPEG file, decoded by csrc/host/jpeg.cc through
+    ``utils.image.decode_image``) and
     produce INCEPTION-scaled FP32 NCHW [3,224,224].  The custom request
     parameter ``antialias`` (bool, default false) resizes with
     ``utils.image.resize_area`` instead of ``resize_bilinear``."""

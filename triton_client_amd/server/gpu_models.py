@@ -481,7 +481,7 @@ class DensenetOnnx(Model):
 
 class PreprocessInception(Model):
     """``preprocess_inception`` on the GPU: the same I/O contract as the CPU
-    model of that name (BYTES PPM / PGM / TCIMG blobs in, INCEPTION-scaled
+    model of that name (BYTES PPM / PGM / TCIMG / JPEG blobs in, INCEPTION-scaled
     FP32 NCHW [3,224,224] out), which it replaces on a ``--gpu`` server.
 
     Per batch the host only parses each blob's header and copies its uint8
@@ -495,6 +495,14 @@ class PreprocessInception(Model):
     the host.  Blobs that do not fit the staging area or exceed K20's size
     limit take the numpy routine.  ``TCAMD_DEVICE_PREPROCESS=0`` (read at
     load) runs the numpy step for everything.
+
+    A baseline JPEG blob is only parsed and Huffman-decoded on the host
+    (csrc/host/jpeg.cc), straight into the pinned staging area; K22
+    ``jpeg_decode`` (csrc/kernels/jpeg.hip, one launch per 64 JPEGs of a batch,
+    before K20 / K21 on the slot's stream) turns the coefficients into pixels
+    at the top of the device staging buffer, which K20 / K21 then read like any
+    staged image.  A JPEG whose coefficients and pixels do not fit what is left
+    of the staging area is decoded on the host and goes on as raw pixels.
 
     The custom request parameter ``antialias`` (bool, default false) selects
     the antialiased resize for that request's images: the batch's device jobs
@@ -531,7 +539,9 @@ class PreprocessInception(Model):
             return
         import torch
 
-        from triton_client_amd.ops import hip
+        from triton_client_amd.ops import hip, host_codec
+
+        self._codec = host_codec.load()  # the JPEG entropy decoder
 
         if not torch.cuda.is_available():
             raise ServerError("preprocess_inception (GPU) requires a GPU")
@@ -577,66 +587,97 @@ class PreprocessInception(Model):
         except Exception as e:  # noqa: BLE001 - per-request failure, the CPU model's own error
             return e
 
+    def _open(self, blob):
+        """A decoded image, or (blob, parse) of a JPEG whose decode is still to be routed."""
+        from triton_client_amd.utils.image import decode_image
+
+        blob = bytes(blob)
+        if blob[:2] == b"\xff\xd8":
+            return blob, self._codec.jpeg_parse(blob)
+        return decode_image(blob)
+
     def execute(self, requests):
         if not self.device_path:
             return [self._host_one(r) for r in requests]
+        i = self._acquire()  # before the plan: JPEG coefficients are decoded straight into the slot's staging area
+        try:
+            return self._execute(self._slots[i], requests)
+        finally:
+            self._release(i)
+
+    def _execute(self, slot, requests):
         from triton_client_amd.ops import hip
-        from triton_client_amd.utils.image import decode_image, inception_preprocess
+        from triton_client_amd.utils.image import inception_preprocess
 
         img_bytes = self.C * self.H * self.W * 4
+        stage = slot["stage_np"]
         plan = []  # per request: (first_row, n_rows), or its exception
-        dev_jobs = {False: [], True: []}  # by the request's antialias flag: (row, image, staging offset)
+        # The staging area: raw pixels and JPEG coefficients fill it from the bottom (``used``, the
+        # bytes of the H2D copy); the pixels K22 decodes exist on the device only and take the top.
+        dev_jobs = {False: [], True: []}  # by the request's antialias flag: (row, image shape, staging offset)
+        jpeg_jobs = []  # (coefficient offset, parse, pixel offset)
         host_jobs = []  # (row, image, antialias)
         rows = used = 0
+        top = self.STAGE_BYTES
         for r in requests:
+            mark = (rows, used, top, len(dev_jobs[False]), len(dev_jobs[True]), len(jpeg_jobs), len(host_jobs))
             try:
-                imgs = [decode_image(b) for b in r.input("INPUT").numpy().reshape(-1)]
+                aa = self._host.wants_antialias(r)
+                for item in [self._open(b) for b in r.input("INPUT").numpy().reshape(-1)]:
+                    if isinstance(item, tuple):
+                        blob, info = item
+                        coef = -(-used // 128) * 128
+                        if coef + info.coef_bytes + info.pixel_bytes <= top:
+                            self._codec.jpeg_entropy_decode(blob, stage[coef:coef + info.coef_bytes])
+                            used = coef + info.coef_bytes
+                            top -= info.pixel_bytes
+                            jpeg_jobs.append((coef, info, top))
+                            dev_jobs[aa].append((rows, info.shape, top))
+                            rows += 1
+                            continue
+                        item = self._codec.jpeg_decode(blob)
+                    h, w, c = item.shape
+                    if 1 <= h <= hip.RESIZE_MAX_DIM and 1 <= w <= hip.RESIZE_MAX_DIM and c in (1, 3) \
+                            and used + item.size <= top:
+                        stage[used:used + item.size] = item.reshape(-1)
+                        dev_jobs[aa].append((rows, item.shape, used))
+                        used += item.size
+                    else:
+                        host_jobs.append((rows, item, aa))
+                    rows += 1
             except Exception as e:  # noqa: BLE001 - an undecodable blob fails its own request
+                rows, used, top = mark[:3]
+                for jobs, n in zip((dev_jobs[False], dev_jobs[True], jpeg_jobs, host_jobs), mark[3:]):
+                    del jobs[n:]
                 plan.append(e)
                 continue
-            plan.append((rows, len(imgs)))
-            aa = self._host.wants_antialias(r)
-            for img in imgs:
-                h, w, c = img.shape
-                if 1 <= h <= hip.RESIZE_MAX_DIM and 1 <= w <= hip.RESIZE_MAX_DIM and c in (1, 3) \
-                        and used + img.size <= self.STAGE_BYTES:
-                    dev_jobs[aa].append((rows, img, used))
-                    used += img.size
-                else:
-                    host_jobs.append((rows, img, aa))
-                rows += 1
+            plan.append((mark[0], rows - mark[0]))
         if rows == 0:
             return plan
         torch = self.torch
-        i = self._acquire()
-        slot = self._slots[i]
-        try:
-            stream = slot["stream"]
-            sh = stream.cuda_stream
-            with roctx.range("preprocess_inception rows=%d" % rows), torch.cuda.stream(stream):
-                out = torch.empty((rows, self.C, self.H, self.W), device=stream.device, dtype=torch.float32)
-                base = out.data_ptr()
-                if used:
-                    stage = slot["stage_np"]
-                    for jobs in dev_jobs.values():
-                        for _, img, off in jobs:
-                            stage[off:off + img.size] = img.reshape(-1)
-                    src = slot["stage_dev"].data_ptr()
-                    hip.memcpy_async(src, slot["stage_host"], used, sh)
-                    for aa, jobs in dev_jobs.items():
-                        if jobs:
-                            hip.resize_pack([src + off for _, _, off in jobs], [img.shape for _, img, _ in jobs],
-                                            [base + row * img_bytes for row, _, _ in jobs], "FP32", "NCHW",
-                                            self.C, self.H, self.W, scale=[1.0 / 127.5] * 3, bias=[-1.0] * 3,
-                                            stream=sh, antialias=aa)
-                for row, img, aa in host_jobs:
-                    out[row].copy_(torch.from_numpy(inception_preprocess(img, self.H, self.W, "NCHW", antialias=aa)))
-                want_host = any(not isinstance(p, Exception) and not getattr(r, "accepts_device_outputs", False)
-                                for r, p in zip(requests, plan))
-                host_all = out.cpu().numpy() if want_host else None  # synchronises the stream
-                hip.stream_synchronize(sh)
-        finally:
-            self._release(i)
+        stream = slot["stream"]
+        sh = stream.cuda_stream
+        with roctx.range("preprocess_inception rows=%d" % rows), torch.cuda.stream(stream):
+            out = torch.empty((rows, self.C, self.H, self.W), device=stream.device, dtype=torch.float32)
+            base = out.data_ptr()
+            src = slot["stage_dev"].data_ptr()
+            if used:
+                hip.memcpy_async(src, slot["stage_host"], used, sh)
+            if jpeg_jobs:
+                hip.jpeg_decode([src + coef for coef, _, _ in jpeg_jobs], [info for _, info, _ in jpeg_jobs],
+                                [src + pix for _, _, pix in jpeg_jobs], stream=sh)
+            for aa, jobs in dev_jobs.items():
+                if jobs:
+                    hip.resize_pack([src + off for _, _, off in jobs], [shape for _, shape, _ in jobs],
+                                    [base + row * img_bytes for row, _, _ in jobs], "FP32", "NCHW",
+                                    self.C, self.H, self.W, scale=[1.0 / 127.5] * 3, bias=[-1.0] * 3,
+                                    stream=sh, antialias=aa)
+            for row, img, aa in host_jobs:
+                out[row].copy_(torch.from_numpy(inception_preprocess(img, self.H, self.W, "NCHW", antialias=aa)))
+            want_host = any(not isinstance(p, Exception) and not getattr(r, "accepts_device_outputs", False)
+                            for r, p in zip(requests, plan))
+            host_all = out.cpu().numpy() if want_host else None  # synchronises the stream
+            hip.stream_synchronize(sh)
         res = []
         for r, p in zip(requests, plan):
             if isinstance(p, Exception):

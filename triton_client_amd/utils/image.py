@@ -2,8 +2,9 @@
 
 Mirrors the preprocessing of reference src/python/examples/image_client.py:154-194
 (INCEPTION scaling ``x/127.5 - 1``, VGG mean subtraction, NCHW/NHWC) using
-numpy only.  Decodes binary PPM (P6) / PGM (P5) and a raw ``TCIMG`` container
-(``b"TCIMG" + u16 H + u16 W + u8 C + HWC bytes``) used by the examples.
+numpy only.  Decodes binary PPM (P6) / PGM (P5), a raw ``TCIMG`` container
+(``b"TCIMG" + u16 H + u16 W + u8 C + HWC bytes``) used by the examples, and
+baseline JPEG through the host decoder of libtcamd_host.so (csrc/host/jpeg.cc).
 """
 
 import struct
@@ -25,8 +26,25 @@ def encode_ppm(img):
     return b"P6\n%d %d\n255\n" % (w, h) + img.tobytes()
 
 
+JPEG_SOI = b"\xff\xd8"
+
+
+def _jpeg_codec():
+    from triton_client_amd.ops import host_codec
+
+    try:
+        return host_codec.load()
+    except (OSError, AttributeError) as e:
+        raise ValueError("JPEG decoding needs libtcamd_host.so, which is not built (run make): %s" % e) from e
+
+
 def decode_image(blob):
+    """PPM / PGM / TCIMG / baseline JPEG blob -> uint8 [H, W, C].  A JPEG the
+    decoder does not cover raises ``ValueError("unsupported JPEG: ...")``, a
+    broken one ``ValueError("malformed JPEG: ...")``."""
     blob = bytes(blob)
+    if blob[:2] == JPEG_SOI:
+        return _jpeg_codec().jpeg_decode(blob)
     if blob[:5] == b"TCIMG":
         h, w, c = struct.unpack_from("<HHB", blob, 5)
         return np.frombuffer(blob, dtype=np.uint8, offset=10, count=h * w * c).reshape(h, w, c)
@@ -48,7 +66,7 @@ def decode_image(blob):
         w, h, _ = parts
         c = 3 if blob[:2] == b"P6" else 1
         return np.frombuffer(blob, dtype=np.uint8, offset=pos, count=h * w * c).reshape(h, w, c)
-    raise ValueError("unsupported image encoding (expected PPM/PGM/TCIMG)")
+    raise ValueError("unsupported image encoding (expected PPM/PGM/TCIMG/JPEG)")
 
 
 def resize_bilinear(img, h, w):
@@ -211,7 +229,10 @@ def preprocess_raw_batch_device(images, c, h, w, scaling="INCEPTION", fmt="NCHW"
     ``resize_pack`` launches (64 images each) resample, adapt the channels,
     scale, convert and pack them, and the [n, C, H, W] (or [n, H, W, C]) batch
     comes back as numpy.  ``antialias`` runs K21 ``resize_pack_aa`` (the
-    device form of :func:`resize_area`) instead of K20.  Returns None when the
+    device form of :func:`resize_area`) instead of K20.  An element may also be
+    the ``bytes`` of a baseline JPEG file: the host only Huffman-decodes it
+    into the same upload, and K22 ``jpeg_decode`` turns the coefficients into
+    pixels in a device buffer that K20 / K21 read.  Returns None when the
     datatype has no device path (integer models)."""
     if dtype not in _DEVICE_DTYPES:
         return None
@@ -219,24 +240,53 @@ def preprocess_raw_batch_device(images, c, h, w, scaling="INCEPTION", fmt="NCHW"
 
     from triton_client_amd.ops import hip
 
-    imgs = []
+    items = []  # a uint8 HWC array, or (blob, parse) of a JPEG
     for im in images:
+        if isinstance(im, (bytes, bytearray, memoryview)):
+            blob = bytes(im)
+            items.append((blob, _jpeg_codec().jpeg_parse(blob)))
+            continue
         im = np.ascontiguousarray(im, dtype=np.uint8)
-        imgs.append(im[:, :, None] if im.ndim == 2 else im)
-    if any(max(im.shape[:2]) > hip.RESIZE_MAX_DIM or im.shape[2] not in (1, 3) for im in imgs):
+        items.append(im[:, :, None] if im.ndim == 2 else im)
+    if any(max(im.shape[:2]) > hip.RESIZE_MAX_DIM or im.shape[2] not in (1, 3)
+           for im in items if not isinstance(im, tuple)):
         return None
     dev = torch.device("cuda", device)
-    offs = np.cumsum([0] + [im.size for im in imgs])
-    raw = np.empty(int(offs[-1]), dtype=np.uint8)
-    for im, o in zip(imgs, offs):
-        raw[o:o + im.size] = im.reshape(-1)
+    # the upload: arrays as they are, JPEG coefficient buffers at 128-byte boundaries
+    offs, shapes, up, pix = [], [], 0, 0
+    for im in items:
+        if isinstance(im, tuple):
+            up = -(-up // 128) * 128
+            offs.append(up)
+            up += im[1].coef_bytes
+            pix += im[1].pixel_bytes
+            shapes.append(im[1].shape)
+        else:
+            offs.append(up)
+            up += im.size
+            shapes.append(im.shape)
+    raw = np.empty(up, dtype=np.uint8)
+    for im, o in zip(items, offs):
+        if isinstance(im, tuple):
+            _jpeg_codec().jpeg_entropy_decode(im[0], raw[o:o + im[1].coef_bytes])
+        else:
+            raw[o:o + im.size] = im.reshape(-1)
     src = torch.from_numpy(raw).to(dev, non_blocking=False)
-    shape = (len(imgs), c, h, w) if fmt == "NCHW" else (len(imgs), h, w, c)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    srcs = [src.data_ptr() + o for o in offs]
+    if pix:
+        decoded = torch.empty(pix, device=dev, dtype=torch.uint8)
+        jobs, at = [], decoded.data_ptr()
+        for k, im in enumerate(items):
+            if isinstance(im, tuple):
+                jobs.append((srcs[k], im[1], at))
+                srcs[k] = at
+                at += im[1].pixel_bytes
+        hip.jpeg_decode([j[0] for j in jobs], [j[1] for j in jobs], [j[2] for j in jobs], stream=stream)
+    shape = (len(items), c, h, w) if fmt == "NCHW" else (len(items), h, w, c)
     dst = torch.empty(shape, device=dev, dtype=torch.float32 if dtype == "FP32" else torch.float16)
     scale, bias = _SCALE_BIAS[scaling](c)
-    stream = torch.cuda.current_stream(dev).cuda_stream
     per = c * h * w * dst.element_size()
-    hip.resize_pack([src.data_ptr() + int(o) for o in offs[:-1]], [im.shape for im in imgs],
-                    [dst.data_ptr() + i * per for i in range(len(imgs))], dtype, fmt, c, h, w,
+    hip.resize_pack(srcs, shapes, [dst.data_ptr() + i * per for i in range(len(items))], dtype, fmt, c, h, w,
                     scale=scale, bias=bias, stream=stream, antialias=antialias)
     return dst.cpu().numpy()

@@ -14,6 +14,7 @@
 #include <new>
 #include <vector>
 
+#include "../kernels/jpeg_huff_core.h"
 #include "../kernels/jpeg_math.h"
 
 namespace {
@@ -85,6 +86,7 @@ void fill_info(const Parsed& p, TcamdJpegInfo* info) {
 
 void build_huff(Huff& t, const uint8_t* counts, const uint8_t* vals, int nvals) {
   std::memset(t.look, 0, sizeof(t.look));
+  std::memset(t.vals, 0, sizeof(t.vals));  // the stream pack copies the whole table
   std::memcpy(t.vals, vals, (size_t)nvals);
   int code = 0, k = 0;
   for (int len = 1; len <= 16; ++len) {
@@ -349,6 +351,140 @@ void entropy_decode(const uint8_t* d, size_t n, const Parsed& P, const TcamdJpeg
   }
 }
 
+// ---- the stream buffer of K23 jpeg_huffman (kernels/jpeg_huff_core.h) -------------------
+namespace jh = tcamd_jhuff;
+
+struct NotPackable {};
+
+// One linear pass over the scan: the bytes between markers are copied (memchr /
+// memcpy runs), FF 00 becomes FF, every expected RSTn closes a segment.
+// Anything but the plain structure throws NotPackable: the host decoder then
+// gives the answer or the error.
+uint64_t stream_pack(const uint8_t* d, size_t n, const Parsed& P, uint8_t* out, uint64_t cap) {
+  // the distinct tables in order of first use
+  int ids[jh::kMaxTabs];
+  uint32_t ntab = 0, tabmap = 0;
+  for (int c = 0; c < P.ncomp; ++c) {
+    for (int cls = 0; cls < 2; ++cls) {
+      const int id = cls * 4 + (cls ? P.comp[c].ta : P.comp[c].td);
+      uint32_t k = 0;
+      while (k < ntab && ids[k] != id) ++k;
+      if (k == ntab) ids[ntab++] = id;  // at most 2 * ncomp <= kMaxTabs
+      tabmap |= k << (8 * c + 4 * cls);
+    }
+  }
+  const uint64_t mcus = (uint64_t)P.mcux * P.mcuy;
+  const uint64_t interval = P.dri && (uint64_t)P.dri < mcus ? (uint64_t)P.dri : mcus;
+  const uint64_t nseg = (mcus + interval - 1) / interval;
+  if (nseg > (uint64_t)jh::kMaxSub) throw NotPackable{};
+  const uint32_t data_off = jh::data_offset(ntab, (uint32_t)nseg);
+  if (cap < (uint64_t)data_off + jh::kTailPad) throw NotPackable{};
+
+  std::memset(out, 0, data_off);
+  uint16_t* q = reinterpret_cast<uint16_t*>(out + jh::kQOff);
+  for (int c = 0; c < P.ncomp; ++c) std::memcpy(q + 64 * c, P.q[P.comp[c].tq], 128);
+  for (uint32_t k = 0; k < ntab; ++k) {
+    const Huff& t = P.huff[ids[k] >> 2][ids[k] & 3];
+    jh::HuffTab* o = reinterpret_cast<jh::HuffTab*>(out + jh::kTabOff) + k;
+    std::memcpy(o->look, t.look, sizeof(o->look));
+    std::memcpy(o->maxcode, t.maxcode, sizeof(o->maxcode));
+    std::memcpy(o->valoff, t.valoff, sizeof(o->valoff));
+    std::memcpy(o->vals, t.vals, sizeof(o->vals));
+    o->maxcode[0] = o->valoff[0] = 0;  // never read; defined bytes all the same
+  }
+  jh::Segment* segs = reinterpret_cast<jh::Segment*>(out + jh::kTabOff + ntab * sizeof(jh::HuffTab));
+  uint8_t* data = out + data_off;
+  const uint64_t room = cap - data_off;  // every write below keeps kTailPad + 3 bytes of it free
+
+  size_t p = P.pos;
+  uint64_t o = 0, seg_start = 0;
+  uint32_t k = 0, nsub = 0;
+  for (;;) {
+    const uint8_t* ff = p < n ? static_cast<const uint8_t*>(std::memchr(d + p, 0xFF, n - p)) : nullptr;
+    const size_t run = ff ? (size_t)(ff - (d + p)) : n - p;
+    if (o + run + 1 + 3 + 2 * jh::kTailPad > room) throw NotPackable{};  // does not fit
+    std::memcpy(data + o, d + p, run);
+    o += run;
+    p += run;
+    if (p + 1 < n && d[p + 1] == 0x00) {  // d[p] == 0xFF: a stuffed byte
+      data[o++] = 0xFF;
+      p += 2;
+      continue;
+    }
+    // a marker, or the end of the blob: the segment is complete
+    const uint64_t bytes = o - seg_start;
+    if (bytes > jh::kMaxDataBytes) throw NotPackable{};
+    segs[k].byte_off = (uint32_t)seg_start;
+    segs[k].bits = (uint32_t)bytes * 8;
+    segs[k].first_mcu = (uint32_t)(k * interval);
+    segs[k].first_sub = nsub;
+    nsub += jh::subs_of((uint32_t)bytes * 8);
+    if (nsub > (uint32_t)jh::kMaxSub) throw NotPackable{};  // above what the kernel's workspace holds
+    while (o % 4) data[o++] = 0;
+    size_t m = p;
+    while (m < n && d[m] == 0xFF) ++m;
+    const int marker = m < n ? d[m] : -1;
+    if (k + 1 < nseg) {
+      if (marker != 0xD0 + (int)(k & 7)) throw NotPackable{};  // missing or misnumbered
+      p = m + 1;
+      seg_start = o;
+      ++k;
+      continue;
+    }
+    // The scan is over: a surplus RSTn, another scan and DNL are the host decoder's business.  So
+    // is FF fill followed by 00: the host decoder ends the data at the fill, but its look for a
+    // later scan or DNL reads on past FF FF and FF 00 alike.
+    if ((marker >= 0xD0 && marker <= 0xD7) || marker == 0xDA || marker == 0xDC || marker == 0x00)
+      throw NotPackable{};
+    break;
+  }
+  while (o % 16) data[o++] = 0;
+  std::memset(data + o, 0, jh::kTailPad);
+  o += jh::kTailPad;
+
+  jh::StreamHeader* h = reinterpret_cast<jh::StreamHeader*>(out);
+  h->magic = jh::kMagic;
+  h->total_bytes = data_off + (uint32_t)o;
+  h->h = P.h;
+  h->w = P.w;
+  h->ncomp = P.ncomp;
+  h->hs = P.comp[0].h;
+  h->vs = P.comp[0].v;
+  h->mcux = P.mcux;
+  h->mcuy = P.mcuy;
+  h->interval = (uint32_t)interval;
+  h->nseg = (uint32_t)nseg;
+  h->nsub = nsub;
+  h->ntab = ntab;
+  h->tabmap = tabmap;
+  h->data_bytes = (uint32_t)o;
+  return h->total_bytes;
+}
+
+// K23 on the host: the phases of jpeg_huff_core.h, each run for every thread in
+// turn where the kernel has a barrier.
+uint32_t emulate(const uint8_t* stream, uint8_t* coef, uint64_t cap, uint32_t* rounds) {
+  jh::Geo g;
+  if (rounds) *rounds = 0;
+  if (!jh::read_header(stream, g) || cap < g.coef_bytes) return jh::kBadHeader;
+  std::vector<jh::Work> store(1);
+  jh::Work& w = store[0];
+  w.status = jh::kOk;
+  for (uint32_t t = 0; t < (uint32_t)jh::kThreads; ++t) jh::phase_init(t, g, w, coef);
+  if (w.status != jh::kOk) return w.status;
+  for (uint32_t round = 0; round <= g.nsub; ++round) {
+    if (round)
+      for (uint32_t t = 0; t < (uint32_t)jh::kThreads; ++t) jh::phase_sync_read(t, g, w);
+    bool any = false;
+    for (uint32_t t = 0; t < (uint32_t)jh::kThreads; ++t) any |= jh::phase_sync_decode(t, g, w);
+    if (!any) break;
+    if (rounds) *rounds = round + 1;
+  }
+  for (uint32_t t = 0; t < (uint32_t)jh::kThreads; ++t) jh::phase_count(t, g, w);
+  for (uint32_t t = 0; t < (uint32_t)jh::kThreads; ++t) jh::phase_write(t, g, w, coef);
+  return w.status;
+}
+
 // one component's blocks -> its sample plane, (bh*8) x (bw*8)
 void idct_plane(const uint16_t* q, const int16_t* coef, int bw, int bh, uint8_t* plane) {
   const size_t stride = (size_t)bw * 8;
@@ -451,6 +587,39 @@ int tcamd_host_jpeg_entropy_decode(const uint8_t* blob, uint64_t n, uint8_t* buf
     if (cap < info.coef_bytes) bad("coefficient buffer too small");
     entropy_decode(blob, (size_t)n, P, info, buf);
   });
+}
+
+uint64_t tcamd_host_jpeg_stream_bound(uint64_t n) {
+  // every table and segment slot, the blob itself, the padding of every segment and of the whole
+  return (uint64_t)jh::data_offset(jh::kMaxTabs, jh::kMaxSub) + n + 4ull * jh::kMaxSub + 4 * jh::kTailPad;
+}
+
+int tcamd_host_jpeg_stream_pack(const uint8_t* blob, uint64_t n, uint8_t* out, uint64_t cap, uint64_t* used,
+                                TcamdJpegInfo* info, char* msg, int msg_cap) {
+  return guarded(msg, msg_cap, [&] {
+    Parsed P;
+    parse(blob, (size_t)n, P);
+    if (info) fill_info(P, info);
+    try {
+      if (reinterpret_cast<uintptr_t>(out) % 16) throw NotPackable{};  // the buffer is read as words on the device
+      const uint64_t bytes = stream_pack(blob, (size_t)n, P, out, cap);
+      if (used) *used = bytes;
+    } catch (const NotPackable&) {
+      throw Error{TCAMD_JPEG_NOT_PACKABLE, "not packable"};
+    }
+  });
+}
+
+int tcamd_host_jpeg_huffman_emulate(const uint8_t* stream, uint8_t* coef, uint64_t cap, uint32_t* status,
+                                    uint32_t* rounds) {
+  uint32_t st = jh::kBadHeader;
+  try {
+    st = emulate(stream, coef, cap, rounds);
+  } catch (const std::bad_alloc&) {
+    return -1;
+  }
+  if (status) *status = st;
+  return 0;
 }
 
 int tcamd_host_jpeg_decode(const uint8_t* blob, uint64_t n, uint8_t* out, uint64_t cap, char* msg, int msg_cap) {

@@ -8,7 +8,7 @@
 
 extern "C" {
 
-enum { TCAMD_JPEG_OK = 0, TCAMD_JPEG_UNSUPPORTED = 1, TCAMD_JPEG_MALFORMED = 2 };
+enum { TCAMD_JPEG_OK = 0, TCAMD_JPEG_UNSUPPORTED = 1, TCAMD_JPEG_MALFORMED = 2, TCAMD_JPEG_NOT_PACKABLE = 3 };
 
 // Coefficient buffer: uint16 q[ncomp][64] (natural order), then component c's
 // blocks at coef_off[c], bw[c] x bh[c] blocks in raster order over the
@@ -29,5 +29,30 @@ int tcamd_host_jpeg_parse(const uint8_t* blob, uint64_t n, TcamdJpegInfo* info, 
 int tcamd_host_jpeg_entropy_decode(const uint8_t* blob, uint64_t n, uint8_t* buf, uint64_t cap, char* msg, int msg_cap);
 // out: h * w * ncomp bytes, HWC (cap is checked).
 int tcamd_host_jpeg_decode(const uint8_t* blob, uint64_t n, uint8_t* out, uint64_t cap, char* msg, int msg_cap);
+
+// The entropy decode on the device, K23 jpeg_huffman (csrc/kernels/jpeg_huff.hip).
+// tcamd_host_jpeg_stream_pack parses the blob (info, when not null, is its
+// parse) and writes the stream buffer the kernel reads into out (16-byte
+// aligned, cap bytes; *used = the bytes written): header, quantisation tables,
+// Huffman lookup tables, the segment table and the scan's bytes without FF 00
+// stuffing and RSTn markers (layout: csrc/kernels/jpeg_huff_core.h).  One pass
+// over the blob, no Huffman work.  A parse error is the code and message of
+// tcamd_host_jpeg_parse.  TCAMD_JPEG_NOT_PACKABLE is everything the pack is not
+// sure about: an RSTn that is missing, misnumbered or surplus, FF fill
+// followed by 00 after the scan, another scan or DNL after this one, a scan of
+// more than 2048 subsequences of 128 bytes (what the kernel's workspace holds)
+// or than cap, or an out that is not 16-byte aligned; the caller then takes
+// tcamd_host_jpeg_entropy_decode, which gives the answer or the error.
+// tcamd_host_jpeg_stream_bound(n) is a cap that fits every packable blob of n bytes.
+uint64_t tcamd_host_jpeg_stream_bound(uint64_t n);
+int tcamd_host_jpeg_stream_pack(const uint8_t* blob, uint64_t n, uint8_t* out, uint64_t cap, uint64_t* used,
+                                TcamdJpegInfo* info, char* msg, int msg_cap);
+// K23 run on the host, thread by thread and phase by phase, from the same
+// header as the kernel: stream (4-byte aligned) -> coef (coef_bytes of the
+// parse, cap is checked; 16-byte aligned), *status = 0 or the kernel's reason
+// code, *rounds = the sync rounds that decoded something.  Returns 0, or -1
+// when out of memory.
+int tcamd_host_jpeg_huffman_emulate(const uint8_t* stream, uint8_t* coef, uint64_t cap, uint32_t* status,
+                                    uint32_t* rounds);
 
 }  // extern "C"

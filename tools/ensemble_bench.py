@@ -4,7 +4,7 @@
     python tools/ensemble_bench.py --kernel       # K20 resize_pack alone: 8 images 640x480 -> 224x224, HIP events
     python tools/ensemble_bench.py --antialias    # either mode with the antialiased resize (K21 resize_pack_aa)
     python tools/ensemble_bench.py --jpeg         # served: the committed 640x480 JPEG fixture instead of a TCIMG blob
-    python tools/ensemble_bench.py --kernel --jpeg  # K22 jpeg_decode alone: 8 copies of that fixture, HIP events
+    python tools/ensemble_bench.py --kernel --jpeg  # K22 jpeg_decode, K23 jpeg_huffman alone: 8 copies of that fixture
 
 The served mode starts the bench server (densenet_onnx, preprocess_inception
 and the ensemble, 2 instances) as a child process, keeps ``--concurrency``
@@ -17,7 +17,10 @@ parameter ``antialias=true`` with every request (served) or times K21 in
 place of K20 (``--kernel``).  ``--jpeg`` sends tests/golden/jpeg's 640x480
 4:2:0 file, which the server Huffman-decodes on the host and finishes with K22
 (``TCAMD_DEVICE_PREPROCESS=0`` in the environment: decodes on the host);
-``--kernel --jpeg`` also times the host's entropy decode and full decode.
+``--kernel --jpeg`` also times the host's entropy decode and full decode, and in
+a second JSON line the stream pack (host) and K23 ``jpeg_huffman`` on one and on
+8 copies.  ``TCAMD_DEVICE_HUFFMAN=1`` in the environment of a served run makes
+the server pack the scan and run K23 instead of the host's entropy decode.
 """
 
 import argparse
@@ -143,6 +146,48 @@ def jpeg_kernel_time(n, iters):
                       "host_full_decode_ms_min_mean": [round(float(np.min(host["full_decode"])), 3),
                                                        round(float(np.mean(host["full_decode"])), 3)]}))
 
+    # K23: the pack on the host, the Huffman stage on the device, against the host's entropy decode above
+    packed = host_codec.aligned_buffer(hc.jpeg_stream_bound(len(blob)))
+    _, used = hc.jpeg_stream_pack(blob, packed)
+    assert used is not None
+    pack_ms = []
+    for _ in range(20):
+        t0 = time.perf_counter()
+        hc.jpeg_stream_pack(blob, packed)
+        pack_ms.append((time.perf_counter() - t0) * 1e3)
+    sstride = -(-used // 16) * 16
+    streams = torch.from_numpy(np.concatenate([np.pad(packed[:used], (0, sstride - used))] * n)).cuda()
+    out = torch.zeros(n * stride, device="cuda", dtype=torch.uint8)
+    status = torch.ones(n, device="cuda", dtype=torch.int32)
+    sp = [streams.data_ptr() + i * sstride for i in range(n)]
+    cp = [out.data_ptr() + i * stride for i in range(n)]
+    huff = {}
+    for m in (1, n):
+        for _ in range(10):
+            hip.jpeg_huffman(sp[:m], cp[:m], status.data_ptr(), stream=s)
+        torch.cuda.synchronize()
+        ts = []
+        for _ in range(iters):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            hip.jpeg_huffman(sp[:m], cp[:m], status.data_ptr(), stream=s)
+            b.record()
+            b.synchronize()
+            ts.append(a.elapsed_time(b) * 1e3)
+        huff[m] = ts
+    got = out.cpu().numpy().reshape(n, stride)[:, :coef.size]
+    print(json.dumps({"kernel": "K23 jpeg_huffman", "image": list(info.shape), "jpeg_bytes": len(blob),
+                      "stream_bytes": int(used), "coef_bytes": int(info.coef_bytes), "launches": iters,
+                      "one_image_us_min_mean": [round(float(np.min(huff[1])), 2), round(float(np.mean(huff[1])), 2)],
+                      "images": n,
+                      "all_images_us_min_mean": [round(float(np.min(huff[n])), 2), round(float(np.mean(huff[n])), 2)],
+                      "status_all_zero": bool((status.cpu().numpy() == 0).all()),
+                      "equals_host_entropy_decode": bool((got == coef).all()),
+                      "host_stream_pack_ms_min_mean": [round(float(np.min(pack_ms)), 4),
+                                                       round(float(np.mean(pack_ms)), 4)],
+                      "host_entropy_decode_ms_min_mean": [round(float(np.min(host["entropy_decode"])), 3),
+                                                          round(float(np.mean(host["entropy_decode"])), 3)]}))
+
 
 def closed_loop(c, grpcclient, inp, conc, warmup, seconds, params=None):
     lock = threading.Lock()
@@ -230,6 +275,7 @@ def served(args):
             res.update(antialias=args.antialias, image=[args.height, args.width, 3], preprocess_kind=kind,
                        encoding="JPEG" if args.jpeg else "TCIMG",
                        device_preprocess=os.environ.get("TCAMD_DEVICE_PREPROCESS", "1") != "0",
+                       device_huffman=os.environ.get("TCAMD_DEVICE_HUFFMAN", "0") == "1",
                        top1=int(first[0].argmax()))
             print(json.dumps(res), flush=True)
         c.close()

@@ -5,11 +5,17 @@ development machine only; nothing under tests/ imports Pillow.  The images are
 seeded, so a rerun with the same Pillow / libjpeg-turbo rewrites the same files.
 
 Sizes are width x height.  The tile fixtures are one pixel wider / taller than
-K22's workgroup tile (kTileW x kTileH in csrc/kernels/jpeg.hip)."""
+K22's workgroup tile (kTileW x kTileH in csrc/kernels/jpeg.hip).
+
+``--huff`` writes tests/golden/jpeg_huff instead: the streams that exercise K23
+``jpeg_huffman`` (csrc/kernels/jpeg_huff.hip) beyond what the fixtures above do,
+each ``.jpg`` under 64 KB and its own ``manifest.json``, without Pillow's
+decodes: the oracle of the Huffman stage is the host entropy decoder."""
 
 import io
 import json
 import os
+import sys
 
 import numpy as np
 from PIL import Image, features
@@ -34,6 +40,10 @@ def noise(w, h, c, seed):
     return np.random.default_rng(seed).integers(0, 256, (h, w, c), dtype=np.uint8)
 
 
+def flat(w, h, c, seed):
+    return np.full((h, w, c), 90 + seed % 7, dtype=np.uint8)
+
+
 # name, width, height, mode, kind, image maker, save() parameters
 FIXTURES = [
     ("f01_16x16_444_q90", 16, 16, "444", "case", smooth, {"quality": 90}),
@@ -55,12 +65,24 @@ FIXTURES = [
     ("b01_640x480_420_q75", 640, 480, "420", "bench", smooth, {"quality": 75}),
 ]
 
+# K23: EOB-only blocks (hundreds of blocks in one subsequence); about a hundred subsequences of
+# dense data per sampling; restart intervals longer than a subsequence, unaligned with the MCU
+# rows (10 MCUs a row) and more than 8 of them, so the RSTn numbers wrap
+HUFF_OUT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests", "golden", "jpeg_huff")
+HUFF_FIXTURES = [
+    ("h01_256x256_420_flat", 256, 256, "420", "case", flat, {}),
+    ("h02_200x200_grey_q90_noise", 200, 200, "grey", "case", noise, {"quality": 90}),
+    ("h03_128x128_422_q90_noise", 128, 128, "422", "case", noise, {"quality": 90}),
+    ("h04_128x128_444_q90_noise", 128, 128, "444", "case", noise, {"quality": 90}),
+    ("h05_160x120_420_q90_rst7", 160, 120, "420", "case", noise, {"quality": 90, "restart_marker_blocks": 7}),
+]
 
-def main():
-    os.makedirs(OUT, exist_ok=True)
+
+def main(out=OUT, fixtures=FIXTURES, first_seed=1000, decodes=True):
+    os.makedirs(out, exist_ok=True)
     entries = []
-    for seed, (name, w, h, mode, kind, make, params) in enumerate(FIXTURES):
-        a = make(w, h, 1 if mode == "grey" else 3, 1000 + seed)
+    for seed, (name, w, h, mode, kind, make, params) in enumerate(fixtures):
+        a = make(w, h, 1 if mode == "grey" else 3, first_seed + seed)
         im = Image.fromarray(a[:, :, 0], "L") if mode == "grey" else Image.fromarray(a, "RGB")
         kw = dict(params)
         if mode != "grey":
@@ -68,17 +90,21 @@ def main():
         buf = io.BytesIO()
         im.save(buf, "JPEG", **kw)
         data = buf.getvalue()
-        with open(os.path.join(OUT, name + ".jpg"), "wb") as f:
+        with open(os.path.join(out, name + ".jpg"), "wb") as f:
             f.write(data)
-        np.save(os.path.join(OUT, name + ".npy"), np.asarray(Image.open(io.BytesIO(data))))
+        if decodes:
+            np.save(os.path.join(out, name + ".npy"), np.asarray(Image.open(io.BytesIO(data))))
         entries.append({"name": name, "w": w, "h": h, "mode": mode, "kind": kind, "params": params,
                         "bytes": len(data)})
         print("%-28s %6d bytes" % (name, len(data)))
-    with open(os.path.join(OUT, "manifest.json"), "w") as f:
+    with open(os.path.join(out, "manifest.json"), "w") as f:
         json.dump({"pillow": features.version("pil"), "libjpeg_turbo": features.version_feature("libjpeg_turbo"),
                    "tile": [TILE_W, TILE_H], "fixtures": entries}, f, indent=1)
         f.write("\n")
 
 
 if __name__ == "__main__":
-    main()
+    if sys.argv[1:] == ["--huff"]:
+        main(HUFF_OUT, HUFF_FIXTURES, first_seed=2000, decodes=False)
+    else:
+        main()

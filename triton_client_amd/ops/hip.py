@@ -8,6 +8,7 @@ events, peer access.  Kernels (csrc/kernels/*.hip, gfx950):
 * :func:`layout_pack`     K6 fused gather + NCHW<->NHWC + convert + scale/bias
 * :func:`resize_pack`     K20 bilinear / K21 antialiased resize + adapt + scale/bias + pack of uint8 images
 * :func:`jpeg_decode`     K22 dequantise + IDCT + chroma upsample + YCbCr->RGB of entropy-decoded JPEG coefficients
+* :func:`jpeg_huffman`    K23 Huffman decode of packed JPEG scans into the coefficients K22 reads
 * :func:`batched_copy`    K7 one-launch gather/concat/scatter of byte ranges
 * :func:`pack_bytes`      K2 BYTES serialisation (LDS block scan + scatter)
 * :func:`index_bytes`     K3 BYTES index walk through an LDS window
@@ -131,6 +132,13 @@ _SIGS = {
             ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32),
             ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32),
             ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.c_void_p,
+        ],
+        ctypes.c_int,
+    ),
+    "tcamd_jpeg_huffman": (
+        [
+            ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p), ctypes.c_void_p, ctypes.c_int,
+            ctypes.c_void_p,
         ],
         ctypes.c_int,
     ),
@@ -734,6 +742,25 @@ def jpeg_decode(srcs, infos, dsts, stream=None):
     d = (ctypes.c_void_p * max(n, 1))(*[int(p) for p in dsts])
     cols = [(ctypes.c_int32 * max(n, 1))(*[int(getattr(i, f)) for i in infos]) for f in ("h", "w", "ncomp", "hs", "vs")]
     _check(_load().tcamd_jpeg_decode(s, *cols, n, d, _vp(stream)), "jpeg_decode")
+
+
+def jpeg_huffman(streams, coefs, status, stream=None):
+    """K23: the Huffman stage of a baseline JPEG decode on the device.
+    ``streams[i]`` is a device pointer, 16-byte aligned, to the stream buffer
+    ``ops.host_codec.HostCodec.jpeg_stream_pack`` wrote for image i;
+    ``coefs[i]`` is a device pointer, 16-byte aligned, to ``coef_bytes`` of its
+    parse, which receive the buffer :func:`jpeg_decode` reads, byte for byte
+    what ``jpeg_entropy_decode`` writes; ``status`` is a device pointer to one
+    uint32 per image: 0, or the reason that image's coefficients are not to be
+    used (invalid Huffman data; the host decoder then gives the error).  One
+    workgroup per image, 64 images per launch.  A null or misaligned pointer
+    raises (hipErrorInvalidValue) without a launch."""
+    n = len(streams)
+    if len(coefs) != n:
+        raise ValueError("jpeg_huffman: streams and coefs must have one entry per image")
+    s = (ctypes.c_void_p * max(n, 1))(*[int(p) for p in streams])
+    c = (ctypes.c_void_p * max(n, 1))(*[int(p) for p in coefs])
+    _check(_load().tcamd_jpeg_huffman(s, c, _vp(status), n, _vp(stream)), "jpeg_huffman")
 
 
 def batched_copy(srcs, dsts, sizes, stream=None):

@@ -25,7 +25,15 @@ class JpegInfo(ctypes.Structure):
         return self.h * self.w * self.ncomp
 
 
+def aligned_buffer(nbytes, align=16):
+    """An uninitialised uint8 array of ``nbytes`` whose first byte is ``align``-byte aligned."""
+    a = np.empty(nbytes + align, dtype=np.uint8)
+    o = -a.ctypes.data % align
+    return a[o:o + nbytes]
+
+
 _JPEG_KIND = {1: "unsupported JPEG: ", 2: "malformed JPEG: "}
+JPEG_NOT_PACKABLE = 3  # TCAMD_JPEG_NOT_PACKABLE: no error, the host entropy decoder's turn
 
 
 class HostCodec:
@@ -38,6 +46,15 @@ class HostCodec:
             fn.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_char_p,
                            ctypes.c_int]
             fn.restype = ctypes.c_int
+        lib.tcamd_host_jpeg_stream_bound.argtypes = [ctypes.c_uint64]
+        lib.tcamd_host_jpeg_stream_bound.restype = ctypes.c_uint64
+        lib.tcamd_host_jpeg_stream_pack.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64,
+                                                    ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(JpegInfo),
+                                                    ctypes.c_char_p, ctypes.c_int]
+        lib.tcamd_host_jpeg_stream_pack.restype = ctypes.c_int
+        u32p = ctypes.POINTER(ctypes.c_uint32)
+        lib.tcamd_host_jpeg_huffman_emulate.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, u32p, u32p]
+        lib.tcamd_host_jpeg_huffman_emulate.restype = ctypes.c_int
         lib.tcamd_host_pack_bytes.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]
         lib.tcamd_host_pack_bytes.restype = ctypes.c_int
         lib.tcamd_host_count_bytes.argtypes = [ctypes.c_void_p, ctypes.c_uint64]
@@ -109,6 +126,44 @@ class HostCodec:
         msg = ctypes.create_string_buffer(96)
         self._jpeg_check(self._lib.tcamd_host_jpeg_decode(blob, len(blob), out.ctypes.data, out.size, msg, len(msg)), msg)
         return out
+
+    # -- the stream buffer of K23 jpeg_huffman (csrc/kernels/jpeg_huff_core.h) ----------
+    def jpeg_stream_bound(self, nbytes):
+        """A capacity that holds the stream buffer of every packable blob of ``nbytes``."""
+        return int(self._lib.tcamd_host_jpeg_stream_bound(int(nbytes)))
+
+    def jpeg_stream_pack(self, blob, out):
+        """Pack the scan of ``blob`` into the uint8 array ``out`` (16-byte
+        aligned, :func:`aligned_buffer`; anything else is not packable) as the
+        stream buffer ``ops.hip.jpeg_huffman`` reads: header, quantisation and Huffman tables, segment table, the entropy-coded bytes
+        without stuffing and restart markers.  Returns ``(info, used)``, the
+        parse and the bytes written, or ``(info, None)`` when the blob is not
+        packable (anything unusual about its restart markers or what follows
+        the scan, a scan above the kernel's 2048 x 128 bytes, or ``out`` too
+        small): the caller then takes :meth:`jpeg_entropy_decode`, which gives
+        the answer or the error.  A blob that does not parse raises as
+        :meth:`jpeg_parse` does."""
+        info = JpegInfo()
+        used = ctypes.c_uint64(0)
+        msg = ctypes.create_string_buffer(96)
+        rc = self._lib.tcamd_host_jpeg_stream_pack(blob, len(blob), out.ctypes.data, out.size, ctypes.byref(used),
+                                                   ctypes.byref(info), msg, len(msg))
+        if rc == JPEG_NOT_PACKABLE:
+            return info, None
+        self._jpeg_check(rc, msg)
+        return info, int(used.value)
+
+    def jpeg_huffman_emulate(self, stream, out):
+        """K23 ``jpeg_huffman`` run on the host, thread by thread and phase by
+        phase from the kernel's own header: the uint8 array ``stream`` (a packed
+        stream buffer) -> coefficients in ``out`` (``coef_bytes`` of the parse,
+        16-byte aligned).  Returns ``(status, rounds)``: the kernel's status
+        word (0 = the coefficients are good) and the sync rounds it took."""
+        status, rounds = ctypes.c_uint32(0), ctypes.c_uint32(0)
+        if self._lib.tcamd_host_jpeg_huffman_emulate(stream.ctypes.data, out.ctypes.data, out.size,
+                                                     ctypes.byref(status), ctypes.byref(rounds)):
+            raise MemoryError("jpeg_huffman_emulate")
+        return int(status.value), int(rounds.value)
 
 
 _INSTANCE = None

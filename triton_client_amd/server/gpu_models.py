@@ -504,6 +504,18 @@ class PreprocessInception(Model):
     staged image.  A JPEG whose coefficients and pixels do not fit what is left
     of the staging area is decoded on the host and goes on as raw pixels.
 
+    ``TCAMD_DEVICE_HUFFMAN=1`` (read at load; the default 0 is the route above)
+    moves the Huffman stage to the device too: the host only packs the scan
+    (``HostCodec.jpeg_stream_pack``, one pass over the blob) into the bottom of
+    the staging area, so the compressed bytes are what crosses PCIe; K23
+    ``jpeg_huffman`` (csrc/kernels/jpeg_huff.hip, one launch per 64 JPEGs,
+    before K22 on the slot's stream) writes the coefficients, which like the
+    pixels exist at the device-only top of the staging buffer alone.  One
+    fallback rule: a blob the pack declines, or one that does not fit, takes
+    the route above; an image whose status word K23 left non-zero (read after
+    the stream synchronise) is decoded by the host, which fills its row or
+    fails its request with the host decoder's message.
+
     The custom request parameter ``antialias`` (bool, default false) selects
     the antialiased resize for that request's images: the batch's device jobs
     are split by the flag into at most one K20 and one K21 ``resize_pack``
@@ -535,6 +547,7 @@ class PreprocessInception(Model):
 
         self._host = HostPreprocess(self.version)
         self.device_path = os.environ.get("TCAMD_DEVICE_PREPROCESS", "1") != "0"
+        self.device_huffman = os.environ.get("TCAMD_DEVICE_HUFFMAN", "0") == "1"
         if not self.device_path:
             return
         import torch
@@ -596,6 +609,10 @@ class PreprocessInception(Model):
             return blob, self._codec.jpeg_parse(blob)
         return decode_image(blob)
 
+    def _read_status(self, status):
+        """K23's status words of a batch, after the stream synchronise."""
+        return status.cpu().numpy()
+
     def execute(self, requests):
         if not self.device_path:
             return [self._host_one(r) for r in requests]
@@ -616,16 +633,32 @@ class PreprocessInception(Model):
         # bytes of the H2D copy); the pixels K22 decodes exist on the device only and take the top.
         dev_jobs = {False: [], True: []}  # by the request's antialias flag: (row, image shape, staging offset)
         jpeg_jobs = []  # (coefficient offset, parse, pixel offset)
+        huff_jobs = []  # device Huffman: (stream offset, coefficient offset, row, blob, antialias, request)
         host_jobs = []  # (row, image, antialias)
         rows = used = 0
         top = self.STAGE_BYTES
         for r in requests:
-            mark = (rows, used, top, len(dev_jobs[False]), len(dev_jobs[True]), len(jpeg_jobs), len(host_jobs))
+            mark = (rows, used, top, len(dev_jobs[False]), len(dev_jobs[True]), len(jpeg_jobs), len(host_jobs),
+                    len(huff_jobs))
             try:
                 aa = self._host.wants_antialias(r)
                 for item in [self._open(b) for b in r.input("INPUT").numpy().reshape(-1)]:
                     if isinstance(item, tuple):
                         blob, info = item
+                        if self.device_huffman:
+                            # the stream at the bottom; coefficients and pixels, device only, at the top
+                            at = -(-used // 16) * 16
+                            coef = (top - info.pixel_bytes - info.coef_bytes) // 128 * 128
+                            n = self._codec.jpeg_stream_pack(blob, stage[at:coef])[1] if at < coef else None
+                            if n is not None:
+                                used = at + n
+                                top -= info.pixel_bytes
+                                huff_jobs.append((at, coef, rows, blob, aa, len(plan)))
+                                jpeg_jobs.append((coef, info, top))
+                                dev_jobs[aa].append((rows, info.shape, top))
+                                top = coef
+                                rows += 1
+                                continue
                         coef = -(-used // 128) * 128
                         if coef + info.coef_bytes + info.pixel_bytes <= top:
                             self._codec.jpeg_entropy_decode(blob, stage[coef:coef + info.coef_bytes])
@@ -647,7 +680,7 @@ class PreprocessInception(Model):
                     rows += 1
             except Exception as e:  # noqa: BLE001 - an undecodable blob fails its own request
                 rows, used, top = mark[:3]
-                for jobs, n in zip((dev_jobs[False], dev_jobs[True], jpeg_jobs, host_jobs), mark[3:]):
+                for jobs, n in zip((dev_jobs[False], dev_jobs[True], jpeg_jobs, host_jobs, huff_jobs), mark[3:]):
                     del jobs[n:]
                 plan.append(e)
                 continue
@@ -663,6 +696,11 @@ class PreprocessInception(Model):
             src = slot["stage_dev"].data_ptr()
             if used:
                 hip.memcpy_async(src, slot["stage_host"], used, sh)
+            status = None
+            if huff_jobs:
+                status = torch.empty(len(huff_jobs), device=stream.device, dtype=torch.int32)
+                hip.jpeg_huffman([src + at for at, *_ in huff_jobs], [src + coef for _, coef, *_ in huff_jobs],
+                                 status.data_ptr(), stream=sh)
             if jpeg_jobs:
                 hip.jpeg_decode([src + coef for coef, _, _ in jpeg_jobs], [info for _, info, _ in jpeg_jobs],
                                 [src + pix for _, _, pix in jpeg_jobs], stream=sh)
@@ -678,6 +716,22 @@ class PreprocessInception(Model):
                             for r, p in zip(requests, plan))
             host_all = out.cpu().numpy() if want_host else None  # synchronises the stream
             hip.stream_synchronize(sh)
+            if status is not None:
+                # an image K23 gave up on: the host decodes it into its row, or its request fails
+                redo = [job for job, st in zip(huff_jobs, self._read_status(status)) if st]
+                for _, _, row, blob, aa, req in redo:
+                    if isinstance(plan[req], Exception):
+                        continue
+                    try:
+                        img = inception_preprocess(self._codec.jpeg_decode(blob), self.H, self.W, "NCHW", antialias=aa)
+                    except Exception as e:  # noqa: BLE001 - the host decoder's error fails this request alone
+                        plan[req] = e
+                        continue
+                    out[row].copy_(torch.from_numpy(img))
+                    if host_all is not None:
+                        host_all[row] = img
+                if redo:
+                    hip.stream_synchronize(sh)
         res = []
         for r, p in zip(requests, plan):
             if isinstance(p, Exception):

@@ -7,6 +7,7 @@ numpy only.  Decodes binary PPM (P6) / PGM (P5), a raw ``TCIMG`` container
 baseline JPEG through the host decoder of libtcamd_host.so (csrc/host/jpeg.cc).
 """
 
+import os
 import struct
 
 import numpy as np
@@ -222,7 +223,7 @@ def preprocess_batch_device(resized, scaling="INCEPTION", fmt="NCHW", dtype="FP3
 
 
 def preprocess_raw_batch_device(images, c, h, w, scaling="INCEPTION", fmt="NCHW", dtype="FP32", device=0,
-                                antialias=False):
+                                antialias=False, device_huffman=None):
     """``preprocess`` of a batch of decoded uint8 HWC images of any sizes on
     the GPU: the raw pixels go up in ONE uint8 host->device copy (a quarter of
     the bytes of the resized fp32 images, and no host resize), K20
@@ -232,8 +233,14 @@ def preprocess_raw_batch_device(images, c, h, w, scaling="INCEPTION", fmt="NCHW"
     device form of :func:`resize_area`) instead of K20.  An element may also be
     the ``bytes`` of a baseline JPEG file: the host only Huffman-decodes it
     into the same upload, and K22 ``jpeg_decode`` turns the coefficients into
-    pixels in a device buffer that K20 / K21 read.  Returns None when the
-    datatype has no device path (integer models)."""
+    pixels in a device buffer that K20 / K21 read.  With ``device_huffman``
+    (default: ``TCAMD_DEVICE_HUFFMAN=1`` in the environment) the host only
+    packs a JPEG's scan (``HostCodec.jpeg_stream_pack``) into the upload and K23
+    ``jpeg_huffman`` decodes it on the device; a blob the pack declines takes
+    the host's entropy decoder, and if K23 leaves a non-zero status word the
+    whole batch is done again with the host's entropy decoder, which gives the
+    answer or raises the error.  Returns None when the datatype has no device
+    path (integer models)."""
     if dtype not in _DEVICE_DTYPES:
         return None
     import torch
@@ -252,9 +259,26 @@ def preprocess_raw_batch_device(images, c, h, w, scaling="INCEPTION", fmt="NCHW"
            for im in items if not isinstance(im, tuple)):
         return None
     dev = torch.device("cuda", device)
-    # the upload: arrays as they are, JPEG coefficient buffers at 128-byte boundaries
+    from triton_client_amd.ops import host_codec
+
+    if device_huffman is None:
+        device_huffman = os.environ.get("TCAMD_DEVICE_HUFFMAN", "0") == "1"
+    # the upload: arrays as they are, JPEG coefficient buffers at 128-byte boundaries, packed JPEG
+    # streams (device Huffman) at 16-byte boundaries
     offs, shapes, up, pix = [], [], 0, 0
-    for im in items:
+    packed = {}  # item index -> its stream buffer
+    for k, im in enumerate(items):
+        if isinstance(im, tuple) and device_huffman:
+            buf = host_codec.aligned_buffer(_jpeg_codec().jpeg_stream_bound(len(im[0])))
+            n = _jpeg_codec().jpeg_stream_pack(im[0], buf)[1]
+            if n is not None:
+                packed[k] = buf[:n]
+                up = -(-up // 16) * 16
+                offs.append(up)
+                up += n
+                pix += im[1].pixel_bytes
+                shapes.append(im[1].shape)
+                continue
         if isinstance(im, tuple):
             up = -(-up // 128) * 128
             offs.append(up)
@@ -266,14 +290,28 @@ def preprocess_raw_batch_device(images, c, h, w, scaling="INCEPTION", fmt="NCHW"
             up += im.size
             shapes.append(im.shape)
     raw = np.empty(up, dtype=np.uint8)
-    for im, o in zip(items, offs):
-        if isinstance(im, tuple):
+    for k, (im, o) in enumerate(zip(items, offs)):
+        if k in packed:
+            raw[o:o + packed[k].size] = packed[k]
+        elif isinstance(im, tuple):
             _jpeg_codec().jpeg_entropy_decode(im[0], raw[o:o + im[1].coef_bytes])
         else:
             raw[o:o + im.size] = im.reshape(-1)
     src = torch.from_numpy(raw).to(dev, non_blocking=False)
     stream = torch.cuda.current_stream(dev).cuda_stream
     srcs = [src.data_ptr() + o for o in offs]
+    status = None
+    if packed:
+        # K23: the streams -> coefficient buffers that exist on the device only
+        at = [0]
+        for k in packed:
+            at.append(at[-1] + -(-items[k][1].coef_bytes // 128) * 128)
+        coefs = torch.empty(at[-1], device=dev, dtype=torch.uint8)
+        status = torch.empty(len(packed), device=dev, dtype=torch.int32)
+        hip.jpeg_huffman([srcs[k] for k in packed], [coefs.data_ptr() + a for a in at[:-1]], status.data_ptr(),
+                         stream=stream)
+        for k, a in zip(packed, at):
+            srcs[k] = coefs.data_ptr() + a
     if pix:
         decoded = torch.empty(pix, device=dev, dtype=torch.uint8)
         jobs, at = [], decoded.data_ptr()
@@ -289,4 +327,8 @@ def preprocess_raw_batch_device(images, c, h, w, scaling="INCEPTION", fmt="NCHW"
     per = c * h * w * dst.element_size()
     hip.resize_pack(srcs, shapes, [dst.data_ptr() + i * per for i in range(len(items))], dtype, fmt, c, h, w,
                     scale=scale, bias=bias, stream=stream, antialias=antialias)
-    return dst.cpu().numpy()
+    out = dst.cpu().numpy()
+    if status is not None and status.cpu().numpy().any():
+        return preprocess_raw_batch_device(images, c, h, w, scaling, fmt, dtype, device, antialias,
+                                           device_huffman=False)
+    return out

@@ -86,6 +86,9 @@ KNOBS = [
     Knob("TCAMD_DEVICE_PREPROCESS", "python", 1, "server/gpu_models.py",
          "GPU preprocess_inception: K20 resize_pack on the device; 0 = the numpy step",
          "tests/test_preprocess_device_gpu.py::test_knob_off_is_the_numpy_step"),
+    Knob("TCAMD_DEVICE_HUFFMAN", "python", 0, "server/gpu_models.py, utils/image.py",
+         "JPEG: 1 = the host packs the scan and K23 jpeg_huffman decodes it on the device; 0 = host entropy decode",
+         "tests/test_jpeg_huffman_gpu.py::test_the_knob_changes_the_route_and_not_one_bit_of_the_rows"),
     Knob("TCAMD_BYTES_HOST_MAX", "python", 8192, "tritonclient/utils/hip_shared_memory",
          "BYTES set with bytes_path=auto: host codec up to this many elements, K2 above",
          "tests/test_knobs.py::test_bytes_auto_path_knobs"),

@@ -67,21 +67,30 @@ struct Parsed {
   int mcux = 0, mcuy = 0;
 };
 
-void fill_info(const Parsed& p, TcamdJpegInfo* info) {
+// scale 1 is the full-size layout: 8 x 8 everywhere, 128-byte blocks at multiples of 128
+void fill_info(const Parsed& p, TcamdJpegInfo* info, int scale = 1) {
   std::memset(info, 0, sizeof(*info));
-  info->h = p.h;
-  info->w = p.w;
+  info->h = (p.h + scale - 1) / scale;
+  info->w = (p.w + scale - 1) / scale;
   info->ncomp = p.ncomp;
   info->hs = p.comp[0].h;
   info->vs = p.comp[0].v;
+  info->scale = scale;
   uint64_t off = (uint64_t)p.ncomp * 128;
   for (int c = 0; c < p.ncomp; ++c) {
     info->bw[c] = p.mcux * p.comp[c].h;
     info->bh[c] = p.mcuy * p.comp[c].v;
+    info->ny[c] = scaled_size(scale, p.comp[0].v, p.comp[c].v);
+    info->nx[c] = scaled_size(scale, p.comp[0].h, p.comp[c].h);
+    off = (off + 15) / 16 * 16;
     info->coef_off[c] = off;
-    off += (uint64_t)info->bw[c] * info->bh[c] * 128;
+    off += (uint64_t)info->bw[c] * info->bh[c] * info->ny[c] * info->nx[c] * 2;
   }
   info->coef_bytes = off;
+}
+
+void check_scale(int scale) {
+  if (!scale_ok(scale)) unsupported("scale %d (1, 2, 4 or 8)", scale);
 }
 
 void build_huff(Huff& t, const uint8_t* counts, const uint8_t* vals, int nvals) {
@@ -293,6 +302,16 @@ void entropy_decode(const uint8_t* d, size_t n, const Parsed& P, const TcamdJpeg
   uint16_t* qout = reinterpret_cast<uint16_t*>(buf);
   for (int c = 0; c < P.ncomp; ++c) std::memcpy(qout + 64 * c, P.q[P.comp[c].tq], 128);
   std::memset(buf + info.coef_off[0], 0, info.coef_bytes - info.coef_off[0]);
+  // zigzag index -> where the coefficient goes in its component's ny x nx block, -1 when dropped
+  int8_t slot[3][64];
+  uint64_t blk_bytes[3] = {0, 0, 0};
+  for (int c = 0; c < P.ncomp; ++c) {
+    for (int k = 0; k < 64; ++k) {
+      const int v = kZigzag[k] >> 3, u = kZigzag[k] & 7;
+      slot[c][k] = v < info.ny[c] && u < info.nx[c] ? (int8_t)(v * info.nx[c] + u) : (int8_t)-1;
+    }
+    blk_bytes[c] = (uint64_t)info.ny[c] * info.nx[c] * 2;
+  }
   Bits bits(d, n, P.pos);
   int pred[3] = {0, 0, 0};
   int rst = 0;
@@ -310,7 +329,8 @@ void entropy_decode(const uint8_t* d, size_t n, const Parsed& P, const TcamdJpeg
       for (int by = 0; by < k.v; ++by) {
         for (int bx = 0; bx < k.h; ++bx) {
           const uint64_t blk = (uint64_t)(my * k.v + by) * info.bw[c] + (uint64_t)(mx * k.h + bx);
-          int16_t* out = reinterpret_cast<int16_t*>(buf + info.coef_off[c] + blk * 128);
+          int16_t* out = reinterpret_cast<int16_t*>(buf + info.coef_off[c] + blk * blk_bytes[c]);
+          const int8_t* to = slot[c];
           int s = bits.symbol(dc);
           if (s > 11) bad("DC size category");
           pred[c] += bits.value(s);
@@ -330,7 +350,10 @@ void entropy_decode(const uint8_t* d, size_t n, const Parsed& P, const TcamdJpeg
             if (s > 10) bad("AC size category");
             i += r;
             if (i > 63) bad("run passes coefficient 63");
-            out[kZigzag[i]] = (int16_t)bits.value(s);
+            // a dropped coefficient goes to a sink: which ones are kept is not predictable at 1/2
+            int16_t sink;
+            int16_t* dst = to[i] >= 0 ? out + to[i] : &sink;
+            *dst = (int16_t)bits.value(s);
             ++i;
           }
         }
@@ -548,6 +571,68 @@ void reconstruct(const TcamdJpegInfo& info, const uint8_t* buf, uint8_t* out) {
   }
 }
 
+// one component's ny x nx blocks -> its sample plane, (bh*NY) x (bw*NX)
+template <int NY, int NX>
+void idct_plane_n(const uint16_t* q, const int16_t* coef, int bw, int bh, uint8_t* plane) {
+  const size_t stride = (size_t)bw * NX;
+  for (int by = 0; by < bh; ++by) {
+    for (int bx = 0; bx < bw; ++bx) {
+      const int16_t* blk = coef + ((size_t)by * bw + bx) * (NY * NX);
+      int ws[NY][NX];
+      for (int y = 0; y < NY; ++y) {
+        int v[NX];
+        for (int u = 0; u < NX; ++u) v[u] = dequantise(blk[y * NX + u], q[y * 8 + u]);
+        idct_row_n<NX>(v, ws[y]);
+      }
+      for (int x = 0; x < NX; ++x) {
+        int col[NY], s[NY];
+        for (int y = 0; y < NY; ++y) col[y] = ws[y][x];
+        idct_col_n<NY>(col, s);
+        for (int y = 0; y < NY; ++y) plane[((size_t)by * NY + y) * stride + (size_t)bx * NX + x] = (uint8_t)s[y];
+      }
+    }
+  }
+}
+
+// scale >= 2: every plane is at the output resolution; crop, and convert three of them
+void reconstruct_scaled(const TcamdJpegInfo& info, const uint8_t* buf, uint8_t* out) {
+  std::vector<uint8_t> store[3];
+  size_t stride[3] = {0, 0, 0};
+  const uint16_t* q = reinterpret_cast<const uint16_t*>(buf);
+  for (int c = 0; c < info.ncomp; ++c) {
+    const int ny = info.ny[c], nx = info.nx[c], bw = info.bw[c], bh = info.bh[c];
+    store[c].resize((size_t)bw * bh * ny * nx);
+    stride[c] = (size_t)bw * nx;
+    const int16_t* coef = reinterpret_cast<const int16_t*>(buf + info.coef_off[c]);
+    uint8_t* pl = store[c].data();
+    const uint16_t* qc = q + 64 * c;
+    switch (ny * 16 + nx) {
+      case 0x88: idct_plane_n<8, 8>(qc, coef, bw, bh, pl); break;
+      case 0x48: idct_plane_n<4, 8>(qc, coef, bw, bh, pl); break;
+      case 0x44: idct_plane_n<4, 4>(qc, coef, bw, bh, pl); break;
+      case 0x24: idct_plane_n<2, 4>(qc, coef, bw, bh, pl); break;
+      case 0x22: idct_plane_n<2, 2>(qc, coef, bw, bh, pl); break;
+      case 0x12: idct_plane_n<1, 2>(qc, coef, bw, bh, pl); break;
+      default: idct_plane_n<1, 1>(qc, coef, bw, bh, pl); break;
+    }
+  }
+  for (int y = 0; y < info.h; ++y) {
+    if (info.ncomp == 1) {
+      std::memcpy(out + (size_t)y * info.w, store[0].data() + (size_t)y * stride[0], (size_t)info.w);
+      continue;
+    }
+    for (int x = 0; x < info.w; ++x) {
+      int rgb[3];
+      ycc_to_rgb(store[0][(size_t)y * stride[0] + x], store[1][(size_t)y * stride[1] + x],
+                 store[2][(size_t)y * stride[2] + x], rgb);
+      uint8_t* px = out + ((size_t)y * info.w + x) * 3;
+      px[0] = (uint8_t)rgb[0];
+      px[1] = (uint8_t)rgb[1];
+      px[2] = (uint8_t)rgb[2];
+    }
+  }
+}
+
 int report(const Error& e, char* msg, int cap) {
   if (msg && cap > 0) std::snprintf(msg, (size_t)cap, "%s", e.what);
   return e.code;
@@ -586,6 +671,45 @@ int tcamd_host_jpeg_entropy_decode(const uint8_t* blob, uint64_t n, uint8_t* buf
     fill_info(P, &info);
     if (cap < info.coef_bytes) bad("coefficient buffer too small");
     entropy_decode(blob, (size_t)n, P, info, buf);
+  });
+}
+
+int tcamd_host_jpeg_parse_scaled(const uint8_t* blob, uint64_t n, int scale, TcamdJpegInfo* info, char* msg,
+                                 int msg_cap) {
+  return guarded(msg, msg_cap, [&] {
+    check_scale(scale);
+    Parsed P;
+    parse(blob, (size_t)n, P);
+    fill_info(P, info, scale);
+  });
+}
+
+int tcamd_host_jpeg_entropy_decode_scaled(const uint8_t* blob, uint64_t n, int scale, uint8_t* buf, uint64_t cap,
+                                          char* msg, int msg_cap) {
+  return guarded(msg, msg_cap, [&] {
+    check_scale(scale);
+    Parsed P;
+    parse(blob, (size_t)n, P);
+    TcamdJpegInfo info;
+    fill_info(P, &info, scale);
+    if (cap < info.coef_bytes) bad("coefficient buffer too small");
+    entropy_decode(blob, (size_t)n, P, info, buf);
+  });
+}
+
+int tcamd_host_jpeg_decode_scaled(const uint8_t* blob, uint64_t n, int scale, uint8_t* out, uint64_t cap, char* msg,
+                                  int msg_cap) {
+  if (scale == 1) return tcamd_host_jpeg_decode(blob, n, out, cap, msg, msg_cap);
+  return guarded(msg, msg_cap, [&] {
+    check_scale(scale);
+    Parsed P;
+    parse(blob, (size_t)n, P);
+    TcamdJpegInfo info;
+    fill_info(P, &info, scale);
+    if (cap < (uint64_t)info.h * info.w * info.ncomp) bad("pixel buffer too small");
+    std::vector<uint8_t> coef((size_t)info.coef_bytes);
+    entropy_decode(blob, (size_t)n, P, info, coef.data());
+    reconstruct_scaled(info, coef.data(), out);
   });
 }
 

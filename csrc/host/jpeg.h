@@ -19,6 +19,9 @@ struct TcamdJpegInfo {
   int32_t bw[3], bh[3];
   uint64_t coef_off[3];
   uint64_t coef_bytes;  // the whole buffer, tables included
+  // the reduced-size decode below; 1 and 8 x 8 from the full-size entry points
+  int32_t scale;
+  int32_t ny[3], nx[3];
 };
 
 // Each call returns TCAMD_JPEG_OK or a code with a message in msg (msg_cap
@@ -29,6 +32,24 @@ int tcamd_host_jpeg_parse(const uint8_t* blob, uint64_t n, TcamdJpegInfo* info, 
 int tcamd_host_jpeg_entropy_decode(const uint8_t* blob, uint64_t n, uint8_t* buf, uint64_t cap, char* msg, int msg_cap);
 // out: h * w * ncomp bytes, HWC (cap is checked).
 int tcamd_host_jpeg_decode(const uint8_t* blob, uint64_t n, uint8_t* out, uint64_t cap, char* msg, int msg_cap);
+
+// The reduced-size decode (contract: tests/jpeg_scaled_cases.py): scale is 1, 2,
+// 4 or 8, anything else TCAMD_JPEG_UNSUPPORTED "scale ...".  info.h x info.w is
+// the output, ceil(H / scale) x ceil(W / scale); component c is transformed
+// with an ny[c] x nx[c] inverse DCT of its lowest frequencies (8 / scale, times
+// its subsampling, at most 8), so for scale >= 2 every component comes out at
+// the output resolution and none is upsampled.  The coefficient buffer is
+// compact: uint16 q[ncomp][64] as above, then component c's blocks at the
+// 16-byte-aligned coef_off[c], each ny[c] * nx[c] int16, vertical frequency
+// major.  At scale 1 the three calls are the three above, byte for byte.  The
+// entropy decoder walks the whole stream and only drops what it does not
+// store: a blob fails at a scale exactly where, and as, it fails at full size.
+int tcamd_host_jpeg_parse_scaled(const uint8_t* blob, uint64_t n, int scale, TcamdJpegInfo* info, char* msg,
+                                 int msg_cap);
+int tcamd_host_jpeg_entropy_decode_scaled(const uint8_t* blob, uint64_t n, int scale, uint8_t* buf, uint64_t cap,
+                                          char* msg, int msg_cap);
+int tcamd_host_jpeg_decode_scaled(const uint8_t* blob, uint64_t n, int scale, uint8_t* out, uint64_t cap, char* msg,
+                                  int msg_cap);
 
 // The entropy decode on the device, K23 jpeg_huffman (csrc/kernels/jpeg_huff.hip).
 // tcamd_host_jpeg_stream_pack parses the blob (info, when not null, is its

@@ -72,6 +72,57 @@ TCAMD_HD void idct_col(const int* ws, int* s) {
     s[y] = clampi(((s[y] + (1 << (kC2Bits + kPass1Bits + 2))) >> (kC2Bits + kPass1Bits + 3)) + 128, 0, 255);
 }
 
+// The reduced-size decode (scale 1/2, 1/4, 1/8; contract: tests/jpeg_scaled_cases.py) keeps the
+// N lowest frequencies of an axis and runs an N-point pass with the same bit widths and shifts:
+// M[u][x] = round(s(u) cos((2x+1) u pi / (2N)) * 2^BITS).  sqrt(2) cos(k pi / 8) is the 8-point
+// c2 (k = 1) and c6 (k = 3), and sqrt(2) cos(pi / 4) = 1 is c4, so no constant is new.
+template <int N, int BITS>
+TCAMD_HD void idct_n(const int* in, int* out) {
+  using K = IdctK<BITS>;
+  static_assert(N == 1 || N == 2 || N == 4 || N == 8, "transform size");
+  if constexpr (N == 8) {
+    idct8<BITS>(in, out);
+  } else if constexpr (N == 4) {
+    const int a = K::c4 * (in[0] + in[2]), b = K::c4 * (in[0] - in[2]);
+    const int p = K::c2 * in[1] + K::c6 * in[3], q = K::c6 * in[1] - K::c2 * in[3];
+    out[0] = a + p;
+    out[3] = a - p;
+    out[1] = b + q;
+    out[2] = b - q;
+  } else if constexpr (N == 2) {
+    out[0] = K::c4 * (in[0] + in[1]);
+    out[1] = K::c4 * (in[0] - in[1]);
+  } else {
+    out[0] = K::c4 * in[0];
+  }
+}
+
+// idct_row / idct_col for an N-point axis
+template <int N>
+TCAMD_HD void idct_row_n(const int* v, int* ws) {
+  idct_n<N, kC1Bits>(v, ws);
+  TCAMD_UNROLL
+  for (int x = 0; x < N; ++x) ws[x] = (ws[x] + (1 << (kC1Bits - kPass1Bits - 1))) >> (kC1Bits - kPass1Bits);
+}
+
+template <int N>
+TCAMD_HD void idct_col_n(const int* ws, int* s) {
+  idct_n<N, kC2Bits>(ws, s);
+  TCAMD_UNROLL
+  for (int y = 0; y < N; ++y)
+    s[y] = clampi(((s[y] + (1 << (kC2Bits + kPass1Bits + 2))) >> (kC2Bits + kPass1Bits + 3)) + 128, 0, 255);
+}
+
+// The transform size of a component with sampling hc x vc under the maximum hmax x vmax at scale
+// 1/s: N = 8/s samples per 8 source pixels of the component, times its subsampling, capped at 8.
+// For s >= 2 every component comes out at the output resolution and nothing is upsampled.
+TCAMD_HD int scaled_size(int scale, int max_sampling, int sampling) {
+  const int n = 8 / scale * max_sampling / sampling;
+  return n < 8 ? n : 8;
+}
+
+TCAMD_HD bool scale_ok(int scale) { return scale == 1 || scale == 2 || scale == 4 || scale == 8; }
+
 // The chroma sample under luma pixel (X, Y) by the triangle filter.  p(cx, cy)
 // reads the chroma plane; cw x ch is its valid extent, where edges replicate.
 template <int HS, int VS, class F>

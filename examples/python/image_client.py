@@ -8,7 +8,10 @@ by the server's classification extension.  Images are decoded with PIL when
 available, else with the framework's PPM/raw/JPEG decoder.  With
 ``--device-resize`` a JPEG file is not decoded here at all: its bytes go to
 ``preprocess_raw_batch_device``, which Huffman-decodes on the host and leaves
-the rest to the K22 jpeg_decode kernel.
+the rest to the K22 jpeg_decode kernel.  ``--jpeg-scale`` decodes JPEG files in
+the DCT domain at 1/2, 1/4 or 1/8 of their size (0: the largest of them that
+the model's input size does not have to upscale), on the host path with the
+framework's decoder and with ``--device-resize`` on the GPU.
 """
 import argparse
 import os
@@ -24,7 +27,21 @@ import tritonclient.http as httpclient
 from tritonclient.utils import InferenceServerException, triton_to_np_dtype
 
 
-def load_image(path):
+def load_image(path, jpeg_scale=1, h=0, w=0):
+    """``jpeg_scale`` other than 1 decodes a JPEG file with the framework's
+    decoder at that scale (0: ``jpeg_auto_scale`` for an ``h x w`` model input)."""
+    if jpeg_scale != 1:
+        with open(path, "rb") as f:
+            blob = f.read()
+        if blob[:2] == b"\xff\xd8":
+            from triton_client_amd.ops import host_codec
+            from triton_client_amd.utils.image import decode_image, jpeg_auto_scale
+
+            if jpeg_scale == 0:
+                full = host_codec.load().jpeg_parse(blob)
+                jpeg_scale = jpeg_auto_scale(full.h, full.w, h, w)
+            img = decode_image(blob, jpeg_scale)
+            return np.repeat(img, 3, axis=2) if img.shape[2] == 1 else img
     try:
         from PIL import Image
 
@@ -128,6 +145,10 @@ def main():
                     help="resize with the antialiased triangle filter (support scaled by the downscale ratio, as "
                          "Pillow's BILINEAR resize) instead of 2x2-tap bilinear; with --device-resize it runs the K21 "
                          "resize_pack_aa kernel")
+    ap.add_argument("--jpeg-scale", type=int, choices=[0, 1, 2, 4, 8], default=1,
+                    help="decode JPEG files at 1/N of their size in the DCT domain (0: the largest N the model's input "
+                         "size does not have to upscale); with --device-resize the K22 jpeg_decode kernel does it "
+                         "from a coefficient upload of about 1/N^2 of the bytes")
     ap.add_argument("image_filename")
     a = ap.parse_args()
     protocol = a.protocol.lower()
@@ -158,7 +179,7 @@ def main():
 
         resized = []
         for f in files:
-            img = load_image(f)
+            img = load_image(f, a.jpeg_scale, h, w)
             if c == 1:
                 img = img.mean(axis=2, keepdims=True)
             resized.append(resize_area(img, h, w) if a.antialias else resize_bilinear(img.astype(np.float32), h, w))
@@ -169,11 +190,12 @@ def main():
         from triton_client_amd.utils.image import preprocess_raw_batch_device
 
         packed = preprocess_raw_batch_device([load_for_device(f) for f in files], c, h, w, a.scaling, fmt, dtype,
-                                             antialias=a.antialias)
+                                             antialias=a.antialias, jpeg_scale=a.jpeg_scale)
         if packed is not None:
             images = list(packed)
     if images is None:
-        images = [preprocess(load_image(f), fmt, dtype, c, h, w, a.scaling, a.antialias) for f in files]
+        images = [preprocess(load_image(f, a.jpeg_scale, h, w), fmt, dtype, c, h, w, a.scaling, a.antialias)
+                  for f in files]
     # batches (cycling over the images to fill the last batch)
     requests, batched_names = [], []
     idx = 0

@@ -19,7 +19,12 @@ place of K20 (``--kernel``).  ``--jpeg`` sends tests/golden/jpeg's 640x480
 (``TCAMD_DEVICE_PREPROCESS=0`` in the environment: decodes on the host);
 ``--kernel --jpeg`` also times the host's entropy decode and full decode, and in
 a second JSON line the stream pack (host) and K23 ``jpeg_huffman`` on one and on
-8 copies.  ``TCAMD_DEVICE_HUFFMAN=1`` in the environment of a served run makes
+8 copies.  ``--jpeg-scale N`` (1, 2, 4, 8, or 0 for the automatic scale of a
+224 x 224 target) sends the request parameter ``jpeg_scale`` (served) or times
+the reduced-size decode of K22 and of the host and prints the bytes of the
+compact coefficient buffer (``--kernel --jpeg``; the K23 line is left out: K23
+writes the full layout only).  ``--jpeg-file PATH`` takes another baseline JPEG
+than the fixture, a large photo for instance.  ``TCAMD_DEVICE_HUFFMAN=1`` in the environment of a served run makes
 the server pack the scan and run K23 instead of the host's entropy decode.
 """
 
@@ -82,15 +87,18 @@ def kernel_time(n, h, w, iters, antialias=False):
                       "max_abs_err_vs_float64": err, "numpy_host_ms_per_image": round(host_ms, 3)}))
 
 
-def jpeg_fixture():
+def jpeg_fixture(path=None):
     import glob
 
+    if path:
+        with open(path, "rb") as f:
+            return f.read()
     (path,) = glob.glob(os.path.join(REPO, "tests", "golden", "jpeg", "b01_*.jpg"))
     with open(path, "rb") as f:
         return f.read()
 
 
-def jpeg_kernel_time(n, iters):
+def jpeg_kernel_time(n, iters, scale=1, path=None):
     import numpy as np
     import torch
 
@@ -98,12 +106,17 @@ def jpeg_kernel_time(n, iters):
 
     torch.cuda.set_device(0)
     hc = host_codec.load()
-    blob = jpeg_fixture()
-    info = hc.jpeg_parse(blob)
+    blob = jpeg_fixture(path)
+    if scale == 0:
+        from triton_client_amd.utils.image import jpeg_auto_scale
+
+        full = hc.jpeg_parse(blob)
+        scale = jpeg_auto_scale(full.h, full.w, 224, 224)
+    info = hc.jpeg_parse(blob, scale)
     coef = np.empty(info.coef_bytes, dtype=np.uint8)
     host = {}
-    for what, fn in (("entropy_decode", lambda: hc.jpeg_entropy_decode(blob, coef)),
-                     ("full_decode", lambda: hc.jpeg_decode(blob))):
+    for what, fn in (("entropy_decode", lambda: hc.jpeg_entropy_decode(blob, coef, scale)),
+                     ("full_decode", lambda: hc.jpeg_decode(blob, scale))):
         fn()
         ts = []
         for _ in range(20):
@@ -111,7 +124,7 @@ def jpeg_kernel_time(n, iters):
             fn()
             ts.append((time.perf_counter() - t0) * 1e3)
         host[what] = ts
-    want = hc.jpeg_decode(blob)
+    want = hc.jpeg_decode(blob, scale)
     stride = -(-info.coef_bytes // 128) * 128
     src = torch.from_numpy(np.concatenate([np.pad(coef, (0, stride - coef.size))] * n)).cuda()
     dst = torch.zeros(n, info.pixel_bytes, device="cuda", dtype=torch.uint8)
@@ -135,7 +148,7 @@ def jpeg_kernel_time(n, iters):
         times.append(a.elapsed_time(b) * 1e3)
     equal = bool((dst.cpu().numpy().reshape((n,) + want.shape) == want).all())
     moved = n * (info.coef_bytes + info.pixel_bytes)
-    print(json.dumps({"kernel": "K22 jpeg_decode", "images": n, "image": list(info.shape),
+    print(json.dumps({"kernel": "K22 jpeg_decode", "images": n, "jpeg_scale": scale, "image": list(info.shape),
                       "sampling": [info.hs, info.vs], "jpeg_bytes": len(blob), "coef_bytes": int(info.coef_bytes),
                       "launches": iters, "mean_us": round(float(np.mean(times)), 2),
                       "min_us": round(float(np.min(times)), 2), "max_us": round(float(np.max(times)), 2),
@@ -145,11 +158,15 @@ def jpeg_kernel_time(n, iters):
                                                           round(float(np.mean(host["entropy_decode"])), 3)],
                       "host_full_decode_ms_min_mean": [round(float(np.min(host["full_decode"])), 3),
                                                        round(float(np.mean(host["full_decode"])), 3)]}))
+    if scale != 1:
+        return  # K23 writes the full layout only
 
     # K23: the pack on the host, the Huffman stage on the device, against the host's entropy decode above
     packed = host_codec.aligned_buffer(hc.jpeg_stream_bound(len(blob)))
     _, used = hc.jpeg_stream_pack(blob, packed)
-    assert used is not None
+    if used is None:  # a scan above what K23's workspace holds (--jpeg-file): the host's entropy decoder's turn
+        print(json.dumps({"kernel": "K23 jpeg_huffman", "packable": False}))
+        return
     pack_ms = []
     for _ in range(20):
         t0 = time.perf_counter()
@@ -262,18 +279,28 @@ def served(args):
     try:
         srv.wait_ready(timeout=900, model="preprocess_inception_ensemble")
         img = np.random.default_rng(0).integers(0, 256, (args.height, args.width, 3), dtype=np.uint8)
-        data = np.array([jpeg_fixture() if args.jpeg else encode_raw(img)], dtype=np.object_).reshape(1, 1)
+        data = np.array([jpeg_fixture(args.jpeg_file) if args.jpeg else encode_raw(img)],
+                        dtype=np.object_).reshape(1, 1)
+        shape = [args.height, args.width, 3]
+        if args.jpeg:
+            from triton_client_amd.ops import host_codec
+
+            shape = list(host_codec.load().jpeg_parse(data[0, 0]).shape)
         c = grpcclient.InferenceServerClient(srv.grpc_url)
         inp = grpcclient.InferInput("INPUT", [1, 1], "BYTES")
         inp.set_data_from_numpy(data)
-        params = {"antialias": True} if args.antialias else None
+        params = {"antialias": True} if args.antialias else {}
+        if args.jpeg_scale is not None:
+            params["jpeg_scale"] = args.jpeg_scale
+        params = params or None
         first = c.infer("preprocess_inception_ensemble", [inp], parameters=params).as_numpy("OUTPUT")
         assert first.shape == (1, 1000), first.shape
         kind = c.get_model_config("preprocess_inception", as_json=True)["config"]["instance_group"][0]["kind"]
         for conc in args.concurrency:
             res = closed_loop(c, grpcclient, inp, conc, args.warmup, args.seconds, params)
-            res.update(antialias=args.antialias, image=[args.height, args.width, 3], preprocess_kind=kind,
-                       encoding="JPEG" if args.jpeg else "TCIMG",
+            res.update(antialias=args.antialias, image=shape, preprocess_kind=kind,
+                       encoding="JPEG" if args.jpeg else "TCIMG", jpeg_scale=args.jpeg_scale,
+                       blob_bytes=len(data[0, 0]),
                        device_preprocess=os.environ.get("TCAMD_DEVICE_PREPROCESS", "1") != "0",
                        device_huffman=os.environ.get("TCAMD_DEVICE_HUFFMAN", "0") == "1",
                        top1=int(first[0].argmax()))
@@ -290,6 +317,10 @@ def main():
                     help="the antialiased resize: request parameter antialias=true (served), K21 (--kernel)")
     ap.add_argument("--jpeg", action="store_true",
                     help="the committed 640x480 JPEG fixture: as the request's blob (served), K22 alone (--kernel)")
+    ap.add_argument("--jpeg-scale", type=int, choices=[0, 1, 2, 4, 8], default=None,
+                    help="the reduced-size JPEG decode: request parameter jpeg_scale (served), K22 at that scale "
+                         "(--kernel --jpeg); 0 is the automatic scale for 224 x 224")
+    ap.add_argument("--jpeg-file", default="", metavar="PATH", help="--jpeg: this baseline JPEG instead of the fixture")
     ap.add_argument("--concurrency", type=int, nargs="+", default=[1, 8])
     ap.add_argument("--height", type=int, default=480)
     ap.add_argument("--width", type=int, default=640)
@@ -300,7 +331,7 @@ def main():
     ap.add_argument("--server-log", default="", metavar="PATH", help="keep the server's log in this file")
     args = ap.parse_args()
     if args.kernel and args.jpeg:
-        jpeg_kernel_time(args.images, args.iters)
+        jpeg_kernel_time(args.images, args.iters, 1 if args.jpeg_scale is None else args.jpeg_scale, args.jpeg_file)
     elif args.kernel:
         kernel_time(args.images, args.height, args.width, args.iters, args.antialias)
     else:

@@ -10,7 +10,14 @@ K22's workgroup tile (kTileW x kTileH in csrc/kernels/jpeg.hip).
 ``--huff`` writes tests/golden/jpeg_huff instead: the streams that exercise K23
 ``jpeg_huffman`` (csrc/kernels/jpeg_huff.hip) beyond what the fixtures above do,
 each ``.jpg`` under 64 KB and its own ``manifest.json``, without Pillow's
-decodes: the oracle of the Huffman stage is the host entropy decoder."""
+decodes: the oracle of the Huffman stage is the host entropy decoder.
+
+``--scaled`` writes tests/golden/jpeg_scaled: Pillow's ``draft`` decode (the
+DCT-domain 1/2, 1/4 and 1/8 decode of libjpeg-turbo) of the existing ``.jpg``
+files of tests/golden/jpeg, as ``.npy``, for each scale at which the draft
+comes out at exactly ``ceil(H / s) x ceil(W / s)``, and a ``manifest.json``
+with the max and mean absolute difference of the numpy reference
+(tests/jpeg_scaled_cases.py) to each.  It writes no JPEG file."""
 
 import io
 import json
@@ -103,8 +110,40 @@ def main(out=OUT, fixtures=FIXTURES, first_seed=1000, decodes=True):
         f.write("\n")
 
 
+SCALED_OUT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests", "golden", "jpeg_scaled")
+
+
+def scaled(out=SCALED_OUT):
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+    from tests import jpeg_cases as jc
+    from tests import jpeg_scaled_cases as js
+
+    os.makedirs(out, exist_ok=True)
+    entries = []
+    for e in jc.decodable():
+        data = jc.blob(e)
+        for s in (2, 4, 8):
+            im = Image.open(io.BytesIO(data))
+            im.draft(im.mode, (-(-e["w"] // s), -(-e["h"] // s)))
+            a = np.asarray(im)
+            if a.shape[:2] != (-(-e["h"] // s), -(-e["w"] // s)):
+                continue  # Pillow picked another scale for this size
+            name = "%s_s%d.npy" % (e["name"], s)
+            np.save(os.path.join(out, name), a)
+            d = np.abs(js.decode(data, s).astype(np.int64) - (a[:, :, None] if a.ndim == 2 else a))
+            entries.append({"name": e["name"], "scale": s, "file": name, "max": int(d.max()),
+                            "mean": round(float(d.mean()), 4)})
+            print("%-28s 1/%d  max %3d  mean %.4f" % (e["name"], s, d.max(), d.mean()))
+    with open(os.path.join(out, "manifest.json"), "w") as f:
+        json.dump({"pillow": features.version("pil"), "libjpeg_turbo": features.version_feature("libjpeg_turbo"),
+                   "drafts": entries}, f, indent=1)
+        f.write("\n")
+
+
 if __name__ == "__main__":
-    if sys.argv[1:] == ["--huff"]:
+    if sys.argv[1:] == ["--scaled"]:
+        scaled()
+    elif sys.argv[1:] == ["--huff"]:
         main(HUFF_OUT, HUFF_FIXTURES, first_seed=2000, decodes=False)
     else:
         main()

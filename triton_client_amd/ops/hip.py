@@ -135,6 +135,15 @@ _SIGS = {
         ],
         ctypes.c_int,
     ),
+    "tcamd_jpeg_decode_scaled": (
+        [
+            ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32),
+            ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32),
+            ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32),
+            ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.c_void_p,
+        ],
+        ctypes.c_int,
+    ),
     "tcamd_jpeg_huffman": (
         [
             ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p), ctypes.c_void_p, ctypes.c_int,
@@ -734,14 +743,34 @@ def jpeg_decode(srcs, infos, dsts, stream=None):
     pixels, bitwise those of the host decode.  Images of mixed sizes and
     samplings share a launch, 64 at a time.  A dimension outside
     [1, :data:`RESIZE_MAX_DIM`], an unsupported component count or sampling or a
-    misaligned source raises (hipErrorInvalidValue) without a launch."""
+    misaligned source raises (hipErrorInvalidValue) without a launch.
+
+    A parse with ``scale`` 2, 4 or 8 (``HostCodec.jpeg_parse(blob, scale)``:
+    ``h x w`` the reduced size, ``ny`` / ``nx`` each component's transform size)
+    asks for the reduced-size decode of the compact coefficient buffer of that
+    scale.  One call takes images of mixed sizes, samplings and scales: the
+    full-size images go through the full-size kernel in launches of their own,
+    exactly as in a call without scaled images, and the images of scales 2, 4
+    and 8 share launches of the scaled kernel, 64 at a time, which dispatches
+    per image.  A scale outside {1, 2, 4, 8}, or an ``ny`` / ``nx`` that does
+    not follow from the scale and the sampling, raises (hipErrorInvalidValue)
+    without a launch."""
     n = len(srcs)
     if len(infos) != n or len(dsts) != n:
         raise ValueError("jpeg_decode: srcs, infos and dsts must have one entry per image")
     s = (ctypes.c_void_p * max(n, 1))(*[int(p) for p in srcs])
     d = (ctypes.c_void_p * max(n, 1))(*[int(p) for p in dsts])
     cols = [(ctypes.c_int32 * max(n, 1))(*[int(getattr(i, f)) for i in infos]) for f in ("h", "w", "ncomp", "hs", "vs")]
-    _check(_load().tcamd_jpeg_decode(s, *cols, n, d, _vp(stream)), "jpeg_decode")
+    scales = [int(getattr(i, "scale", 1)) for i in infos]
+    if all(k == 1 for k in scales):
+        _check(_load().tcamd_jpeg_decode(s, *cols, n, d, _vp(stream)), "jpeg_decode")
+        return
+    sc = (ctypes.c_int32 * n)(*scales)
+    ny = (ctypes.c_int32 * (3 * n))(*[int(i.ny[c]) if k != 1 or hasattr(i, "ny") else 8 for i, k in zip(infos, scales)
+                                      for c in range(3)])
+    nx = (ctypes.c_int32 * (3 * n))(*[int(i.nx[c]) if k != 1 or hasattr(i, "nx") else 8 for i, k in zip(infos, scales)
+                                      for c in range(3)])
+    _check(_load().tcamd_jpeg_decode_scaled(s, *cols, sc, ny, nx, n, d, _vp(stream)), "jpeg_decode")
 
 
 def jpeg_huffman(streams, coefs, status, stream=None):

@@ -10,11 +10,14 @@ _PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libtcam
 class JpegInfo(ctypes.Structure):
     """TcamdJpegInfo of csrc/host/jpeg.h: the image and the layout of its
     coefficient buffer (uint16 q[ncomp][64], then component c's ``bw[c] x
-    bh[c]`` blocks of 64 int16 at ``coef_off[c]``)."""
+    bh[c]`` blocks of ``ny[c] * nx[c]`` int16 at ``coef_off[c]``).  ``h x w``
+    is the decoded size: the source's at ``scale`` 1 (8 x 8 blocks), and
+    ``ceil(H / scale) x ceil(W / scale)`` at 2, 4 and 8."""
 
     _fields_ = [("h", ctypes.c_int32), ("w", ctypes.c_int32), ("ncomp", ctypes.c_int32), ("hs", ctypes.c_int32),
                 ("vs", ctypes.c_int32), ("bw", ctypes.c_int32 * 3), ("bh", ctypes.c_int32 * 3),
-                ("coef_off", ctypes.c_uint64 * 3), ("coef_bytes", ctypes.c_uint64)]
+                ("coef_off", ctypes.c_uint64 * 3), ("coef_bytes", ctypes.c_uint64), ("scale", ctypes.c_int32),
+                ("ny", ctypes.c_int32 * 3), ("nx", ctypes.c_int32 * 3)]
 
     @property
     def shape(self):
@@ -32,6 +35,15 @@ def aligned_buffer(nbytes, align=16):
     return a[o:o + nbytes]
 
 
+JPEG_SCALES = (1, 2, 4, 8)
+
+
+def _check_scale(scale):
+    if isinstance(scale, bool) or not isinstance(scale, (int, np.integer)) or scale not in JPEG_SCALES:
+        raise ValueError("jpeg scale must be 1, 2, 4 or 8, not %r" % (scale,))
+    return int(scale)
+
+
 _JPEG_KIND = {1: "unsupported JPEG: ", 2: "malformed JPEG: "}
 JPEG_NOT_PACKABLE = 3  # TCAMD_JPEG_NOT_PACKABLE: no error, the host entropy decoder's turn
 
@@ -45,6 +57,13 @@ class HostCodec:
         for fn in (lib.tcamd_host_jpeg_entropy_decode, lib.tcamd_host_jpeg_decode):
             fn.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_char_p,
                            ctypes.c_int]
+            fn.restype = ctypes.c_int
+        lib.tcamd_host_jpeg_parse_scaled.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int,
+                                                     ctypes.POINTER(JpegInfo), ctypes.c_char_p, ctypes.c_int]
+        lib.tcamd_host_jpeg_parse_scaled.restype = ctypes.c_int
+        for fn in (lib.tcamd_host_jpeg_entropy_decode_scaled, lib.tcamd_host_jpeg_decode_scaled):
+            fn.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64,
+                           ctypes.c_char_p, ctypes.c_int]
             fn.restype = ctypes.c_int
         lib.tcamd_host_jpeg_stream_bound.argtypes = [ctypes.c_uint64]
         lib.tcamd_host_jpeg_stream_bound.restype = ctypes.c_uint64
@@ -103,28 +122,46 @@ class HostCodec:
         if rc:
             raise ValueError(_JPEG_KIND.get(rc, "JPEG: ") + msg.value.decode())
 
-    def jpeg_parse(self, blob):
+    def jpeg_parse(self, blob, scale=1):
         """The :class:`JpegInfo` of a JPEG blob; ``ValueError`` ("unsupported
-        JPEG: ..." / "malformed JPEG: ...") when it cannot be decoded."""
+        JPEG: ..." / "malformed JPEG: ...") when it cannot be decoded.  With
+        ``scale`` 2, 4 or 8 it describes the reduced-size decode: the scaled
+        shape, each component's transform size and the compact buffer."""
         info = JpegInfo()
         msg = ctypes.create_string_buffer(96)
-        self._jpeg_check(self._lib.tcamd_host_jpeg_parse(blob, len(blob), ctypes.byref(info), msg, len(msg)), msg)
+        if _check_scale(scale) == 1:
+            rc = self._lib.tcamd_host_jpeg_parse(blob, len(blob), ctypes.byref(info), msg, len(msg))
+        else:
+            rc = self._lib.tcamd_host_jpeg_parse_scaled(blob, len(blob), scale, ctypes.byref(info), msg, len(msg))
+        self._jpeg_check(rc, msg)
         return info
 
-    def jpeg_entropy_decode(self, blob, out):
+    def jpeg_entropy_decode(self, blob, out, scale=1):
         """Huffman-decode ``blob`` into the uint8 array ``out`` (at least
-        ``coef_bytes`` of its parse, 16-byte aligned): quantisation tables,
-        then the de-zigzagged int16 coefficients, not dequantised."""
+        ``coef_bytes`` of its parse at ``scale``, 16-byte aligned):
+        quantisation tables, then the de-zigzagged int16 coefficients, not
+        dequantised.  At ``scale`` 2, 4 or 8 only the coefficients the reduced
+        transform uses are stored; the stream is walked and checked in full."""
         msg = ctypes.create_string_buffer(96)
-        self._jpeg_check(self._lib.tcamd_host_jpeg_entropy_decode(blob, len(blob), out.ctypes.data, out.size, msg,
-                                                             len(msg)), msg)
+        if _check_scale(scale) == 1:
+            rc = self._lib.tcamd_host_jpeg_entropy_decode(blob, len(blob), out.ctypes.data, out.size, msg, len(msg))
+        else:
+            rc = self._lib.tcamd_host_jpeg_entropy_decode_scaled(blob, len(blob), scale, out.ctypes.data, out.size,
+                                                                 msg, len(msg))
+        self._jpeg_check(rc, msg)
 
-    def jpeg_decode(self, blob):
-        """Blob -> uint8 [H, W, 1 or 3], entirely on the host."""
-        info = self.jpeg_parse(blob)
+    def jpeg_decode(self, blob, scale=1):
+        """Blob -> uint8 [H, W, 1 or 3], entirely on the host; at ``scale`` 2, 4
+        or 8 decoded in the DCT domain to ``ceil(H / scale) x ceil(W / scale)``."""
+        info = self.jpeg_parse(blob, scale)
         out = np.empty(info.shape, dtype=np.uint8)
         msg = ctypes.create_string_buffer(96)
-        self._jpeg_check(self._lib.tcamd_host_jpeg_decode(blob, len(blob), out.ctypes.data, out.size, msg, len(msg)), msg)
+        if scale == 1:
+            rc = self._lib.tcamd_host_jpeg_decode(blob, len(blob), out.ctypes.data, out.size, msg, len(msg))
+        else:
+            rc = self._lib.tcamd_host_jpeg_decode_scaled(blob, len(blob), scale, out.ctypes.data, out.size, msg,
+                                                         len(msg))
+        self._jpeg_check(rc, msg)
         return out
 
     # -- the stream buffer of K23 jpeg_huffman (csrc/kernels/jpeg_huff_core.h) ----------

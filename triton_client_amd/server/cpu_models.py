@@ -236,7 +236,12 @@ class PreprocessInception(Model):
     ``utils.image.decode_image``) and
     produce INCEPTION-scaled FP32 NCHW [3,224,224].  The custom request
     parameter ``antialias`` (bool, default false) resizes with
-    ``utils.image.resize_area`` instead of ``resize_bilinear``."""
+    ``utils.image.resize_area`` instead of ``resize_bilinear``.  The custom
+    request parameter ``jpeg_scale`` (int64: 1, 2, 4 or 8, or 0 for
+    ``utils.image.jpeg_auto_scale`` against 224 x 224; default: full size)
+    decodes the request's JPEG blobs at that fraction of their size in the DCT
+    domain before the resize; the other encodings ignore it, and any other
+    value fails the request."""
 
     name = "preprocess_inception"
     max_batch_size = 8
@@ -247,16 +252,43 @@ class PreprocessInception(Model):
     def wants_antialias(request):
         return bool(request.parameters.get("antialias", False))
 
+    @staticmethod
+    def jpeg_scale_of(request):
+        """The request's ``jpeg_scale``: 0 (automatic), 1, 2, 4 or 8; 1 without the parameter."""
+        from triton_client_amd.utils.image import check_jpeg_scale
+
+        if "jpeg_scale" not in request.parameters:
+            return 1
+        try:
+            return check_jpeg_scale(request.parameters["jpeg_scale"])
+        except ValueError as e:
+            raise ValueError("request parameter %s" % e) from None
+
+    @staticmethod
+    def resolve_jpeg_scale(codec, blob, scale, h, w):
+        """``scale``, or for 0 the automatic scale of this JPEG blob for an ``h x w`` target."""
+        from triton_client_amd.utils.image import jpeg_auto_scale
+
+        if scale:
+            return scale
+        full = codec.jpeg_parse(blob)
+        return jpeg_auto_scale(full.h, full.w, h, w)
+
     def execute(self, requests):
-        from triton_client_amd.utils.image import decode_image, inception_preprocess
+        from triton_client_amd.utils.image import JPEG_SOI, _jpeg_codec, decode_image, inception_preprocess
 
         res = []
         for r in requests:
             blobs = r.input("INPUT").numpy().reshape(-1)
             aa = self.wants_antialias(r)
+            scale = self.jpeg_scale_of(r)
             outs = []
             for b in blobs:
-                img = decode_image(b)
+                if scale != 1 and bytes(b[:2]) == JPEG_SOI:
+                    b = bytes(b)
+                    img = decode_image(b, self.resolve_jpeg_scale(_jpeg_codec(), b, scale, 224, 224))
+                else:
+                    img = decode_image(b)
                 outs.append(inception_preprocess(img, 224, 224, "NCHW", antialias=aa))
             res.append([self.out("OUTPUT", np.stack(outs).astype(np.float32))])
         return res

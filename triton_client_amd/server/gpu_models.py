@@ -520,7 +520,21 @@ class PreprocessInception(Model):
     the antialiased resize for that request's images: the batch's device jobs
     are split by the flag into at most one K20 and one K21 ``resize_pack``
     call, both on the slot's stream, and the host fallbacks use
-    ``utils.image.resize_area``."""
+    ``utils.image.resize_area``.
+
+    The custom request parameter ``jpeg_scale`` (int64: 1, 2, 4 or 8, or 0 for
+    ``utils.image.jpeg_auto_scale`` against the model's H x W; without it a
+    request is served at full size, as before) decodes that request's JPEG
+    blobs at 1/2, 1/4 or 1/8 size in the DCT domain: the host's entropy
+    decoder stores only the coefficients the reduced transform uses, the
+    staging-area fit test counts the compact coefficient buffer and the reduced
+    pixels (a 12-megapixel 4:2:0 photo needs about 1.7 MB at 1/8 instead of
+    72 MB), and K22 decodes the images of all scales of a batch in the same
+    ``jpeg_decode`` call.  A JPEG at a scale other than 1 always takes the
+    host's entropy decoder, whatever ``TCAMD_DEVICE_HUFFMAN`` says: K23 writes
+    the full layout.  The host fallbacks decode at the same scale, so every
+    route gives the same rows.  PPM / PGM / TCIMG blobs ignore the parameter;
+    any other value fails that request alone."""
 
     name = "preprocess_inception"
     max_batch_size = 8
@@ -600,13 +614,16 @@ class PreprocessInception(Model):
         except Exception as e:  # noqa: BLE001 - per-request failure, the CPU model's own error
             return e
 
-    def _open(self, blob):
-        """A decoded image, or (blob, parse) of a JPEG whose decode is still to be routed."""
+    def _open(self, blob, scale=1):
+        """A decoded image, or (blob, parse) of a JPEG whose decode is still to be routed;
+        ``scale`` is the request's ``jpeg_scale``, 0 for automatic."""
         from triton_client_amd.utils.image import decode_image
 
         blob = bytes(blob)
         if blob[:2] == b"\xff\xd8":
-            return blob, self._codec.jpeg_parse(blob)
+            if scale != 1:
+                scale = self._host.resolve_jpeg_scale(self._codec, blob, scale, self.H, self.W)
+            return blob, self._codec.jpeg_parse(blob, scale)
         return decode_image(blob)
 
     def _read_status(self, status):
@@ -642,10 +659,11 @@ class PreprocessInception(Model):
                     len(huff_jobs))
             try:
                 aa = self._host.wants_antialias(r)
-                for item in [self._open(b) for b in r.input("INPUT").numpy().reshape(-1)]:
+                scale = self._host.jpeg_scale_of(r)
+                for item in [self._open(b, scale) for b in r.input("INPUT").numpy().reshape(-1)]:
                     if isinstance(item, tuple):
                         blob, info = item
-                        if self.device_huffman:
+                        if self.device_huffman and info.scale == 1:
                             # the stream at the bottom; coefficients and pixels, device only, at the top
                             at = -(-used // 16) * 16
                             coef = (top - info.pixel_bytes - info.coef_bytes) // 128 * 128
@@ -661,14 +679,14 @@ class PreprocessInception(Model):
                                 continue
                         coef = -(-used // 128) * 128
                         if coef + info.coef_bytes + info.pixel_bytes <= top:
-                            self._codec.jpeg_entropy_decode(blob, stage[coef:coef + info.coef_bytes])
+                            self._codec.jpeg_entropy_decode(blob, stage[coef:coef + info.coef_bytes], info.scale)
                             used = coef + info.coef_bytes
                             top -= info.pixel_bytes
                             jpeg_jobs.append((coef, info, top))
                             dev_jobs[aa].append((rows, info.shape, top))
                             rows += 1
                             continue
-                        item = self._codec.jpeg_decode(blob)
+                        item = self._codec.jpeg_decode(blob, info.scale)
                     h, w, c = item.shape
                     if 1 <= h <= hip.RESIZE_MAX_DIM and 1 <= w <= hip.RESIZE_MAX_DIM and c in (1, 3) \
                             and used + item.size <= top:

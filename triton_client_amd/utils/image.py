@@ -39,13 +39,54 @@ def _jpeg_codec():
         raise ValueError("JPEG decoding needs libtcamd_host.so, which is not built (run make): %s" % e) from e
 
 
-def decode_image(blob):
+JPEG_SCALES = (1, 2, 4, 8)
+
+
+def jpeg_auto_scale(H, W, h_out, w_out):
+    """The largest reduced-size JPEG decode that a resize to ``h_out x w_out``
+    does not have to upscale: the largest ``s`` in {1, 2, 4, 8} with
+    ``H >= s * h_out`` and ``W >= s * w_out``, so that the ``ceil(H / s) x
+    ceil(W / s)`` decode has ``h_out x w_out`` whole samples (the last row and
+    column of a size that ``s`` does not divide cover fewer source pixels and
+    do not count: 447 -> 1, 448 -> 2 for a 224 target); 1 for an image that is
+    already smaller than the target on an axis."""
+    for s in (8, 4, 2):
+        if int(H) >= s * h_out and int(W) >= s * w_out:
+            return s
+    return 1
+
+
+def check_jpeg_scale(value, auto=True):
+    """``value`` as a JPEG scale: 1, 2, 4 or 8, or (with ``auto``) 0 for
+    :func:`jpeg_auto_scale`; anything else raises ``ValueError``."""
+    allowed = ((0,) if auto else ()) + JPEG_SCALES
+    if isinstance(value, bool) or not isinstance(value, (int, np.integer)) or int(value) not in allowed:
+        raise ValueError("jpeg_scale must be one of %s, not %r" % (", ".join(str(a) for a in allowed), value))
+    return int(value)
+
+
+def _jpeg_parse_scaled(blob, jpeg_scale, h_out, w_out):
+    """The parse of a JPEG blob at ``jpeg_scale``; 0 picks the scale for the target."""
+    codec = _jpeg_codec()
+    if jpeg_scale == 1:
+        return codec.jpeg_parse(blob)
+    if jpeg_scale == 0:
+        full = codec.jpeg_parse(blob)
+        jpeg_scale = jpeg_auto_scale(full.h, full.w, h_out, w_out)
+        if jpeg_scale == 1:
+            return full
+    return codec.jpeg_parse(blob, jpeg_scale)
+
+
+def decode_image(blob, jpeg_scale=1):
     """PPM / PGM / TCIMG / baseline JPEG blob -> uint8 [H, W, C].  A JPEG the
     decoder does not cover raises ``ValueError("unsupported JPEG: ...")``, a
-    broken one ``ValueError("malformed JPEG: ...")``."""
+    broken one ``ValueError("malformed JPEG: ...")``.  ``jpeg_scale`` 2, 4 or 8
+    decodes a JPEG in the DCT domain at that fraction of its size,
+    ``ceil(H / s) x ceil(W / s)``; the other encodings ignore it."""
     blob = bytes(blob)
     if blob[:2] == JPEG_SOI:
-        return _jpeg_codec().jpeg_decode(blob)
+        return _jpeg_codec().jpeg_decode(blob, check_jpeg_scale(jpeg_scale, auto=False))
     if blob[:5] == b"TCIMG":
         h, w, c = struct.unpack_from("<HHB", blob, 5)
         return np.frombuffer(blob, dtype=np.uint8, offset=10, count=h * w * c).reshape(h, w, c)
@@ -223,7 +264,7 @@ def preprocess_batch_device(resized, scaling="INCEPTION", fmt="NCHW", dtype="FP3
 
 
 def preprocess_raw_batch_device(images, c, h, w, scaling="INCEPTION", fmt="NCHW", dtype="FP32", device=0,
-                                antialias=False, device_huffman=None):
+                                antialias=False, device_huffman=None, jpeg_scale=1):
     """``preprocess`` of a batch of decoded uint8 HWC images of any sizes on
     the GPU: the raw pixels go up in ONE uint8 host->device copy (a quarter of
     the bytes of the resized fp32 images, and no host resize), K20
@@ -239,19 +280,24 @@ def preprocess_raw_batch_device(images, c, h, w, scaling="INCEPTION", fmt="NCHW"
     ``jpeg_huffman`` decodes it on the device; a blob the pack declines takes
     the host's entropy decoder, and if K23 leaves a non-zero status word the
     whole batch is done again with the host's entropy decoder, which gives the
-    answer or raises the error.  Returns None when the datatype has no device
-    path (integer models)."""
+    answer or raises the error.  ``jpeg_scale`` 2, 4 or 8 decodes the JPEGs at
+    that fraction of their size (the host stores, and the upload carries, only
+    the coefficients the reduced transform uses), 0 picks
+    :func:`jpeg_auto_scale` per JPEG for the ``h x w`` target; a JPEG decoded
+    at a reduced size always takes the host's entropy decoder.  Returns None
+    when the datatype has no device path (integer models)."""
     if dtype not in _DEVICE_DTYPES:
         return None
     import torch
 
     from triton_client_amd.ops import hip
 
+    jpeg_scale = check_jpeg_scale(jpeg_scale)
     items = []  # a uint8 HWC array, or (blob, parse) of a JPEG
     for im in images:
         if isinstance(im, (bytes, bytearray, memoryview)):
             blob = bytes(im)
-            items.append((blob, _jpeg_codec().jpeg_parse(blob)))
+            items.append((blob, _jpeg_parse_scaled(blob, jpeg_scale, h, w)))
             continue
         im = np.ascontiguousarray(im, dtype=np.uint8)
         items.append(im[:, :, None] if im.ndim == 2 else im)
@@ -268,7 +314,7 @@ def preprocess_raw_batch_device(images, c, h, w, scaling="INCEPTION", fmt="NCHW"
     offs, shapes, up, pix = [], [], 0, 0
     packed = {}  # item index -> its stream buffer
     for k, im in enumerate(items):
-        if isinstance(im, tuple) and device_huffman:
+        if isinstance(im, tuple) and device_huffman and im[1].scale == 1:
             buf = host_codec.aligned_buffer(_jpeg_codec().jpeg_stream_bound(len(im[0])))
             n = _jpeg_codec().jpeg_stream_pack(im[0], buf)[1]
             if n is not None:
@@ -294,7 +340,7 @@ def preprocess_raw_batch_device(images, c, h, w, scaling="INCEPTION", fmt="NCHW"
         if k in packed:
             raw[o:o + packed[k].size] = packed[k]
         elif isinstance(im, tuple):
-            _jpeg_codec().jpeg_entropy_decode(im[0], raw[o:o + im[1].coef_bytes])
+            _jpeg_codec().jpeg_entropy_decode(im[0], raw[o:o + im[1].coef_bytes], im[1].scale)
         else:
             raw[o:o + im.size] = im.reshape(-1)
     src = torch.from_numpy(raw).to(dev, non_blocking=False)
@@ -330,5 +376,5 @@ def preprocess_raw_batch_device(images, c, h, w, scaling="INCEPTION", fmt="NCHW"
     out = dst.cpu().numpy()
     if status is not None and status.cpu().numpy().any():
         return preprocess_raw_batch_device(images, c, h, w, scaling, fmt, dtype, device, antialias,
-                                           device_huffman=False)
+                                           device_huffman=False, jpeg_scale=jpeg_scale)
     return out

@@ -1909,6 +1909,9 @@ __global__ void __launch_bounds__(768, 1) x3_dense_ws_kernel(X3FusedParams p) {
 // HBM per layer: the input X once (+ the halo rows through L2) and 32 output
 // channels; one launch.  LDS: 4 K-step stages (128 KB); z and the 3x3
 // scratch alias them once the 1x1 drained.
+// Half 14x14 images also have a PAIR kernel (x3_dense_small_pair_kernel,
+// below the single-layer one): layers j and j+1 in one launch, which reads
+// X[0:K) once for both.
 
 struct X3SmallParams {
   const float* x;  // block buffer rows of ldx (the layer's first K channels)
@@ -2239,6 +2242,444 @@ __device__ __forceinline__ void x3_small_body(const X3SmallParams& p) {
 template <int W, int T>
 __global__ void __launch_bounds__(512, 1) x3_dense_small_kernel(X3SmallParams p) {
   x3_small_body<W, T>(p);
+}
+
+// ----------------------------------------------------------------------------
+// K14x pair: layers j and j+1 of a block in one launch, on ONE read of X[0:K)
+// ----------------------------------------------------------------------------
+// Layer j+1 reads the channels layer j read plus layer j's 32 outputs, so two
+// single launches stream the block input from HBM twice.  Here a workgroup
+// owns the same row tile as K14x and runs both layers:
+//
+//   K loop (K/32 steps, X[0:K) only): waves 0-3 (group A) own layer j's
+//   MFMAs, waves 4-7 (group B) layer j+1's, one of each per SIMD; a wave is a
+//   32-channel quarter over every 32-pixel block, holds its W1 fragments two
+//   steps ahead and reads B from its layer's two planes of the stage.  The
+//   rows of an X step are dealt over all 512 threads; a thread keeps PF steps
+//   of its rows in registers and converts each TWICE, with layer j's and
+//   layer j+1's BN1 + ReLU, split hi/lo, into the four planes of the other
+//   stage, a piece of 6-8 vector instructions after every second MFMA.
+//   (Each group loading and converting X for itself, the first version, put X
+//   through the CU's vector-memory path twice a step and measured 7-12 %
+//   slower per pair.)  HBM and the CU see X once.  One raw s_barrier a step,
+//   the same count in every wave.
+//   Then: group A's epilogue writes z_j (tile rows +-2, clamped; <= 128
+//   pixels) into a padded image; all 8 waves run layer j's 3x3 over the tile
+//   rows +-1; the owner lanes store y_j for the tile's OWN rows only (the
+//   sibling tile recomputes the shared rows, as it recomputes the halo of z
+//   today) and write BN1_{j+1}(y_j), split, as one more K-step stage; group B,
+//   its partial sums still in registers, runs that step against W1_{j+1}'s
+//   last 32 k, writes z_{j+1}; all 8 waves run layer j+1's 3x3.
+//   No workgroup ever waits for another: no flags, no atomics.
+//
+// LDS (144 KB): [0, 64 KB) two K-step stages (A hi|lo, B hi|lo planes),
+// [64, 96 KB) the two BN1 tables; after the loop the padded z image (80 KB)
+// and the 3x3 scratch (42 KB) alias both; [128, 144 KB) the y_j stage.
+struct X3PairLayer {
+  const float* s1;  // as X3SmallParams, one per layer; layer j+1's tables have K + 32 entries
+  const float* t1;
+  const uint16_t* w1f_hi;
+  const uint16_t* w1f_lo;
+  const float* b1;
+  const uint16_t* w2_hi;
+  const uint16_t* w2_lo;
+};
+
+struct X3PairParams {
+  const float* x;
+  X3PairLayer a, b;  // layers j, j+1
+  float* y;          // layer j's 32-channel slice; layer j+1's is y + 32
+  int ldx, K, ldy, imgs;
+};
+
+// most rows of [r0 - halo, r1 + halo) clamped to the image, over a W x W image's T tiles
+constexpr int x3s_rows_max(int W, int T, int halo) {
+  int m = 0;
+  for (int t = 0; t < T; ++t) {
+    const int r0 = t * W / T, r1 = (t + 1) * W / T;
+    const int z0 = r0 > halo ? r0 - halo : 0, z1 = r1 + halo < W ? r1 + halo : W;
+    m = z1 - z0 > m ? z1 - z0 : m;
+  }
+  return m;
+}
+
+constexpr int x3s_rows_min(int W, int T, int halo) {
+  int m = W;
+  for (int t = 0; t < T; ++t) {
+    const int r0 = t * W / T, r1 = (t + 1) * W / T;
+    const int z0 = r0 > halo ? r0 - halo : 0, z1 = r1 + halo < W ? r1 + halo : W;
+    m = z1 - z0 < m ? z1 - z0 : m;
+  }
+  return m;
+}
+
+constexpr int kPairStages = 2 * kWsStage;             // 64 KB
+constexpr int kPairBn = kPairStages;                  // 2 x 16 KB BN1 tables (K <= 2016)
+constexpr int kPairYStage = 4 * kWsStage;             // 16 KB: BN1_{j+1}(y_j) hi | lo
+constexpr int kLdsPair = kPairYStage + 2 * kWsPlane;  // 144 KB
+
+template <int W, int T>
+__device__ __forceinline__ void x3_small_pair_body(const X3PairParams& p) {
+  constexpr int PF = 3;
+  constexpr int kPW = W + 2;
+  constexpr int kRowsA = x3s_rows_max(W, T, 1);   // most y_j rows = z_{j+1} rows of a tile
+  constexpr int kZRowsA = x3s_rows_max(W, T, 2);  // most z_j rows
+  constexpr int kNPad = (kRowsA + 2) * kPW;       // padded z_j image (z_{j+1}'s is smaller)
+  constexpr int kNPG = (kRowsA * W + 15) / 16;    // 16-pixel groups of either 3x3
+  constexpr int kTRMax = kZRowsA * W;
+  constexpr int kNB = (kTRMax + 31) / 32;
+  constexpr int kNRI = kNB / 2;  // X row passes of the 512 threads (64 rows each)
+  static_assert(kTRMax <= 128, "the layer-j z tile is one 1x1 tile");
+  static_assert(kNPad * kRowB + 2 * 4 * 3 * kNPG * 64 * 4 <= kPairYStage, "K14x pair LDS budget");
+  extern __shared__ __attribute__((aligned(16))) uint8_t ldss[];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int grp = wave >> 2, wq = wave & 3;  // layer (0: j, 1: j+1), 32-channel quarter
+
+  const int g8 = blockIdx.x / (8 * T), rr = blockIdx.x % (8 * T);
+  const int tile = rr >> 3, img = 8 * g8 + (rr & 7);
+  if (img >= p.imgs) return;  // block-uniform, before any barrier
+  const int r0 = tile * W / T, r1 = (tile + 1) * W / T;  // the tile's own rows
+  const int b0r = max(r0 - 1, 0), b1r = min(r1 + 1, W);  // y_j rows = z_{j+1} rows
+  const int a0r = max(b0r - 1, 0), a1r = min(b1r + 1, W);  // z_j rows = the X rows of the K loop
+  const int TR = (a1r - a0r) * W;
+  const int mz0 = img * W * W + a0r * W;
+  const int shift = (b0r - a0r) * W;  // y_j pixel o is pixel o + shift of the 1x1 tile
+  const int K = p.K, nst = K / kBK, Q = nst;
+  const X3PairLayer& L = grp ? p.b : p.a;
+  const int col = lane & 31, h = lane >> 5;
+  const int rot = (int)(blockIdx.x % (unsigned)nst);  // one rotation for both groups
+  auto kofs = [&](int ks) { ks += rot; return (ks >= nst ? ks - nst : ks) * kBK; };
+  float* const bnl = reinterpret_cast<float*>(ldss + kPairBn + grp * 2 * kWsPlane);
+  uint8_t* const gst = ldss + grp * 2 * kWsPlane;  // this group's hi plane of stage 0
+
+  f32x16 acc[kNB];
+#pragma unroll
+  for (int b = 0; b < kNB; ++b)
+#pragma unroll
+    for (int e = 0; e < 16; ++e) acc[b][e] = 0.f;
+  struct AOps {
+    v4u h[2], l[2];
+  };
+  {
+    // the X rows are dealt over all 512 threads and each thread converts its
+    // rows for BOTH layers (the two differ in their BN1 affine only): a CU's
+    // vector-memory path carries X once and every wave has the same vector work
+    const int pj = tid & 7, prow = tid >> 3;
+    f32x4 xr[PF][kNRI];
+    auto issue_x = [&](int q, int slot) {
+      const int k0 = kofs(min(q, Q - 1));
+#pragma unroll
+      for (int i = 0; i < kNRI; ++i) {
+        const int m = mz0 + min(prow + 64 * i, TR - 1);
+        xr[slot][i] = ldf4(p.x + (size_t)m * p.ldx + k0 + 4 * pj);
+      }
+    };
+    const int wk = grp ? K + kBK : K;  // layer j+1's W1 has 32 more k
+    const auto w1h = __builtin_amdgcn_make_buffer_rsrc((void*)L.w1f_hi, (short)0, wk * 256, 0x00020000);
+    const auto w1l = __builtin_amdgcn_make_buffer_rsrc((void*)L.w1f_lo, (short)0, wk * 256, 0x00020000);
+    const int vo = (wq * 64 + lane) * 16;
+    auto ld_a = [&](int q, AOps& o) {
+      const int k16 = kofs(min(q, Q - 1)) / 16;
+#pragma unroll
+      for (int kk = 0; kk < 2; ++kk) {
+        o.h[kk] = __builtin_amdgcn_raw_buffer_load_b128(w1h, vo, (k16 + kk) * 4096, 0);
+        o.l[kk] = __builtin_amdgcn_raw_buffer_load_b128(w1l, vo, (k16 + kk) * 4096, 0);
+      }
+    };
+    // this thread's 8 bytes of row prow (+ 64 i: the same swizzle) in a hi plane
+    const int woff = ws_chunk(prow, pj >> 1) + (pj & 1) * 8;
+    // vector-memory order: X0 A0 A1 X1 X2 | X3 | A2 X4 | A3 X5 | ...  (X: kNRI
+    // ops, A: 4): W1 two steps ahead, so the wait for A(q) leaves X(q+2) and
+    // X(q+3) in flight
+    AOps fa[3];
+    issue_x(0, 0);
+    ld_a(0, fa[0]);
+    ld_a(1, fa[1]);
+#pragma unroll
+    for (int s = 1; s < PF; ++s) issue_x(s, s);
+    // this group's BN1 table (its first K entries)
+    for (int i = tid & 255; i < K / 4; i += 256) {
+      *reinterpret_cast<f32x4*>(bnl + 4 * i) = ldf4(L.s1 + 4 * i);
+      *reinterpret_cast<f32x4*>(bnl + K + 4 * i) = ldf4(L.t1 + 4 * i);
+    }
+    {
+      // step 0's X with the BN1 entries from global memory (the tables are not published yet)
+      const int k0 = kofs(0) + 4 * pj;
+#pragma unroll
+      for (int l = 0; l < 2; ++l) {
+        const X3PairLayer& ly = l ? p.b : p.a;
+        const f32x4 sc = ldf4(ly.s1 + k0), sb = ldf4(ly.t1 + k0);
+        uint8_t* wst = ldss + l * 2 * kWsPlane + woff;
+#pragma unroll
+        for (int i = 0; i < kNRI; ++i) {
+          v2u hh, ll;
+          split4(bn_relu4(xr[0][i], sc, sb), hh, ll);
+          *reinterpret_cast<v2u*>(wst + 64 * i * 64) = hh;
+          *reinterpret_cast<v2u*>(wst + kWsPlane + 64 * i * 64) = ll;
+        }
+      }
+      __builtin_amdgcn_sched_barrier(0);
+      issue_x(PF, 0);
+    }
+    __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0): stage 0 and the tables are in LDS
+    ws_barrier();  // B0
+    // Step q: the 6 * kNB MFMAs of step q (B from stage q, a (kk, pixel block)
+    // group at a time, read two groups ahead) and the conversion of X(q+1)
+    // into the other stage, for both layers, cut into 6 * kNRI pieces of 6-8
+    // vector instructions, one after every second MFMA, each fenced in place,
+    // so a wave's vector work runs under the SIMD's matrix work (with the
+    // conversion ahead of the MFMAs a step took twice as long).  The
+    // vector-memory waits are the compiler's.
+    constexpr bool kAllB = 32 * (kNB - 1) < x3s_rows_min(W, T, 2) * W;  // no tile leaves a pixel block empty
+    static_assert(2 * kNRI == kNB, "one conversion piece per two MFMAs");
+    const float* const bn0 = reinterpret_cast<const float*>(ldss + kPairBn);
+    auto step = [&](int q, int slot, const AOps& A, AOps& nxt2) {
+      ld_a(q + 2, nxt2);
+      const uint8_t* rs = gst + (q & 1) * kWsStage;
+      uint8_t* wst = ldss + ((q + 1) & 1) * kWsStage + woff;
+      f32x4 sc[2], sb[2];
+      {
+        const int k0 = kofs(min(q + 1, Q - 1)) + 4 * pj;
+#pragma unroll
+        for (int l = 0; l < 2; ++l) {
+          sc[l] = *reinterpret_cast<const f32x4*>(bn0 + l * (2 * kWsPlane / 4) + k0);
+          sb[l] = *reinterpret_cast<const f32x4*>(bn0 + l * (2 * kWsPlane / 4) + K + k0);
+        }
+      }
+      if (q < Q) {  // block-uniform
+      v4u bh[2 * kNB], bl[2 * kNB];
+      auto rd_b = [&](int g) {
+        const int xo = ws_chunk(32 * (g % kNB) + col, 2 * (g / kNB) + h);
+        bh[g] = ld16(rs + xo);
+        bl[g] = ld16(rs + kWsPlane + xo);
+      };
+      rd_b(0);
+      rd_b(1);
+      __builtin_amdgcn_sched_barrier(0);
+      f32x4 v;
+      uint32_t h0, l0, h1, l1;
+#pragma unroll
+      for (int m = 0; m < 6 * kNB; ++m) {
+        const int g = m / 3, j = m % 3, kk = g / kNB, b = g % kNB;
+        if (j == 0 && g + 2 < 2 * kNB) rd_b(g + 2);
+        if (kAllB || 32 * b < TR)
+          acc[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fr(j == 0 ? A.l[kk] : A.h[kk]),
+                                                           fr(j == 1 ? bl[g] : bh[g]), acc[b], 0, 0, 0);
+        __builtin_amdgcn_sched_barrier(0);
+        if (m & 1) {
+          // rows >= TR hold row TR-1's data: their columns are never used
+          const int pc = m >> 1, i = pc / 6, l = (pc / 3) % 2, part = pc % 3;
+          if (part == 0) {
+            v = bn_relu4(xr[slot][i], sc[l], sb[l]);
+          } else if (part == 1) {
+            split2(v[0], v[1], h0, l0);
+          } else {
+            split2(v[2], v[3], h1, l1);
+            *reinterpret_cast<v2u*>(wst + l * 2 * kWsPlane + 64 * i * 64) = v2u{h0, h1};
+            *reinterpret_cast<v2u*>(wst + (l * 2 + 1) * kWsPlane + 64 * i * 64) = v2u{l0, l1};
+          }
+          __builtin_amdgcn_sched_barrier(0);
+        }
+      }
+      }
+      __builtin_amdgcn_sched_barrier(0);
+      issue_x(q + 1 + PF, slot);
+      __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0): the stage writes
+      ws_barrier();                        // B(q+1)
+    };
+    // Whole rounds of PF steps with no way out of a round; the steps past Q
+    // (at most PF-1) keep their loads and their barrier and skip the work, so
+    // every wave runs the same barrier rounds.  (A break out of the unrolled
+    // round put a path from the middle of a round to the loop head, and the
+    // compiler's vector-memory waits at the head then assumed the X slot
+    // issued last and drained the prefetch every third step; a tail of
+    // leftover steps behind the loop spilled registers.)
+    for (int q0 = 0; q0 < Q; q0 += PF) {
+#pragma unroll
+      for (int u = 0; u < PF; ++u) step(q0 + u, (u + 1) % PF, fa[u], fa[(u + 2) % PF]);
+    }
+  }
+  // after B(Q): every stage read and write has retired, the LDS changes hands
+
+  const int kq = wave & 3, oh = wave >> 2;  // 3x3 roles: input-channel quarter x output half
+  const int c4 = lane >> 4;
+  constexpr int kSlot = kNPG * 64;
+  float* const scr = reinterpret_cast<float*>(ldss + kNPad * kRowB);
+  // padded image of the z rows [z0, z1) around the output rows from `top`:
+  // padded row pr is image row top - 1 + pr
+  auto zero_pad = [&](int top, int nrows, int z0, int z1) {
+    for (int i = tid; i < (nrows + 2) * kPW * 32; i += 512) {
+      const int pos = i >> 5, piece = i & 31;
+      const int prr = pos / kPW, pc = pos - prr * kPW;
+      const int ir = top - 1 + prr;
+      if (pc == 0 || pc == kPW - 1 || ir < z0 || ir >= z1)
+        *reinterpret_cast<v4u*>(ldss + pos * kRowB + piece * 16) = v4u{0, 0, 0, 0};
+    }
+  };
+  // 1x1 epilogue of this wave's quarter: + bias, ReLU, split, into the padded
+  // image; pixel pz of the 1x1 tile is image row a0r + pz / W
+  auto write_z = [&](const X3PairLayer& ly, int top, int z0, int z1) {
+    f32x4 ob[4];
+#pragma unroll
+    for (int g = 0; g < 4; ++g) ob[g] = ldf4(ly.b1 + 32 * wq + 8 * g + 4 * h);
+#pragma unroll
+    for (int b = 0; b < kNB; ++b) {
+      const int pz = 32 * b + col;
+      const int zy = pz / W, zx = pz - zy * W;
+      const int ir = a0r + zy;
+      if (pz < TR && ir >= z0 && ir < z1) {
+        const int pos = (ir - top + 1) * kPW + zx + 1;
+        uint8_t* rp = ldss + pos * kRowB + 8 * h;
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+          f32x4 r;
+#pragma unroll
+          for (int e = 0; e < 4; ++e) r[e] = fmaxf(acc[b][4 * g + e] + ob[g][e], 0.f);
+          v2u hh, ll;
+          split4(r, hh, ll);
+          uint8_t* q = rp + ((((4 * wq) + g) ^ (pos & 15)) << 4);
+          *reinterpret_cast<v2u*>(q) = hh;
+          *reinterpret_cast<v2u*>(q + 256) = ll;
+        }
+      }
+    }
+  };
+  // 3x3 over nout outputs of the padded image (output o at padded (o / W + 1,
+  // o % W + 1)); on return the owner lanes (c4 == kq) hold their 4 channels'
+  // sums in acc3 and the other three waves' partials are in the scratch
+  // (the 3x3 weights are fetched ahead of the phase that builds the image)
+  v4u w2h[kTaps], w2l[kTaps];
+  auto ld_w2 = [&](const X3PairLayer& ly) {
+#pragma unroll
+    for (int t = 0; t < kTaps; ++t) {
+      const size_t off = ((size_t)((t * 4 + kq) * 2 + oh) * 64 + lane) * 8;
+      w2h[t] = ld16(ly.w2_hi + off);
+      w2l[t] = ld16(ly.w2_lo + off);
+    }
+  };
+  auto conv3 = [&](int nout, f32x4 (&acc3)[kNPG]) {
+    int base[kNPG];
+#pragma unroll
+    for (int pg = 0; pg < kNPG; ++pg) {
+      const int o = 16 * pg + (lane & 15);
+      const int yy = o / W, xx = o - (o / W) * W;
+      base[pg] = o < nout ? yy * kPW + xx : 0;
+      acc3[pg] = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+    __syncthreads();  // z and its padding complete
+    const int chunk16 = 4 * kq + c4;
+    constexpr int kSteps = kTaps * kNPG;
+    constexpr int kLead = 3;
+    v4u bq[kLead + 1][2];
+    auto rd = [&](int step) {
+      const int t = step / kNPG, pg = step - (step / kNPG) * kNPG;
+      const int pos = base[pg] + (t / 3) * kPW + (t % 3);
+      const uint8_t* q = ldss + pos * kRowB + (((chunk16 ^ (pos & 15))) << 4);
+      bq[step % (kLead + 1)][0] = ld16(q);
+      bq[step % (kLead + 1)][1] = ld16(q + 256);
+    };
+#pragma unroll
+    for (int step = 0; step < kLead; ++step) rd(step);
+#pragma unroll
+    for (int step = 0; step < kSteps; ++step) {
+      if (step + kLead < kSteps) rd(step + kLead);
+      __builtin_amdgcn_sched_barrier(0);
+      const int t = step / kNPG, pg = step - (step / kNPG) * kNPG;
+      acc3[pg] = x3_16(w2h[t], w2l[t], bq[step % (kLead + 1)][0], bq[step % (kLead + 1)][1], acc3[pg]);
+    }
+    if (c4 != kq) {
+      float* sw = scr + ((oh * 4 + c4) * 3 + (kq - c4 + 3) % 4) * kSlot + (lane & 15) * 4;
+#pragma unroll
+      for (int pg = 0; pg < kNPG; ++pg) *reinterpret_cast<f32x4*>(sw + pg * 64) = acc3[pg];
+    }
+  };
+  const float* const sr = scr + (oh * 4 + kq) * 3 * kSlot + (lane & 15) * 4;
+  f32x4 acc3[kNPG];
+
+  // ---- layer j: z_j, its 3x3 over the rows [b0r, b1r) ----
+  ld_w2(p.a);
+  zero_pad(b0r, b1r - b0r, a0r, a1r);
+  if (grp == 0) write_z(p.a, b0r, a0r, a1r);
+  conv3((b1r - b0r) * W, acc3);
+  ld_w2(p.b);
+  // group B's W1 fragments of the y_j step (k = K .. K+32) and the owners'
+  // BN1_{j+1} entries of their 4 channels land behind the exchange
+  AOps fy;
+  if (grp) {
+    const int vo = (wq * 64 + lane) * 16;
+#pragma unroll
+    for (int kk = 0; kk < 2; ++kk) {
+      fy.h[kk] = ld16(p.b.w1f_hi + (size_t)(K / 16 + kk) * 2048 + vo / 2);
+      fy.l[kk] = ld16(p.b.w1f_lo + (size_t)(K / 16 + kk) * 2048 + vo / 2);
+    }
+  }
+  const f32x4 ys = ldf4(p.b.s1 + K + 16 * oh + 4 * kq), yt = ldf4(p.b.t1 + K + 16 * oh + 4 * kq);
+  __syncthreads();  // partials in the scratch; every read of z_j retired
+  if (c4 == kq) {
+    const int nout = (b1r - b0r) * W;
+    const int m0 = img * W * W + b0r * W;
+    uint8_t* const yst = ldss + kPairYStage;
+#pragma unroll
+    for (int pg = 0; pg < kNPG; ++pg) {
+      f32x4 v = acc3[pg];
+#pragma unroll
+      for (int src = 0; src < 3; ++src) v += *reinterpret_cast<const f32x4*>(sr + src * kSlot + pg * 64);
+      const int o = 16 * pg + (lane & 15);
+      if (o < nout) {
+        const int ir = b0r + o / W;
+        // HBM gets the tile's own rows only; the rows shared with the sibling tile are its to store
+        if (ir >= r0 && ir < r1) *reinterpret_cast<f32x4*>(p.y + (size_t)(m0 + o) * p.ldy + 16 * oh + 4 * kq) = v;
+        v2u hh, ll;
+        split4(bn_relu4(v, ys, yt), hh, ll);
+        const int off = ws_chunk(o + shift, 2 * oh + (kq >> 1)) + (kq & 1) * 8;
+        *reinterpret_cast<v2u*>(yst + off) = hh;
+        *reinterpret_cast<v2u*>(yst + kWsPlane + off) = ll;
+      }
+    }
+  }
+  __syncthreads();  // the y_j stage complete; the scratch read
+
+  // ---- layer j+1: the y_j step, z_{j+1}, its 3x3 over the tile's rows ----
+  zero_pad(r0, r1 - r0, b0r, b1r);
+  if (grp) {
+    // (the 1x1 tile's rows outside [b0r, b1r) of the y_j stage were never
+    // written: they only reach accumulator columns that write_z skips)
+    const uint8_t* yst = ldss + kPairYStage;
+#pragma unroll
+    for (int kk = 0; kk < 2; ++kk) {
+      v4u bh[kNB], bl[kNB];
+#pragma unroll
+      for (int b = 0; b < kNB; ++b) {
+        const int xo = ws_chunk(32 * b + col, 2 * kk + h);
+        bh[b] = ld16(yst + xo);
+        bl[b] = ld16(yst + kWsPlane + xo);
+      }
+#pragma unroll
+      for (int b = 0; b < kNB; ++b)
+        if (32 * b < TR) acc[b] = x3_32(fy.h[kk], fy.l[kk], bh[b], bl[b], acc[b]);
+    }
+    write_z(p.b, r0, b0r, b1r);
+  }
+  conv3((r1 - r0) * W, acc3);
+  __syncthreads();
+  if (c4 == kq) {
+    const int nout = (r1 - r0) * W;
+    const int m0 = img * W * W + r0 * W;
+#pragma unroll
+    for (int pg = 0; pg < kNPG; ++pg) {
+      f32x4 v = acc3[pg];
+#pragma unroll
+      for (int src = 0; src < 3; ++src) v += *reinterpret_cast<const f32x4*>(sr + src * kSlot + pg * 64);
+      const int o = 16 * pg + (lane & 15);
+      if (o < nout) *reinterpret_cast<f32x4*>(p.y + (size_t)(m0 + o) * p.ldy + kBK + 16 * oh + 4 * kq) = v;
+    }
+  }
+}
+
+template <int W, int T>
+__global__ void __launch_bounds__(512, 1) x3_dense_small_pair_kernel(X3PairParams p) {
+  x3_small_pair_body<W, T>(p);
 }
 
 // ============================================================================
@@ -2934,6 +3375,57 @@ int tcamd_x3_dense_small(const float* x, int ldx, int imgs, int H, int W, int K,
   void* args[] = {&p};
   const hipError_t e = hipLaunchKernel(fns[W == 14 ? 0 : 1][ti], dim3(blocks), dim3(512), args, kLds,
                                        (hipStream_t)stream);
+  if (e != hipSuccess) return e;
+  return hipGetLastError();
+}
+
+// [W, tiles] the pair kernel is built for: half images at 14x14 (the other
+// K14x tilings were not measured to win as pairs and are not instantiated)
+int tcamd_x3_dense_small_pair_supported(int W, int tiles) { return W == 14 && tiles == 2; }
+
+// K14x pair: layers j and j+1 of a 14x14 block (cin = K and K + 32) in one
+// launch on one read of x[:, 0:K); `1` / `2` name the layers' parameters as in
+// tcamd_x3_dense_small (s1_2 / t1_2 / w1f_*2 cover K + 32 input channels);
+// y is layer j's 32-channel slice, layer j+1's follows it.  tiles as above
+// (<= 0: the chip-filling default); a (W, tiles) without a pair kernel is
+// hipErrorInvalidValue: the caller asks tcamd_x3_dense_small_pair_supported.
+int tcamd_x3_dense_small_pair(const float* x, int ldx, int imgs, int H, int W, int K, const float* s1_1,
+                              const float* t1_1, const void* w1f_hi1, const void* w1f_lo1, const float* b1_1,
+                              const void* w2_hi1, const void* w2_lo1, const float* s1_2, const float* t1_2,
+                              const void* w1f_hi2, const void* w1f_lo2, const float* b1_2, const void* w2_hi2,
+                              const void* w2_lo2, float* y, int ldy, int tiles, void* stream) {
+  if (imgs <= 0) return hipSuccess;
+  if ((W != 14 && W != 7) || H != W || K < 64 || K + 32 > 2048 || K % 32 || ldx < K + 64 || ldx % 4 || ldy % 4)
+    return hipErrorInvalidValue;
+  const void* const ptrs[] = {x,    s1_1, t1_1,    w1f_hi1, w1f_lo1, b1_1,   w2_hi1, w2_lo1,
+                              s1_2, t1_2, w1f_hi2, w1f_lo2, b1_2,    w2_hi2, w2_lo2, y};
+  for (const void* q : ptrs)
+    if (!q || !aligned16(q)) return hipErrorInvalidValue;
+  if ((size_t)imgs * H * W >= (1u << 30) / 4) return hipErrorInvalidValue;
+  if (tiles <= 0) tiles = tcamd_x3_small_tiles(imgs, W);
+  if (!tcamd_x3_dense_small_pair_supported(W, tiles)) return hipErrorInvalidValue;
+  X3PairParams p;
+  p.x = x;
+  p.a = {s1_1, t1_1, (const uint16_t*)w1f_hi1, (const uint16_t*)w1f_lo1, b1_1, (const uint16_t*)w2_hi1,
+         (const uint16_t*)w2_lo1};
+  p.b = {s1_2, t1_2, (const uint16_t*)w1f_hi2, (const uint16_t*)w1f_lo2, b1_2, (const uint16_t*)w2_hi2,
+         (const uint16_t*)w2_lo2};
+  p.y = y;
+  p.ldx = ldx;
+  p.K = K;
+  p.ldy = ldy;
+  p.imgs = imgs;
+  const void* const fn = (const void*)x3_dense_small_pair_kernel<14, 2>;
+  static std::atomic<bool> attr_set[kMaxDevices];
+  const int dev_slot = device_slot();
+  if (!attr_set[dev_slot].load(std::memory_order_acquire)) {
+    const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsPair);
+    if (e != hipSuccess) return e;
+    attr_set[dev_slot].store(true, std::memory_order_release);
+  }
+  const int blocks = (imgs + 7) / 8 * 8 * tiles;
+  void* args[] = {&p};
+  const hipError_t e = hipLaunchKernel(fn, dim3(blocks), dim3(512), args, kLdsPair, (hipStream_t)stream);
   if (e != hipSuccess) return e;
   return hipGetLastError();
 }

@@ -27,7 +27,11 @@ Network walk (same as :class:`densenet_fused.FusedDenseNet`, fp32 activations):
                         or (14x14 / 7x7 blocks from ~16-32 images): K14x, one
                         launch per layer over row tiles of the images (2-4
                         per image, halo rows recomputed), z in a zero-padded
-                        LDS image of the tile
+                        LDS image of the tile; on half 14x14 images (from 128
+                        images) the K14x pair kernel: layers j and j+1 in one
+                        launch on ONE read of the block input, y_j handed to
+                        layer j+1 through LDS (12 launches for block 3's 24
+                        layers)
    -> per transition:   K8x conv1x1 with BN+ReLU+2x2 avg-pool prologue
                         -> next block buffer ch[0 : C/2] (fp32)
    -> K10x head: relu(BN5(x)) global average -> [b,1024] fp32
@@ -58,6 +62,11 @@ def split_bf16(w):
     hi = w.to(torch.bfloat16)
     lo = (w - hi.float()).to(torch.bfloat16)
     return hi.contiguous(), lo.contiguous()
+
+
+def _k14x_ptrs(L):
+    """A layer's K14x arguments: s1, t1, w1 fragments hi / lo, b1, w2 fragments hi / lo."""
+    return tuple(L[k].data_ptr() for k in ("s1", "t1", "w1fh", "w1fl", "b1", "w2fh", "w2fl"))
 
 
 class FusedDenseNetFP32:
@@ -153,6 +162,10 @@ class FusedDenseNetFP32:
         # two streams, +3 %; 0 = the one-stream choice on every stream (A/B
         # runs; profiles/r7_k14x_whole.md)
         self.smallf_shared = int(os.environ.get("TCAMD_X3_SMALLF_SHARED", "1"))
+        # ... 1: the K14x pair kernel (layers j and j+1 in one launch, the
+        # block input read once) where it is built for the tiling; 0 = one
+        # launch per layer (A/B runs; profiles/r13_k14x_pair.md)
+        self.smallf_pair = int(os.environ.get("TCAMD_X3_SMALLF_PAIR", "1"))
         self._alloc(max_batch)
 
     def _alloc(self, n):
@@ -238,12 +251,24 @@ class FusedDenseNetFP32:
             fmax = self._fuse_max_k(M)
             small = 0 < M <= self.small_m and M <= self.zacc.shape[1]
             if self._small_fused(b, hw):
-                # K14x: the 14x14 / 7x7 blocks, one launch per layer, z on chip
-                for L in layers:
-                    hip.x3_dense_small(fp, ctot, b, hw, hw, L["cin"], L["s1"].data_ptr(), L["t1"].data_ptr(),
-                                       L["w1fh"].data_ptr(), L["w1fl"].data_ptr(), L["b1"].data_ptr(),
-                                       L["w2fh"].data_ptr(), L["w2fl"].data_ptr(), fp + 4 * L["cin"], ctot, stream=st,
-                                       tiles=self._small_tiles(b, hw))
+                # K14x: the 14x14 / 7x7 blocks, one launch per layer, z on chip;
+                tiles = self._small_tiles(b, hw)
+                # ... two layers per launch on one read of the block input
+                # where the pair kernel is built for this tiling (half 14x14
+                # images); a leftover layer runs alone
+                pair = self.smallf_pair and hip.x3_dense_small_pair_supported(hw, tiles)
+                j = 0
+                while j < len(layers):
+                    L = layers[j]
+                    if pair and j + 1 < len(layers):
+                        hip.x3_dense_small_pair(fp, ctot, b, hw, hw, L["cin"], _k14x_ptrs(L),
+                                                _k14x_ptrs(layers[j + 1]), fp + 4 * L["cin"], ctot, stream=st,
+                                                tiles=tiles)
+                        j += 2
+                        continue
+                    hip.x3_dense_small(fp, ctot, b, hw, hw, L["cin"], *_k14x_ptrs(L), fp + 4 * L["cin"], ctot,
+                                       stream=st, tiles=tiles)
+                    j += 1
                 self._transition(bi, fp, ctot, b, hw, ws, wsb, st)
                 continue
             ch = self.chain[bi]

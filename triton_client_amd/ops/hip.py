@@ -276,6 +276,11 @@ _SIGS = {
         ],
         ctypes.c_int,
     ),
+    "tcamd_x3_dense_small_pair": (
+        [ctypes.c_void_p] + [ctypes.c_int] * 5 + [ctypes.c_void_p] * 15 + [ctypes.c_int, ctypes.c_int, ctypes.c_void_p],
+        ctypes.c_int,
+    ),
+    "tcamd_x3_dense_small_pair_supported": ([ctypes.c_int, ctypes.c_int], ctypes.c_int),
     "tcamd_x3_small_tiles": ([ctypes.c_int, ctypes.c_int], ctypes.c_int),
     "tcamd_x3_small_tiles_shared": ([ctypes.c_int, ctypes.c_int, ctypes.c_int], ctypes.c_int),
     "tcamd_x3_dense_fused_ws": (
@@ -1013,6 +1018,22 @@ def x3_dense_small(x, ldx, imgs, H, W, K, s1, t1, w1f_hi, w1f_lo, b1, w2_hi, w2_
     x3_w3f_fragments; K a multiple of 32 in 64..2048."""
     _check(_load().tcamd_x3_dense_small(x, int(ldx), int(imgs), int(H), int(W), int(K), s1, t1, w1f_hi, w1f_lo, b1,
                                         w2_hi, w2_lo, y, int(ldy), int(tiles), _vp(stream)), "x3_dense_small")
+
+
+def x3_dense_small_pair(x, ldx, imgs, H, W, K, layer1, layer2, y, ldy, stream=None, tiles=0):
+    """K14x pair: dense layers j and j+1 of a 14x14 block (``K`` and ``K + 32``
+    input channels) in ONE kernel on one read of ``x[:, :K]``.  ``layer1`` /
+    ``layer2``: each layer's ``(s1, t1, w1f_hi, w1f_lo, b1, w2_hi, w2_lo)``
+    pointers as :func:`x3_dense_small` takes them.  ``y`` is layer j's 32-channel
+    slice; layer j+1's follows it (``ldx >= K + 64``).  Only the (W, tiles)
+    of :func:`x3_dense_small_pair_supported`; anything else is an error."""
+    _check(_load().tcamd_x3_dense_small_pair(x, int(ldx), int(imgs), int(H), int(W), int(K), *layer1, *layer2, y,
+                                             int(ldy), int(tiles), _vp(stream)), "x3_dense_small_pair")
+
+
+def x3_dense_small_pair_supported(W, tiles):
+    """Whether the K14x pair kernel is built for ``tiles`` row tiles of a ``W`` x ``W`` image."""
+    return bool(_load().tcamd_x3_dense_small_pair_supported(int(W), int(tiles)))
 
 
 def x3_small_tiles(imgs, W):

@@ -66,6 +66,10 @@ KNOBS = [
          "K14x whole 7x7 images when a batch fills its stream's share of the CUs (server instances >= 2); "
          "0 = the one-stream tiling on every stream",
          "tests/test_k14x_whole_gpu.py::test_engine_tiles_follow_the_shared_rule"),
+    Knob("TCAMD_X3_SMALLF_PAIR", "python", 1, "FP32DenseNet.smallf_pair",
+         "K14x pair kernel (two dense layers per launch, the block input read once) where it is built for the "
+         "tiling (half 14x14 images); 0 = one launch per layer",
+         "tests/test_x3_dense_pair_gpu.py::test_engine_pairs_the_14x14_block"),
     # ---- python: BERT ----
     Knob("TC_BERT_FUSED", "python", 1, "models/bert.py FUSED",
          "K11 / K12 fused kernels on the GPU; 0 = plain torch ops", "tests/test_bert_kernels_gpu.py::test_bert_fused_layers_match_torch_ops"),

@@ -31,7 +31,7 @@ $(HIPLIB): $(HIP_OBJS)
 	@mkdir -p $(dir $@)
 	$(HIPCC) -shared -fPIC --offload-arch=$(ARCH) -o $@ $^ -L$(ROCM)/lib -lamdhip64
 
-$(HOSTLIB): csrc/host/host_codec.cc csrc/host/jpeg.cc csrc/host/jpeg.h csrc/kernels/jpeg_math.h csrc/kernels/jpeg_huff_core.h
+$(HOSTLIB): csrc/host/host_codec.cc csrc/host/jpeg.cc csrc/host/jpeg.h csrc/kernels/jpeg_math.h csrc/kernels/jpeg_huff_core.h csrc/kernels/jpeg_huff_wide_core.h
 	@mkdir -p $(dir $@)
 	$(CXX) $(CXXFLAGS) -shared -o $@ csrc/host/host_codec.cc csrc/host/jpeg.cc
 

@@ -11,10 +11,12 @@
 
 #include <cstdio>
 #include <cstring>
+#include <memory>
 #include <new>
 #include <vector>
 
 #include "../kernels/jpeg_huff_core.h"
+#include "../kernels/jpeg_huff_wide_core.h"
 #include "../kernels/jpeg_math.h"
 
 namespace {
@@ -374,16 +376,24 @@ void entropy_decode(const uint8_t* d, size_t n, const Parsed& P, const TcamdJpeg
   }
 }
 
-// ---- the stream buffer of K23 jpeg_huffman (kernels/jpeg_huff_core.h) -------------------
+// ---- the stream buffer of K23 jpeg_huffman (kernels/jpeg_huff_core.h) and of the K24 ----
+// ---- jpeg_huffman_wide kernels (kernels/jpeg_huff_wide_core.h) ---------------------------
 namespace jh = tcamd_jhuff;
 
 struct NotPackable {};
+
+// what the kernel that reads the buffer takes
+struct PackFor {
+  uint32_t magic, max_sub, max_data, scale;  // scale: the header word K23 leaves 0
+};
+constexpr PackFor kPackK23{jh::kMagic, (uint32_t)jh::kMaxSub, jh::kMaxDataBytes, 0};
 
 // One linear pass over the scan: the bytes between markers are copied (memchr /
 // memcpy runs), FF 00 becomes FF, every expected RSTn closes a segment.
 // Anything but the plain structure throws NotPackable: the host decoder then
 // gives the answer or the error.
-uint64_t stream_pack(const uint8_t* d, size_t n, const Parsed& P, uint8_t* out, uint64_t cap) {
+uint64_t stream_pack(const uint8_t* d, size_t n, const Parsed& P, uint8_t* out, uint64_t cap,
+                     const PackFor& lim = kPackK23) {
   // the distinct tables in order of first use
   int ids[jh::kMaxTabs];
   uint32_t ntab = 0, tabmap = 0;
@@ -399,7 +409,7 @@ uint64_t stream_pack(const uint8_t* d, size_t n, const Parsed& P, uint8_t* out, 
   const uint64_t mcus = (uint64_t)P.mcux * P.mcuy;
   const uint64_t interval = P.dri && (uint64_t)P.dri < mcus ? (uint64_t)P.dri : mcus;
   const uint64_t nseg = (mcus + interval - 1) / interval;
-  if (nseg > (uint64_t)jh::kMaxSub) throw NotPackable{};
+  if (nseg > (uint64_t)lim.max_sub) throw NotPackable{};
   const uint32_t data_off = jh::data_offset(ntab, (uint32_t)nseg);
   if (cap < (uint64_t)data_off + jh::kTailPad) throw NotPackable{};
 
@@ -436,13 +446,13 @@ uint64_t stream_pack(const uint8_t* d, size_t n, const Parsed& P, uint8_t* out, 
     }
     // a marker, or the end of the blob: the segment is complete
     const uint64_t bytes = o - seg_start;
-    if (bytes > jh::kMaxDataBytes) throw NotPackable{};
+    if (bytes > lim.max_data) throw NotPackable{};
     segs[k].byte_off = (uint32_t)seg_start;
     segs[k].bits = (uint32_t)bytes * 8;
     segs[k].first_mcu = (uint32_t)(k * interval);
     segs[k].first_sub = nsub;
     nsub += jh::subs_of((uint32_t)bytes * 8);
-    if (nsub > (uint32_t)jh::kMaxSub) throw NotPackable{};  // above what the kernel's workspace holds
+    if (nsub > lim.max_sub) throw NotPackable{};  // above what the kernel's workspace holds
     while (o % 4) data[o++] = 0;
     size_t m = p;
     while (m < n && d[m] == 0xFF) ++m;
@@ -466,7 +476,8 @@ uint64_t stream_pack(const uint8_t* d, size_t n, const Parsed& P, uint8_t* out, 
   o += jh::kTailPad;
 
   jh::StreamHeader* h = reinterpret_cast<jh::StreamHeader*>(out);
-  h->magic = jh::kMagic;
+  h->magic = lim.magic;
+  h->reserved = lim.scale;
   h->total_bytes = data_off + (uint32_t)o;
   h->h = P.h;
   h->w = P.w;
@@ -506,6 +517,73 @@ uint32_t emulate(const uint8_t* stream, uint8_t* coef, uint64_t cap, uint32_t* r
   for (uint32_t t = 0; t < (uint32_t)jh::kThreads; ++t) jh::phase_count(t, g, w);
   for (uint32_t t = 0; t < (uint32_t)jh::kThreads; ++t) jh::phase_write(t, g, w, coef);
   return w.status;
+}
+
+// The K24 launch sequence on the host (kernels/jpeg_huff_wide_core.h): launch by launch, workgroup
+// by workgroup, each phase for every thread in turn where the kernels have a barrier.  A
+// workgroup that a kernel leaves by a uniform early return is left the same way.  The workspace
+// is a heap block of exactly the size the device call asks for.  *changed counts the inter-chunk
+// launches (r >= 1) in which a chunk took a new entry.
+uint32_t emulate_wide(const uint8_t* stream, uint8_t* coef, uint64_t cap, uint32_t cs, uint32_t* changed) {
+  if (changed) *changed = 0;
+  if (cs == 0) cs = jh::kThreads;
+  jh::WideGeo wg;
+  if (!jh::chunk_subs_ok(cs) || !jh::read_header_wide(stream, wg) || cap < wg.g.coef_bytes) return jh::kBadHeader;
+  const jh::Geo& g = wg.g;
+  const uint32_t T = jh::kThreads, nchunk = (g.nsub + cs - 1) / cs;
+  std::unique_ptr<uint8_t[]> store(new uint8_t[jh::wide_ws_bytes(g.nsub, nchunk)]);
+  const jh::WideWs w = jh::wide_ws_carve(store.get(), g.nsub, nchunk);
+  std::vector<jh::HuffTab> tabs(jh::kMaxTabs);  // every workgroup's copy holds the same
+  std::vector<jh::Acc> lds(T), next(T);
+  uint32_t status = jh::kOk;
+  for (uint32_t k = 0; k < nchunk; ++k) {
+    const jh::Chunk c = jh::chunk_of(g, cs, k);
+    for (uint32_t t = 0; t < T; ++t) jh::wide_init(t, wg, w, c, coef, &status);
+  }
+  if (status != jh::kOk) return status;  // the later launches return at once
+  for (uint32_t t = 0; t < T; ++t) jh::wide_load_tables(t, g, tabs.data());
+  for (uint32_t r = 0; r < nchunk; ++r) {
+    bool took = false;
+    for (uint32_t k = 0; k < nchunk; ++k) {
+      const jh::Chunk c = jh::chunk_of(g, cs, k);
+      if (r == 0 || jh::wide_take(w, c, r)) {
+        took = true;
+        for (uint32_t round = 0; round <= c.n; ++round) {
+          if (round)
+            for (uint32_t t = 0; t < T; ++t) jh::wide_sync_read(t, w, c);
+          bool any = false;
+          for (uint32_t t = 0; t < T; ++t) any |= jh::wide_sync_decode(t, g, tabs.data(), w, c);
+          if (!any) break;
+        }
+      }
+      jh::wide_publish(w, c, r);
+    }
+    if (r && took && changed) ++*changed;
+  }
+  auto scan = [&](uint32_t n) {
+    for (uint32_t d = 1; d < n; d <<= 1) {
+      for (uint32_t t = 0; t < T; ++t) next[t] = jh::scan_step(t, d, lds.data());
+      lds.swap(next);
+    }
+  };
+  for (uint32_t k = 0; k < nchunk; ++k) {
+    const jh::Chunk c = jh::chunk_of(g, cs, k);
+    for (uint32_t t = 0; t < T; ++t) lds[t] = jh::wide_count_load(t, w, c);
+    scan(c.n);
+    for (uint32_t t = 0; t < T; ++t) jh::wide_count_store(t, w, c, lds.data());
+  }
+  jh::Acc carry{0, 0, 0, 0, 0};
+  for (uint32_t base = 0; base < nchunk; base += T) {
+    for (uint32_t t = 0; t < T; ++t) lds[t] = jh::wide_tile_load(t, w, base, nchunk);
+    scan(T);
+    for (uint32_t t = 0; t < T; ++t) jh::wide_tile_store(t, w, base, nchunk, carry, lds.data());
+    carry = jh::combine(carry, lds[T - 1]);
+  }
+  for (uint32_t k = 0; k < nchunk; ++k) {
+    const jh::Chunk c = jh::chunk_of(g, cs, k);
+    for (uint32_t t = 0; t < T; ++t) jh::wide_write(t, wg, tabs.data(), w, c, coef, &status);
+  }
+  return status;
 }
 
 // one component's blocks -> its sample plane, (bh*8) x (bw*8)
@@ -739,6 +817,43 @@ int tcamd_host_jpeg_huffman_emulate(const uint8_t* stream, uint8_t* coef, uint64
   uint32_t st = jh::kBadHeader;
   try {
     st = emulate(stream, coef, cap, rounds);
+  } catch (const std::bad_alloc&) {
+    return -1;
+  }
+  if (status) *status = st;
+  return 0;
+}
+
+uint64_t tcamd_host_jpeg_stream_bound_wide(uint64_t n) {
+  // as above; a restart interval ends in a marker of two bytes, so n bytes hold n / 2 + 1 at most
+  const uint64_t nseg = n / 2 + 1 < jh::kWideMaxSub ? n / 2 + 1 : jh::kWideMaxSub;
+  return (uint64_t)jh::data_offset(jh::kMaxTabs, (uint32_t)nseg) + n + 4 * nseg + 4 * jh::kTailPad;
+}
+
+int tcamd_host_jpeg_stream_pack_wide(const uint8_t* blob, uint64_t n, int scale, uint8_t* out, uint64_t cap,
+                                     uint64_t* used, uint32_t* nsub, TcamdJpegInfo* info, char* msg, int msg_cap) {
+  return guarded(msg, msg_cap, [&] {
+    check_scale(scale);
+    Parsed P;
+    parse(blob, (size_t)n, P);
+    if (info) fill_info(P, info, scale);
+    try {
+      if (reinterpret_cast<uintptr_t>(out) % 16) throw NotPackable{};  // the buffer is read as words on the device
+      const uint64_t bytes = stream_pack(blob, (size_t)n, P, out, cap,
+                                         PackFor{jh::kWideMagic, jh::kWideMaxSub, jh::kWideMaxDataBytes, (uint32_t)scale});
+      if (used) *used = bytes;
+      if (nsub) *nsub = reinterpret_cast<const jh::StreamHeader*>(out)->nsub;
+    } catch (const NotPackable&) {
+      throw Error{TCAMD_JPEG_NOT_PACKABLE, "not packable"};
+    }
+  });
+}
+
+int tcamd_host_jpeg_huffman_wide_emulate(const uint8_t* stream, uint8_t* coef, uint64_t cap, uint32_t chunk_subs,
+                                         uint32_t* status, uint32_t* launches_that_changed) {
+  uint32_t st = jh::kBadHeader;
+  try {
+    st = emulate_wide(stream, coef, cap, chunk_subs, launches_that_changed);
   } catch (const std::bad_alloc&) {
     return -1;
   }

@@ -76,4 +76,25 @@ int tcamd_host_jpeg_stream_pack(const uint8_t* blob, uint64_t n, uint8_t* out, u
 int tcamd_host_jpeg_huffman_emulate(const uint8_t* stream, uint8_t* coef, uint64_t cap, uint32_t* status,
                                     uint32_t* rounds);
 
+// The same for the K24 jpeg_huffman_wide kernels (csrc/kernels/jpeg_huff_wide.hip,
+// layout and launch sequence: csrc/kernels/jpeg_huff_wide_core.h), which take a
+// scan of up to 32 MiB of unstuffed data (262,144 subsequences) and write the
+// compact coefficient buffer of any scale.  The pack is the one above with
+// another magic word, so that neither kernel accepts the other's buffer, and
+// the scale (1, 2, 4 or 8; anything else is the error of
+// tcamd_host_jpeg_parse_scaled) in the header; info is the parse at that
+// scale, *nsub the scan's subsequences, which size the device call's grid and
+// workspace.  The rules of TCAMD_JPEG_NOT_PACKABLE are the same but for the ceiling.
+uint64_t tcamd_host_jpeg_stream_bound_wide(uint64_t n);
+int tcamd_host_jpeg_stream_pack_wide(const uint8_t* blob, uint64_t n, int scale, uint8_t* out, uint64_t cap,
+                                     uint64_t* used, uint32_t* nsub, TcamdJpegInfo* info, char* msg, int msg_cap);
+// The K24 launch sequence run on the host, launch by launch, workgroup by
+// workgroup and thread by thread from the kernels' own header, with chunks of
+// chunk_subs subsequences (a power of two up to 1024; 0 = 1024, the kernels'
+// default; anything else is status 1).  *launches_that_changed = the
+// inter-chunk launches in which a chunk took a new entry.  Returns 0, or -1
+// when out of memory.
+int tcamd_host_jpeg_huffman_wide_emulate(const uint8_t* stream, uint8_t* coef, uint64_t cap, uint32_t chunk_subs,
+                                         uint32_t* status, uint32_t* launches_that_changed);
+
 }  // extern "C"

@@ -115,9 +115,11 @@ struct Geo {
   const uint32_t* words;
 };
 
-TCAMD_HD bool read_header(const uint8_t* buf, Geo& g) {
+// magic, max_sub, max_data: what the reading kernel takes (K23: kMagic, kMaxSub, kMaxDataBytes; the
+// wide kernels of jpeg_huff_wide_core.h have their own)
+TCAMD_HD bool read_header_as(const uint8_t* buf, Geo& g, uint32_t magic, uint32_t max_sub, uint32_t max_data) {
   const StreamHeader& h = *reinterpret_cast<const StreamHeader*>(buf);
-  if (h.magic != kMagic) return false;
+  if (h.magic != magic) return false;
   if (h.h < 1 || h.w < 1 || h.h > kMaxDim || h.w > kMaxDim) return false;
   const bool grey = h.ncomp == 1 && h.hs == 1 && h.vs == 1;
   const bool colour = h.ncomp == 3 && (h.hs == 1 || h.hs == 2) && (h.vs == 1 || h.vs == 2) && !(h.hs == 1 && h.vs == 2);
@@ -142,9 +144,9 @@ TCAMD_HD bool read_header(const uint8_t* buf, Geo& g) {
   g.coef_bytes = (uint32_t)off;
   if (h.interval < 1 || h.interval > g.mcus) return false;
   if (h.nseg != (g.mcus + h.interval - 1) / h.interval) return false;
-  if (h.nsub < h.nseg || h.nsub > (uint32_t)kMaxSub) return false;
+  if (h.nsub < h.nseg || h.nsub > max_sub) return false;
   if (h.ntab < 1 || h.ntab > (uint32_t)kMaxTabs) return false;
-  if (h.data_bytes < kTailPad || h.data_bytes > kMaxDataBytes + 4 * h.nseg + 2 * kTailPad) return false;
+  if (h.data_bytes < kTailPad || h.data_bytes > max_data + 4 * h.nseg + 2 * kTailPad) return false;
   if (h.data_bytes % 4) return false;
   if (h.total_bytes != data_offset(h.ntab, h.nseg) + h.data_bytes) return false;
   g.interval = h.interval;
@@ -166,6 +168,10 @@ TCAMD_HD bool read_header(const uint8_t* buf, Geo& g) {
   g.segs = reinterpret_cast<const Segment*>(buf + kTabOff + h.ntab * sizeof(HuffTab));
   g.words = reinterpret_cast<const uint32_t*>(buf + data_offset(h.ntab, h.nseg));
   return true;
+}
+
+TCAMD_HD bool read_header(const uint8_t* buf, Geo& g) {
+  return read_header_as(buf, g, kMagic, (uint32_t)kMaxSub, kMaxDataBytes);
 }
 
 // the workspace of one image: LDS on the device

@@ -18,8 +18,11 @@ place of K20 (``--kernel``).  ``--jpeg`` sends tests/golden/jpeg's 640x480
 4:2:0 file, which the server Huffman-decodes on the host and finishes with K22
 (``TCAMD_DEVICE_PREPROCESS=0`` in the environment: decodes on the host);
 ``--kernel --jpeg`` also times the host's entropy decode and full decode, and in
-a second JSON line the stream pack (host) and K23 ``jpeg_huffman`` on one and on
-8 copies.  ``--jpeg-scale N`` (1, 2, 4, 8, or 0 for the automatic scale of a
+further JSON lines the wide stream pack (host) and the K24 ``jpeg_huffman_wide``
+launch sequence on one and on 8 copies, with its chunks, launches and the
+inter-chunk launches that changed something, and the stream pack (host) and K23
+``jpeg_huffman`` on one and on 8 copies.  ``--huffman-wide N`` starts the served
+loop's server with ``TCAMD_DEVICE_HUFFMAN_WIDE=N``.  ``--jpeg-scale N`` (1, 2, 4, 8, or 0 for the automatic scale of a
 224 x 224 target) sends the request parameter ``jpeg_scale`` (served) or times
 the reduced-size decode of K22 and of the host and prints the bytes of the
 compact coefficient buffer (``--kernel --jpeg``; the K23 line is left out: K23
@@ -158,6 +161,7 @@ def jpeg_kernel_time(n, iters, scale=1, path=None):
                                                           round(float(np.mean(host["entropy_decode"])), 3)],
                       "host_full_decode_ms_min_mean": [round(float(np.min(host["full_decode"])), 3),
                                                        round(float(np.mean(host["full_decode"])), 3)]}))
+    jpeg_wide_line(hc, hip, blob, info, scale, coef, host, n, iters)
     if scale != 1:
         return  # K23 writes the full layout only
 
@@ -198,6 +202,70 @@ def jpeg_kernel_time(n, iters, scale=1, path=None):
                       "one_image_us_min_mean": [round(float(np.min(huff[1])), 2), round(float(np.mean(huff[1])), 2)],
                       "images": n,
                       "all_images_us_min_mean": [round(float(np.min(huff[n])), 2), round(float(np.mean(huff[n])), 2)],
+                      "status_all_zero": bool((status.cpu().numpy() == 0).all()),
+                      "equals_host_entropy_decode": bool((got == coef).all()),
+                      "host_stream_pack_ms_min_mean": [round(float(np.min(pack_ms)), 4),
+                                                       round(float(np.mean(pack_ms)), 4)],
+                      "host_entropy_decode_ms_min_mean": [round(float(np.min(host["entropy_decode"])), 3),
+                                                          round(float(np.mean(host["entropy_decode"])), 3)]}))
+
+
+def jpeg_wide_line(hc, hip, blob, info, scale, coef, host, n, iters):
+    """K24: the wide pack on the host, the launch sequence of ``hip.jpeg_huffman_wide`` on one image and on
+    ``n`` copies, against the host's entropy decode of the same run."""
+    import numpy as np
+    import torch
+
+    from triton_client_amd.ops import host_codec
+
+    packed = host_codec.aligned_buffer(hc.jpeg_stream_bound_wide(len(blob)))
+    _, used, nsub = hc.jpeg_stream_pack_wide(blob, packed, scale)
+    if used is None:
+        print(json.dumps({"kernel": "K24 jpeg_huffman_wide", "packable": False}))
+        return
+    pack_ms = []
+    for _ in range(20):
+        t0 = time.perf_counter()
+        hc.jpeg_stream_pack_wide(blob, packed, scale)
+        pack_ms.append((time.perf_counter() - t0) * 1e3)
+    _, changed = hc.jpeg_huffman_wide_emulate(packed[:used], np.empty(info.coef_bytes, dtype=np.uint8))
+    chunks = -(-nsub // hip.JPEG_WIDE_CHUNK_SUBS)
+    stride = -(-info.coef_bytes // 128) * 128
+    sstride = -(-used // 16) * 16
+    streams = torch.from_numpy(np.concatenate([np.pad(packed[:used], (0, sstride - used))] * n)).cuda()
+    out = torch.zeros(n * stride, device="cuda", dtype=torch.uint8)
+    status = torch.ones(n, device="cuda", dtype=torch.int32)
+    need = hip.jpeg_huffman_wide_workspace([nsub] * n)
+    ws = torch.empty(need, device="cuda", dtype=torch.uint8)
+    s = torch.cuda.current_stream().cuda_stream
+    sp = [streams.data_ptr() + i * sstride for i in range(n)]
+    cp = [out.data_ptr() + i * stride for i in range(n)]
+    wide = {}
+    for m in (1, n):
+        def call():
+            hip.jpeg_huffman_wide(sp[:m], cp[:m], [nsub] * m, status.data_ptr(), ws.data_ptr(), need, stream=s)
+
+        for _ in range(10):
+            call()
+        torch.cuda.synchronize()
+        ts = []
+        for _ in range(iters):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            call()
+            b.record()
+            b.synchronize()
+            ts.append(a.elapsed_time(b) * 1e3)
+        wide[m] = ts
+    got = out.cpu().numpy().reshape(n, stride)[:, :coef.size]
+    print(json.dumps({"kernel": "K24 jpeg_huffman_wide", "image": list(info.shape), "jpeg_scale": scale,
+                      "jpeg_bytes": len(blob), "stream_bytes": int(used), "coef_bytes": int(info.coef_bytes),
+                      "subsequences": nsub, "chunks": chunks, "launches_per_call": 6 + chunks,
+                      "inter_chunk_launches_that_changed": changed, "workspace_bytes_one_image":
+                      hip.jpeg_huffman_wide_workspace([nsub]), "timed_calls": iters,
+                      "one_image_us_min_mean": [round(float(np.min(wide[1])), 2), round(float(np.mean(wide[1])), 2)],
+                      "images": n,
+                      "all_images_us_min_mean": [round(float(np.min(wide[n])), 2), round(float(np.mean(wide[n])), 2)],
                       "status_all_zero": bool((status.cpu().numpy() == 0).all()),
                       "equals_host_entropy_decode": bool((got == coef).all()),
                       "host_stream_pack_ms_min_mean": [round(float(np.min(pack_ms)), 4),
@@ -271,6 +339,8 @@ def served(args):
     from triton_client_amd.perf.harness import ServerProcess
     from triton_client_amd.utils.image import encode_raw
 
+    if args.huffman_wide is not None:
+        os.environ["TCAMD_DEVICE_HUFFMAN_WIDE"] = str(args.huffman_wide)  # the server process inherits it
     log = os.path.abspath(args.server_log) if args.server_log else None
     if log:
         os.makedirs(os.path.dirname(log), exist_ok=True)
@@ -303,6 +373,7 @@ def served(args):
                        blob_bytes=len(data[0, 0]),
                        device_preprocess=os.environ.get("TCAMD_DEVICE_PREPROCESS", "1") != "0",
                        device_huffman=os.environ.get("TCAMD_DEVICE_HUFFMAN", "0") == "1",
+                       device_huffman_wide=int(os.environ.get("TCAMD_DEVICE_HUFFMAN_WIDE", "0") or 0),
                        top1=int(first[0].argmax()))
             print(json.dumps(res), flush=True)
         c.close()
@@ -321,6 +392,9 @@ def main():
                     help="the reduced-size JPEG decode: request parameter jpeg_scale (served), K22 at that scale "
                          "(--kernel --jpeg); 0 is the automatic scale for 224 x 224")
     ap.add_argument("--jpeg-file", default="", metavar="PATH", help="--jpeg: this baseline JPEG instead of the fixture")
+    ap.add_argument("--huffman-wide", type=int, default=None, metavar="N",
+                    help="served: start the server with TCAMD_DEVICE_HUFFMAN_WIDE=N (JPEG blobs of at least N bytes "
+                         "take the K24 jpeg_huffman_wide kernels; 0 = off)")
     ap.add_argument("--concurrency", type=int, nargs="+", default=[1, 8])
     ap.add_argument("--height", type=int, default=480)
     ap.add_argument("--width", type=int, default=640)

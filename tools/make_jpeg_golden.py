@@ -17,7 +17,12 @@ DCT-domain 1/2, 1/4 and 1/8 decode of libjpeg-turbo) of the existing ``.jpg``
 files of tests/golden/jpeg, as ``.npy``, for each scale at which the draft
 comes out at exactly ``ceil(H / s) x ceil(W / s)``, and a ``manifest.json``
 with the max and mean absolute difference of the numpy reference
-(tests/jpeg_scaled_cases.py) to each.  It writes no JPEG file."""
+(tests/jpeg_scaled_cases.py) to each.  It writes no JPEG file.
+
+``--wide`` writes tests/golden/jpeg_wide: one stream of more than 2048
+subsequences, which K23 declines and the K24 ``jpeg_huffman_wide`` kernels
+(csrc/kernels/jpeg_huff_wide.hip) decode in several chunks; ``.jpg`` and
+``manifest.json`` only, as for ``--huff``."""
 
 import io
 import json
@@ -84,6 +89,12 @@ HUFF_FIXTURES = [
     ("h05_160x120_420_q90_rst7", 160, 120, "420", "case", noise, {"quality": 90, "restart_marker_blocks": 7}),
 ]
 
+# K24: more than 2048 subsequences in one segment (no restart markers): three chunks of 1024
+WIDE_OUT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests", "golden", "jpeg_wide")
+WIDE_FIXTURES = [
+    ("w01_640x480_420_q95_noise", 640, 480, "420", "case", noise, {"quality": 95}),
+]
+
 
 def main(out=OUT, fixtures=FIXTURES, first_seed=1000, decodes=True):
     os.makedirs(out, exist_ok=True)
@@ -145,5 +156,7 @@ if __name__ == "__main__":
         scaled()
     elif sys.argv[1:] == ["--huff"]:
         main(HUFF_OUT, HUFF_FIXTURES, first_seed=2000, decodes=False)
+    elif sys.argv[1:] == ["--wide"]:
+        main(WIDE_OUT, WIDE_FIXTURES, first_seed=3000, decodes=False)
     else:
         main()

@@ -9,6 +9,7 @@ events, peer access.  Kernels (csrc/kernels/*.hip, gfx950):
 * :func:`resize_pack`     K20 bilinear / K21 antialiased resize + adapt + scale/bias + pack of uint8 images
 * :func:`jpeg_decode`     K22 dequantise + IDCT + chroma upsample + YCbCr->RGB of entropy-decoded JPEG coefficients
 * :func:`jpeg_huffman`    K23 Huffman decode of packed JPEG scans into the coefficients K22 reads
+* :func:`jpeg_huffman_wide`  K24 the same across workgroups: scans up to 32 MiB, the compact buffer of any scale
 * :func:`batched_copy`    K7 one-launch gather/concat/scatter of byte ranges
 * :func:`pack_bytes`      K2 BYTES serialisation (LDS block scan + scatter)
 * :func:`index_bytes`     K3 BYTES index walk through an LDS window
@@ -148,6 +149,14 @@ _SIGS = {
         [
             ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p), ctypes.c_void_p, ctypes.c_int,
             ctypes.c_void_p,
+        ],
+        ctypes.c_int,
+    ),
+    "tcamd_jpeg_huffman_wide_workspace": ([ctypes.c_uint64, ctypes.c_uint64], ctypes.c_uint64),
+    "tcamd_jpeg_huffman_wide": (
+        [
+            ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_uint32),
+            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, ctypes.c_uint32, ctypes.c_void_p,
         ],
         ctypes.c_int,
     ),
@@ -795,6 +804,46 @@ def jpeg_huffman(streams, coefs, status, stream=None):
     s = (ctypes.c_void_p * max(n, 1))(*[int(p) for p in streams])
     c = (ctypes.c_void_p * max(n, 1))(*[int(p) for p in coefs])
     _check(_load().tcamd_jpeg_huffman(s, c, _vp(status), n, _vp(stream)), "jpeg_huffman")
+
+
+JPEG_WIDE_CHUNK_SUBS = 1024  # the default chunk of jpeg_huffman_wide: one subsequence per thread
+
+
+def jpeg_huffman_wide_workspace(nsubs, chunk_subs=0):
+    """The bytes of device workspace a :func:`jpeg_huffman_wide` call over
+    images of ``nsubs`` subsequences needs at ``chunk_subs``."""
+    cs = int(chunk_subs) or JPEG_WIDE_CHUNK_SUBS
+    return int(_load().tcamd_jpeg_huffman_wide_workspace(sum(int(n) for n in nsubs),
+                                                         sum(-(-int(n) // cs) for n in nsubs)))
+
+
+def jpeg_huffman_wide(streams, coefs, nsubs, status, workspace, workspace_bytes, chunk_subs=0, stream=None):
+    """K24: the Huffman stage of a baseline JPEG decode across workgroups, for
+    scans of up to 32 MiB and for any scale.  ``streams[i]`` is a device
+    pointer, 16-byte aligned, to the stream buffer
+    ``ops.host_codec.HostCodec.jpeg_stream_pack_wide`` wrote for image i at its
+    scale, ``nsubs[i]`` the subsequence count the pack returned, ``coefs[i]`` a
+    device pointer, 16-byte aligned, to ``coef_bytes`` of the parse at that
+    scale, which receive the compact buffer :func:`jpeg_decode` reads, byte for
+    byte what ``jpeg_entropy_decode(blob, out, scale)`` writes.  ``status`` is
+    a device pointer to one uint32 per image: 0, or the reason that image's
+    coefficients are not to be used.  ``workspace`` is a device pointer,
+    16-byte aligned, to ``workspace_bytes`` of scratch memory, at least
+    :func:`jpeg_huffman_wide_workspace` of the call.  ``chunk_subs`` (a power
+    of two up to 1024; 0 = 1024) is the number of subsequences a workgroup
+    handles.  A call is a sequence of launches on ``stream``, none of which
+    waits for the host: ``5 + the largest chunk count of an image`` per 64
+    images.  A null or misaligned pointer, a workspace too small, another
+    ``chunk_subs`` or an ``nsubs[i]`` of 0 raises (hipErrorInvalidValue)
+    without a launch."""
+    n = len(streams)
+    if len(coefs) != n or len(nsubs) != n:
+        raise ValueError("jpeg_huffman_wide: streams, coefs and nsubs must have one entry per image")
+    s = (ctypes.c_void_p * max(n, 1))(*[int(p) for p in streams])
+    c = (ctypes.c_void_p * max(n, 1))(*[int(p) for p in coefs])
+    k = (ctypes.c_uint32 * max(n, 1))(*[int(v) for v in nsubs])
+    _check(_load().tcamd_jpeg_huffman_wide(s, c, k, _vp(status), _vp(workspace), int(workspace_bytes), n,
+                                           int(chunk_subs), _vp(stream)), "jpeg_huffman_wide")
 
 
 def batched_copy(srcs, dsts, sizes, stream=None):

@@ -74,6 +74,15 @@ class HostCodec:
         u32p = ctypes.POINTER(ctypes.c_uint32)
         lib.tcamd_host_jpeg_huffman_emulate.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, u32p, u32p]
         lib.tcamd_host_jpeg_huffman_emulate.restype = ctypes.c_int
+        lib.tcamd_host_jpeg_stream_bound_wide.argtypes = [ctypes.c_uint64]
+        lib.tcamd_host_jpeg_stream_bound_wide.restype = ctypes.c_uint64
+        lib.tcamd_host_jpeg_stream_pack_wide.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, ctypes.c_void_p,
+                                                         ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64), u32p,
+                                                         ctypes.POINTER(JpegInfo), ctypes.c_char_p, ctypes.c_int]
+        lib.tcamd_host_jpeg_stream_pack_wide.restype = ctypes.c_int
+        lib.tcamd_host_jpeg_huffman_wide_emulate.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64,
+                                                             ctypes.c_uint32, u32p, u32p]
+        lib.tcamd_host_jpeg_huffman_wide_emulate.restype = ctypes.c_int
         lib.tcamd_host_pack_bytes.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]
         lib.tcamd_host_pack_bytes.restype = ctypes.c_int
         lib.tcamd_host_count_bytes.argtypes = [ctypes.c_void_p, ctypes.c_uint64]
@@ -201,6 +210,45 @@ class HostCodec:
                                                      ctypes.byref(status), ctypes.byref(rounds)):
             raise MemoryError("jpeg_huffman_emulate")
         return int(status.value), int(rounds.value)
+
+    # -- the stream buffer of the K24 jpeg_huffman_wide kernels (csrc/kernels/jpeg_huff_wide_core.h)
+    def jpeg_stream_bound_wide(self, nbytes):
+        """A capacity that holds the wide stream buffer of every packable blob of ``nbytes``."""
+        return int(self._lib.tcamd_host_jpeg_stream_bound_wide(int(nbytes)))
+
+    def jpeg_stream_pack_wide(self, blob, out, scale=1):
+        """:meth:`jpeg_stream_pack` for ``ops.hip.jpeg_huffman_wide``: the same
+        one-pass pack under another magic word, with ``scale`` (1, 2, 4 or 8)
+        in the header and a ceiling of 32 MiB of scan data instead of 256 KiB.
+        Returns ``(info, used, nsub)``: the parse at ``scale``, the bytes
+        written and the scan's subsequences (they size the kernel's grid and
+        workspace), or ``(info, None, None)`` when the blob is not packable."""
+        info = JpegInfo()
+        used, nsub = ctypes.c_uint64(0), ctypes.c_uint32(0)
+        msg = ctypes.create_string_buffer(96)
+        rc = self._lib.tcamd_host_jpeg_stream_pack_wide(blob, len(blob), _check_scale(scale), out.ctypes.data, out.size,
+                                                        ctypes.byref(used), ctypes.byref(nsub), ctypes.byref(info),
+                                                        msg, len(msg))
+        if rc == JPEG_NOT_PACKABLE:
+            return info, None, None
+        self._jpeg_check(rc, msg)
+        return info, int(used.value), int(nsub.value)
+
+    def jpeg_huffman_wide_emulate(self, stream, out, chunk_subs=0):
+        """The K24 launch sequence run on the host, launch by launch, workgroup
+        by workgroup and thread by thread from the kernels' own header: the
+        uint8 array ``stream`` (a wide stream buffer) -> coefficients in
+        ``out`` (``coef_bytes`` of the parse at the stream's scale, 16-byte
+        aligned), in chunks of ``chunk_subs`` subsequences (a power of two up
+        to 1024; 0 = the default 1024).  Returns ``(status, changed)``: the
+        status word (0 = the coefficients are good) and the inter-chunk
+        launches in which a chunk took a new entry."""
+        status, changed = ctypes.c_uint32(0), ctypes.c_uint32(0)
+        if self._lib.tcamd_host_jpeg_huffman_wide_emulate(stream.ctypes.data, out.ctypes.data, out.size,
+                                                          int(chunk_subs), ctypes.byref(status),
+                                                          ctypes.byref(changed)):
+            raise MemoryError("jpeg_huffman_wide_emulate")
+        return int(status.value), int(changed.value)
 
 
 _INSTANCE = None

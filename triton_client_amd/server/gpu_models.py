@@ -516,6 +516,18 @@ class PreprocessInception(Model):
     the stream synchronise) is decoded by the host, which fills its row or
     fails its request with the host decoder's message.
 
+    ``TCAMD_DEVICE_HUFFMAN_WIDE=N`` (read at load; the default 0 is off) sends
+    every JPEG blob of at least N bytes that K23 did not take (its knob is off,
+    the request is scaled, its pack declined) to the K24 ``jpeg_huffman_wide``
+    kernels (csrc/kernels/jpeg_huff_wide.hip), which decode a scan of up to
+    32 MiB across workgroups and write the compact coefficient buffer of any
+    ``jpeg_scale``: the host packs the scan (``HostCodec.jpeg_stream_pack_wide``)
+    into the bottom of the staging area, one ``hip.jpeg_huffman_wide`` call per
+    batch runs before K22 on the slot's stream, and its workspace, like the
+    coefficients and the pixels, comes from the device-only top of the staging
+    buffer and counts in the fit test.  The fallback rule is K23's, at the
+    request's scale.
+
     The custom request parameter ``antialias`` (bool, default false) selects
     the antialiased resize for that request's images: the batch's device jobs
     are split by the flag into at most one K20 and one K21 ``resize_pack``
@@ -530,9 +542,8 @@ class PreprocessInception(Model):
     staging-area fit test counts the compact coefficient buffer and the reduced
     pixels (a 12-megapixel 4:2:0 photo needs about 1.7 MB at 1/8 instead of
     72 MB), and K22 decodes the images of all scales of a batch in the same
-    ``jpeg_decode`` call.  A JPEG at a scale other than 1 always takes the
-    host's entropy decoder, whatever ``TCAMD_DEVICE_HUFFMAN`` says: K23 writes
-    the full layout.  The host fallbacks decode at the same scale, so every
+    ``jpeg_decode`` call.  A JPEG at a scale other than 1 never takes K23,
+    whatever ``TCAMD_DEVICE_HUFFMAN`` says: K23 writes the full layout.  The host fallbacks decode at the same scale, so every
     route gives the same rows.  PPM / PGM / TCIMG blobs ignore the parameter;
     any other value fails that request alone."""
 
@@ -562,6 +573,7 @@ class PreprocessInception(Model):
         self._host = HostPreprocess(self.version)
         self.device_path = os.environ.get("TCAMD_DEVICE_PREPROCESS", "1") != "0"
         self.device_huffman = os.environ.get("TCAMD_DEVICE_HUFFMAN", "0") == "1"
+        self.device_huffman_wide = max(0, int(os.environ.get("TCAMD_DEVICE_HUFFMAN_WIDE", "0") or 0))
         if not self.device_path:
             return
         import torch
@@ -627,7 +639,7 @@ class PreprocessInception(Model):
         return decode_image(blob)
 
     def _read_status(self, status):
-        """K23's status words of a batch, after the stream synchronise."""
+        """The status words K23 or K24 left for a batch, after the stream synchronise."""
         return status.cpu().numpy()
 
     def execute(self, requests):
@@ -651,12 +663,14 @@ class PreprocessInception(Model):
         dev_jobs = {False: [], True: []}  # by the request's antialias flag: (row, image shape, staging offset)
         jpeg_jobs = []  # (coefficient offset, parse, pixel offset)
         huff_jobs = []  # device Huffman: (stream offset, coefficient offset, row, blob, antialias, request)
+        wide_jobs = []  # K24: (stream offset, coefficient offset, row, blob, antialias, request, subsequences, scale)
         host_jobs = []  # (row, image, antialias)
         rows = used = 0
         top = self.STAGE_BYTES
+        ws_need = 0  # K24's workspace, placed below ``top`` once the plan is made: what is left ends there
         for r in requests:
             mark = (rows, used, top, len(dev_jobs[False]), len(dev_jobs[True]), len(jpeg_jobs), len(host_jobs),
-                    len(huff_jobs))
+                    len(huff_jobs), len(wide_jobs), ws_need)
             try:
                 aa = self._host.wants_antialias(r)
                 scale = self._host.jpeg_scale_of(r)
@@ -667,7 +681,8 @@ class PreprocessInception(Model):
                             # the stream at the bottom; coefficients and pixels, device only, at the top
                             at = -(-used // 16) * 16
                             coef = (top - info.pixel_bytes - info.coef_bytes) // 128 * 128
-                            n = self._codec.jpeg_stream_pack(blob, stage[at:coef])[1] if at < coef else None
+                            n = self._codec.jpeg_stream_pack(blob, stage[at:coef - ws_need])[1] \
+                                if at < coef - ws_need else None
                             if n is not None:
                                 used = at + n
                                 top -= info.pixel_bytes
@@ -677,8 +692,28 @@ class PreprocessInception(Model):
                                 top = coef
                                 rows += 1
                                 continue
+                        if self.device_huffman_wide and len(blob) >= self.device_huffman_wide:
+                            # as above, and room for the workspace of the batch's K24 call
+                            at = -(-used // 16) * 16
+                            coef = (top - info.pixel_bytes - info.coef_bytes) // 128 * 128
+                            n = need = None
+                            if at < coef - ws_need:
+                                n, nsub = self._codec.jpeg_stream_pack_wide(blob, stage[at:coef - ws_need],
+                                                                            info.scale)[1:]
+                            if n is not None:  # 16: the workspace starts at a 16-byte boundary
+                                need = 16 + hip.jpeg_huffman_wide_workspace([j[6] for j in wide_jobs] + [nsub])
+                            if n is not None and at + n <= coef - need:
+                                used = at + n
+                                ws_need = need
+                                top -= info.pixel_bytes
+                                wide_jobs.append((at, coef, rows, blob, aa, len(plan), nsub, info.scale))
+                                jpeg_jobs.append((coef, info, top))
+                                dev_jobs[aa].append((rows, info.shape, top))
+                                top = coef
+                                rows += 1
+                                continue
                         coef = -(-used // 128) * 128
-                        if coef + info.coef_bytes + info.pixel_bytes <= top:
+                        if coef + info.coef_bytes + info.pixel_bytes <= top - ws_need:
                             self._codec.jpeg_entropy_decode(blob, stage[coef:coef + info.coef_bytes], info.scale)
                             used = coef + info.coef_bytes
                             top -= info.pixel_bytes
@@ -689,7 +724,7 @@ class PreprocessInception(Model):
                         item = self._codec.jpeg_decode(blob, info.scale)
                     h, w, c = item.shape
                     if 1 <= h <= hip.RESIZE_MAX_DIM and 1 <= w <= hip.RESIZE_MAX_DIM and c in (1, 3) \
-                            and used + item.size <= top:
+                            and used + item.size <= top - ws_need:
                         stage[used:used + item.size] = item.reshape(-1)
                         dev_jobs[aa].append((rows, item.shape, used))
                         used += item.size
@@ -698,7 +733,9 @@ class PreprocessInception(Model):
                     rows += 1
             except Exception as e:  # noqa: BLE001 - an undecodable blob fails its own request
                 rows, used, top = mark[:3]
-                for jobs, n in zip((dev_jobs[False], dev_jobs[True], jpeg_jobs, host_jobs, huff_jobs), mark[3:]):
+                ws_need = mark[-1]
+                for jobs, n in zip((dev_jobs[False], dev_jobs[True], jpeg_jobs, host_jobs, huff_jobs, wide_jobs),
+                                   mark[3:-1]):
                     del jobs[n:]
                 plan.append(e)
                 continue
@@ -719,6 +756,12 @@ class PreprocessInception(Model):
                 status = torch.empty(len(huff_jobs), device=stream.device, dtype=torch.int32)
                 hip.jpeg_huffman([src + at for at, *_ in huff_jobs], [src + coef for _, coef, *_ in huff_jobs],
                                  status.data_ptr(), stream=sh)
+            wide_status = None
+            if wide_jobs:
+                wide_status = torch.empty(len(wide_jobs), device=stream.device, dtype=torch.int32)
+                hip.jpeg_huffman_wide([src + j[0] for j in wide_jobs], [src + j[1] for j in wide_jobs],
+                                      [j[6] for j in wide_jobs], wide_status.data_ptr(),
+                                      src + (top - ws_need + 15) // 16 * 16, ws_need - 16, stream=sh)
             if jpeg_jobs:
                 hip.jpeg_decode([src + coef for coef, _, _ in jpeg_jobs], [info for _, info, _ in jpeg_jobs],
                                 [src + pix for _, _, pix in jpeg_jobs], stream=sh)
@@ -734,14 +777,19 @@ class PreprocessInception(Model):
                             for r, p in zip(requests, plan))
             host_all = out.cpu().numpy() if want_host else None  # synchronises the stream
             hip.stream_synchronize(sh)
-            if status is not None:
-                # an image K23 gave up on: the host decodes it into its row, or its request fails
-                redo = [job for job, st in zip(huff_jobs, self._read_status(status)) if st]
-                for _, _, row, blob, aa, req in redo:
+            if status is not None or wide_status is not None:
+                # an image K23 or K24 gave up on: the host decodes it into its row, or its request fails
+                redo = []
+                if status is not None:
+                    redo += [job + (0, 1) for job, st in zip(huff_jobs, self._read_status(status)) if st]
+                if wide_status is not None:
+                    redo += [job for job, st in zip(wide_jobs, self._read_status(wide_status)) if st]
+                for _, _, row, blob, aa, req, _, scale in redo:
                     if isinstance(plan[req], Exception):
                         continue
                     try:
-                        img = inception_preprocess(self._codec.jpeg_decode(blob), self.H, self.W, "NCHW", antialias=aa)
+                        img = inception_preprocess(self._codec.jpeg_decode(blob, scale), self.H, self.W, "NCHW",
+                                                   antialias=aa)
                     except Exception as e:  # noqa: BLE001 - the host decoder's error fails this request alone
                         plan[req] = e
                         continue

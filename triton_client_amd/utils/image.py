@@ -263,8 +263,15 @@ def preprocess_batch_device(resized, scaling="INCEPTION", fmt="NCHW", dtype="FP3
     return dst.cpu().numpy()
 
 
+def device_huffman_wide_knob():
+    """``TCAMD_DEVICE_HUFFMAN_WIDE``: the smallest JPEG blob, in bytes, whose
+    Huffman stage the K24 ``jpeg_huffman_wide`` kernels take; 0 (the default)
+    is off, 1 is every JPEG."""
+    return max(0, int(os.environ.get("TCAMD_DEVICE_HUFFMAN_WIDE", "0") or 0))
+
+
 def preprocess_raw_batch_device(images, c, h, w, scaling="INCEPTION", fmt="NCHW", dtype="FP32", device=0,
-                                antialias=False, device_huffman=None, jpeg_scale=1):
+                                antialias=False, device_huffman=None, jpeg_scale=1, device_huffman_wide=None):
     """``preprocess`` of a batch of decoded uint8 HWC images of any sizes on
     the GPU: the raw pixels go up in ONE uint8 host->device copy (a quarter of
     the bytes of the resized fp32 images, and no host resize), K20
@@ -284,8 +291,14 @@ def preprocess_raw_batch_device(images, c, h, w, scaling="INCEPTION", fmt="NCHW"
     that fraction of their size (the host stores, and the upload carries, only
     the coefficients the reduced transform uses), 0 picks
     :func:`jpeg_auto_scale` per JPEG for the ``h x w`` target; a JPEG decoded
-    at a reduced size always takes the host's entropy decoder.  Returns None
-    when the datatype has no device path (integer models)."""
+    at a reduced size never takes K23.  ``device_huffman_wide`` (default:
+    ``TCAMD_DEVICE_HUFFMAN_WIDE`` in the environment; 0 is off) is the smallest
+    JPEG blob, in bytes, that the K24 ``jpeg_huffman_wide`` kernels decode,
+    at any scale and up to 32 MiB of scan, when K23 did not take it: the host
+    packs its scan (``HostCodec.jpeg_stream_pack_wide``) and one
+    ``hip.jpeg_huffman_wide`` call per batch writes the compact coefficient
+    buffers ahead of K22; the fallbacks are K23's.  Returns None when the
+    datatype has no device path (integer models)."""
     if dtype not in _DEVICE_DTYPES:
         return None
     import torch
@@ -309,16 +322,30 @@ def preprocess_raw_batch_device(images, c, h, w, scaling="INCEPTION", fmt="NCHW"
 
     if device_huffman is None:
         device_huffman = os.environ.get("TCAMD_DEVICE_HUFFMAN", "0") == "1"
+    if device_huffman_wide is None:
+        device_huffman_wide = device_huffman_wide_knob()
     # the upload: arrays as they are, JPEG coefficient buffers at 128-byte boundaries, packed JPEG
     # streams (device Huffman) at 16-byte boundaries
     offs, shapes, up, pix = [], [], 0, 0
-    packed = {}  # item index -> its stream buffer
+    packed = {}  # item index -> its stream buffer (K23)
+    wide = {}  # item index -> (its wide stream buffer, its subsequences) (K24)
     for k, im in enumerate(items):
         if isinstance(im, tuple) and device_huffman and im[1].scale == 1:
             buf = host_codec.aligned_buffer(_jpeg_codec().jpeg_stream_bound(len(im[0])))
             n = _jpeg_codec().jpeg_stream_pack(im[0], buf)[1]
             if n is not None:
                 packed[k] = buf[:n]
+                up = -(-up // 16) * 16
+                offs.append(up)
+                up += n
+                pix += im[1].pixel_bytes
+                shapes.append(im[1].shape)
+                continue
+        if isinstance(im, tuple) and device_huffman_wide and len(im[0]) >= device_huffman_wide:
+            buf = host_codec.aligned_buffer(_jpeg_codec().jpeg_stream_bound_wide(len(im[0])))
+            _, n, nsub = _jpeg_codec().jpeg_stream_pack_wide(im[0], buf, im[1].scale)
+            if n is not None:
+                wide[k] = (buf[:n], nsub)
                 up = -(-up // 16) * 16
                 offs.append(up)
                 up += n
@@ -339,6 +366,8 @@ def preprocess_raw_batch_device(images, c, h, w, scaling="INCEPTION", fmt="NCHW"
     for k, (im, o) in enumerate(zip(items, offs)):
         if k in packed:
             raw[o:o + packed[k].size] = packed[k]
+        elif k in wide:
+            raw[o:o + wide[k][0].size] = wide[k][0]
         elif isinstance(im, tuple):
             _jpeg_codec().jpeg_entropy_decode(im[0], raw[o:o + im[1].coef_bytes], im[1].scale)
         else:
@@ -358,6 +387,21 @@ def preprocess_raw_batch_device(images, c, h, w, scaling="INCEPTION", fmt="NCHW"
                          stream=stream)
         for k, a in zip(packed, at):
             srcs[k] = coefs.data_ptr() + a
+    wide_status = None
+    if wide:
+        # K24: the same, with a workspace
+        at = [0]
+        for k in wide:
+            at.append(at[-1] + -(-items[k][1].coef_bytes // 128) * 128)
+        wide_coefs = torch.empty(at[-1], device=dev, dtype=torch.uint8)
+        wide_status = torch.empty(len(wide), device=dev, dtype=torch.int32)
+        nsubs = [nsub for _, nsub in wide.values()]
+        need = hip.jpeg_huffman_wide_workspace(nsubs)
+        workspace = torch.empty(need, device=dev, dtype=torch.uint8)
+        hip.jpeg_huffman_wide([srcs[k] for k in wide], [wide_coefs.data_ptr() + a for a in at[:-1]], nsubs,
+                              wide_status.data_ptr(), workspace.data_ptr(), need, stream=stream)
+        for k, a in zip(wide, at):
+            srcs[k] = wide_coefs.data_ptr() + a
     if pix:
         decoded = torch.empty(pix, device=dev, dtype=torch.uint8)
         jobs, at = [], decoded.data_ptr()
@@ -374,7 +418,7 @@ def preprocess_raw_batch_device(images, c, h, w, scaling="INCEPTION", fmt="NCHW"
     hip.resize_pack(srcs, shapes, [dst.data_ptr() + i * per for i in range(len(items))], dtype, fmt, c, h, w,
                     scale=scale, bias=bias, stream=stream, antialias=antialias)
     out = dst.cpu().numpy()
-    if status is not None and status.cpu().numpy().any():
+    if any(st is not None and st.cpu().numpy().any() for st in (status, wide_status)):
         return preprocess_raw_batch_device(images, c, h, w, scaling, fmt, dtype, device, antialias,
-                                           device_huffman=False, jpeg_scale=jpeg_scale)
+                                           device_huffman=False, jpeg_scale=jpeg_scale, device_huffman_wide=0)
     return out

@@ -861,6 +861,10 @@ int tcamd_host_jpeg_huffman_wide_emulate(const uint8_t* stream, uint8_t* coef, u
   return 0;
 }
 
+uint64_t tcamd_host_jpeg_huffman_wide_workspace(uint64_t total_subsequences, uint64_t total_chunks) {
+  return jh::wide_ws_bytes(total_subsequences, total_chunks);
+}
+
 int tcamd_host_jpeg_decode(const uint8_t* blob, uint64_t n, uint8_t* out, uint64_t cap, char* msg, int msg_cap) {
   return guarded(msg, msg_cap, [&] {
     Parsed P;

@@ -96,5 +96,9 @@ int tcamd_host_jpeg_stream_pack_wide(const uint8_t* blob, uint64_t n, int scale,
 // when out of memory.
 int tcamd_host_jpeg_huffman_wide_emulate(const uint8_t* stream, uint8_t* coef, uint64_t cap, uint32_t chunk_subs,
                                          uint32_t* status, uint32_t* launches_that_changed);
+// The bytes of workspace a K24 call over that many subsequences and chunks
+// needs: tcamd_jpeg_huffman_wide_workspace of the device library, for a
+// staging plan made where that library is not loaded.
+uint64_t tcamd_host_jpeg_huffman_wide_workspace(uint64_t total_subsequences, uint64_t total_chunks);
 
 }  // extern "C"

@@ -107,8 +107,10 @@ def test_every_fixture_alone_equals_the_host_entropy_decode(cases, scale):
 
 
 def test_w01_is_what_it_is_for(cases, hc):
-    from triton_client_amd.ops import host_codec
+    from triton_client_amd.ops import hip, host_codec
 
+    for nsubs in ([1], [1024], [1025, 1], [2808] * 3, [2048] * 64):  # the host library sizes the same workspace
+        assert hc.jpeg_huffman_wide_workspace(nsubs) == hip.jpeg_huffman_wide_workspace(nsubs), nsubs
     w01 = cases[1][-1]
     assert w01.nsub > jh.MAX_SUB and -(-w01.nsub // 1024) == 3  # three chunks at the default
     assert int(w01.stream[:64].view("<u4")[10]) == 1  # one segment

@@ -338,6 +338,7 @@ def served(args):
     import tritonclient.grpc as grpcclient
     from triton_client_amd.perf.harness import ServerProcess
     from triton_client_amd.utils.image import encode_raw
+    from triton_client_amd.utils.jpeg_stage import device_huffman_knob, device_huffman_wide_knob
 
     if args.huffman_wide is not None:
         os.environ["TCAMD_DEVICE_HUFFMAN_WIDE"] = str(args.huffman_wide)  # the server process inherits it
@@ -372,8 +373,7 @@ def served(args):
                        encoding="JPEG" if args.jpeg else "TCIMG", jpeg_scale=args.jpeg_scale,
                        blob_bytes=len(data[0, 0]),
                        device_preprocess=os.environ.get("TCAMD_DEVICE_PREPROCESS", "1") != "0",
-                       device_huffman=os.environ.get("TCAMD_DEVICE_HUFFMAN", "0") == "1",
-                       device_huffman_wide=int(os.environ.get("TCAMD_DEVICE_HUFFMAN_WIDE", "0") or 0),
+                       device_huffman=device_huffman_knob(), device_huffman_wide=device_huffman_wide_knob(),
                        top1=int(first[0].argmax()))
             print(json.dumps(res), flush=True)
         c.close()

@@ -83,6 +83,8 @@ class HostCodec:
         lib.tcamd_host_jpeg_huffman_wide_emulate.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64,
                                                              ctypes.c_uint32, u32p, u32p]
         lib.tcamd_host_jpeg_huffman_wide_emulate.restype = ctypes.c_int
+        lib.tcamd_host_jpeg_huffman_wide_workspace.argtypes = [ctypes.c_uint64, ctypes.c_uint64]
+        lib.tcamd_host_jpeg_huffman_wide_workspace.restype = ctypes.c_uint64
         lib.tcamd_host_pack_bytes.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]
         lib.tcamd_host_pack_bytes.restype = ctypes.c_int
         lib.tcamd_host_count_bytes.argtypes = [ctypes.c_void_p, ctypes.c_uint64]
@@ -249,6 +251,14 @@ class HostCodec:
                                                           ctypes.byref(changed)):
             raise MemoryError("jpeg_huffman_wide_emulate")
         return int(status.value), int(changed.value)
+
+    def jpeg_huffman_wide_workspace(self, nsubs, chunk_subs=0):
+        """``ops.hip.jpeg_huffman_wide_workspace`` without the device library:
+        the bytes of workspace a K24 call over images of ``nsubs``
+        subsequences needs at ``chunk_subs`` (0 = the default 1024)."""
+        cs = int(chunk_subs) or 1024
+        return int(self._lib.tcamd_host_jpeg_huffman_wide_workspace(sum(int(n) for n in nsubs),
+                                                                    sum(-(-int(n) // cs) for n in nsubs)))
 
 
 _INSTANCE = None

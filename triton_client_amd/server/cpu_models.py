@@ -264,18 +264,9 @@ class PreprocessInception(Model):
         except ValueError as e:
             raise ValueError("request parameter %s" % e) from None
 
-    @staticmethod
-    def resolve_jpeg_scale(codec, blob, scale, h, w):
-        """``scale``, or for 0 the automatic scale of this JPEG blob for an ``h x w`` target."""
-        from triton_client_amd.utils.image import jpeg_auto_scale
-
-        if scale:
-            return scale
-        full = codec.jpeg_parse(blob)
-        return jpeg_auto_scale(full.h, full.w, h, w)
-
     def execute(self, requests):
         from triton_client_amd.utils.image import JPEG_SOI, _jpeg_codec, decode_image, inception_preprocess
+        from triton_client_amd.utils.jpeg_stage import parse_at_scale
 
         res = []
         for r in requests:
@@ -286,7 +277,7 @@ class PreprocessInception(Model):
             for b in blobs:
                 if scale != 1 and bytes(b[:2]) == JPEG_SOI:
                     b = bytes(b)
-                    img = decode_image(b, self.resolve_jpeg_scale(_jpeg_codec(), b, scale, 224, 224))
+                    img = decode_image(b, parse_at_scale(_jpeg_codec(), b, scale, 224, 224).scale)
                 else:
                     img = decode_image(b)
                 outs.append(inception_preprocess(img, 224, 224, "NCHW", antialias=aa))

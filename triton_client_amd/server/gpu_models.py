@@ -29,7 +29,7 @@ import threading
 
 import numpy as np
 
-from triton_client_amd.utils import roctx
+from triton_client_amd.utils import jpeg_stage, roctx
 
 from .model_base import Model, TensorSpec
 from .types import DeviceView, OutputTensor, ServerError
@@ -496,37 +496,20 @@ class PreprocessInception(Model):
     limit take the numpy routine.  ``TCAMD_DEVICE_PREPROCESS=0`` (read at
     load) runs the numpy step for everything.
 
-    A baseline JPEG blob is only parsed and Huffman-decoded on the host
-    (csrc/host/jpeg.cc), straight into the pinned staging area; K22
-    ``jpeg_decode`` (csrc/kernels/jpeg.hip, one launch per 64 JPEGs of a batch,
-    before K20 / K21 on the slot's stream) turns the coefficients into pixels
-    at the top of the device staging buffer, which K20 / K21 then read like any
-    staged image.  A JPEG whose coefficients and pixels do not fit what is left
-    of the staging area is decoded on the host and goes on as raw pixels.
-
-    ``TCAMD_DEVICE_HUFFMAN=1`` (read at load; the default 0 is the route above)
-    moves the Huffman stage to the device too: the host only packs the scan
-    (``HostCodec.jpeg_stream_pack``, one pass over the blob) into the bottom of
-    the staging area, so the compressed bytes are what crosses PCIe; K23
-    ``jpeg_huffman`` (csrc/kernels/jpeg_huff.hip, one launch per 64 JPEGs,
-    before K22 on the slot's stream) writes the coefficients, which like the
-    pixels exist at the device-only top of the staging buffer alone.  One
-    fallback rule: a blob the pack declines, or one that does not fit, takes
-    the route above; an image whose status word K23 left non-zero (read after
+    A baseline JPEG blob is routed by ``utils.jpeg_stage``, which defines the
+    routes, their order and the layout of the staging area: by default the host
+    Huffman-decodes it straight into the pinned staging area;
+    ``TCAMD_DEVICE_HUFFMAN=1`` and ``TCAMD_DEVICE_HUFFMAN_WIDE=N`` (both read
+    at load) have the host only pack the scan, and K23 ``jpeg_huffman`` or the
+    K24 ``jpeg_huffman_wide`` kernels decode it on the device.  K22
+    ``jpeg_decode`` turns the coefficients of every route into pixels, which
+    K20 / K21 read like any staged image; all of it runs on the slot's stream,
+    K23, K24, K22 and then the resize.  What this model adds to that module's
+    contract: a JPEG that fits no route is decoded on the host and goes on as
+    raw pixels; a request that raises takes everything it staged back out of
+    the plan; an image whose status word K23 or K24 left non-zero (read after
     the stream synchronise) is decoded by the host, which fills its row or
-    fails its request with the host decoder's message.
-
-    ``TCAMD_DEVICE_HUFFMAN_WIDE=N`` (read at load; the default 0 is off) sends
-    every JPEG blob of at least N bytes that K23 did not take (its knob is off,
-    the request is scaled, its pack declined) to the K24 ``jpeg_huffman_wide``
-    kernels (csrc/kernels/jpeg_huff_wide.hip), which decode a scan of up to
-    32 MiB across workgroups and write the compact coefficient buffer of any
-    ``jpeg_scale``: the host packs the scan (``HostCodec.jpeg_stream_pack_wide``)
-    into the bottom of the staging area, one ``hip.jpeg_huffman_wide`` call per
-    batch runs before K22 on the slot's stream, and its workspace, like the
-    coefficients and the pixels, comes from the device-only top of the staging
-    buffer and counts in the fit test.  The fallback rule is K23's, at the
-    request's scale.
+    fails its request, and that request alone, with the host decoder's message.
 
     The custom request parameter ``antialias`` (bool, default false) selects
     the antialiased resize for that request's images: the batch's device jobs
@@ -542,9 +525,8 @@ class PreprocessInception(Model):
     staging-area fit test counts the compact coefficient buffer and the reduced
     pixels (a 12-megapixel 4:2:0 photo needs about 1.7 MB at 1/8 instead of
     72 MB), and K22 decodes the images of all scales of a batch in the same
-    ``jpeg_decode`` call.  A JPEG at a scale other than 1 never takes K23,
-    whatever ``TCAMD_DEVICE_HUFFMAN`` says: K23 writes the full layout.  The host fallbacks decode at the same scale, so every
-    route gives the same rows.  PPM / PGM / TCIMG blobs ignore the parameter;
+    ``jpeg_decode`` call.  The host fallbacks decode at the same scale, so
+    every route gives the same rows.  PPM / PGM / TCIMG blobs ignore the parameter;
     any other value fails that request alone."""
 
     name = "preprocess_inception"
@@ -572,8 +554,8 @@ class PreprocessInception(Model):
 
         self._host = HostPreprocess(self.version)
         self.device_path = os.environ.get("TCAMD_DEVICE_PREPROCESS", "1") != "0"
-        self.device_huffman = os.environ.get("TCAMD_DEVICE_HUFFMAN", "0") == "1"
-        self.device_huffman_wide = max(0, int(os.environ.get("TCAMD_DEVICE_HUFFMAN_WIDE", "0") or 0))
+        self.device_huffman = jpeg_stage.device_huffman_knob()
+        self.device_huffman_wide = jpeg_stage.device_huffman_wide_knob()
         if not self.device_path:
             return
         import torch
@@ -633,9 +615,7 @@ class PreprocessInception(Model):
 
         blob = bytes(blob)
         if blob[:2] == b"\xff\xd8":
-            if scale != 1:
-                scale = self._host.resolve_jpeg_scale(self._codec, blob, scale, self.H, self.W)
-            return blob, self._codec.jpeg_parse(blob, scale)
+            return blob, jpeg_stage.parse_at_scale(self._codec, blob, scale, self.H, self.W)
         return decode_image(blob)
 
     def _read_status(self, status):
@@ -656,90 +636,27 @@ class PreprocessInception(Model):
         from triton_client_amd.utils.image import inception_preprocess
 
         img_bytes = self.C * self.H * self.W * 4
-        stage = slot["stage_np"]
+        stage = jpeg_stage.StagePlan(slot["stage_np"][:self.STAGE_BYTES], self._codec, self.device_huffman,
+                                     self.device_huffman_wide, hip.RESIZE_MAX_DIM)
         plan = []  # per request: (first_row, n_rows), or its exception
-        # The staging area: raw pixels and JPEG coefficients fill it from the bottom (``used``, the
-        # bytes of the H2D copy); the pixels K22 decodes exist on the device only and take the top.
-        dev_jobs = {False: [], True: []}  # by the request's antialias flag: (row, image shape, staging offset)
-        jpeg_jobs = []  # (coefficient offset, parse, pixel offset)
-        huff_jobs = []  # device Huffman: (stream offset, coefficient offset, row, blob, antialias, request)
-        wide_jobs = []  # K24: (stream offset, coefficient offset, row, blob, antialias, request, subsequences, scale)
-        host_jobs = []  # (row, image, antialias)
-        rows = used = 0
-        top = self.STAGE_BYTES
-        ws_need = 0  # K24's workspace, placed below ``top`` once the plan is made: what is left ends there
         for r in requests:
-            mark = (rows, used, top, len(dev_jobs[False]), len(dev_jobs[True]), len(jpeg_jobs), len(host_jobs),
-                    len(huff_jobs), len(wide_jobs), ws_need)
+            mark = stage.mark()
             try:
                 aa = self._host.wants_antialias(r)
                 scale = self._host.jpeg_scale_of(r)
                 for item in [self._open(b, scale) for b in r.input("INPUT").numpy().reshape(-1)]:
                     if isinstance(item, tuple):
                         blob, info = item
-                        if self.device_huffman and info.scale == 1:
-                            # the stream at the bottom; coefficients and pixels, device only, at the top
-                            at = -(-used // 16) * 16
-                            coef = (top - info.pixel_bytes - info.coef_bytes) // 128 * 128
-                            n = self._codec.jpeg_stream_pack(blob, stage[at:coef - ws_need])[1] \
-                                if at < coef - ws_need else None
-                            if n is not None:
-                                used = at + n
-                                top -= info.pixel_bytes
-                                huff_jobs.append((at, coef, rows, blob, aa, len(plan)))
-                                jpeg_jobs.append((coef, info, top))
-                                dev_jobs[aa].append((rows, info.shape, top))
-                                top = coef
-                                rows += 1
-                                continue
-                        if self.device_huffman_wide and len(blob) >= self.device_huffman_wide:
-                            # as above, and room for the workspace of the batch's K24 call
-                            at = -(-used // 16) * 16
-                            coef = (top - info.pixel_bytes - info.coef_bytes) // 128 * 128
-                            n = need = None
-                            if at < coef - ws_need:
-                                n, nsub = self._codec.jpeg_stream_pack_wide(blob, stage[at:coef - ws_need],
-                                                                            info.scale)[1:]
-                            if n is not None:  # 16: the workspace starts at a 16-byte boundary
-                                need = 16 + hip.jpeg_huffman_wide_workspace([j[6] for j in wide_jobs] + [nsub])
-                            if n is not None and at + n <= coef - need:
-                                used = at + n
-                                ws_need = need
-                                top -= info.pixel_bytes
-                                wide_jobs.append((at, coef, rows, blob, aa, len(plan), nsub, info.scale))
-                                jpeg_jobs.append((coef, info, top))
-                                dev_jobs[aa].append((rows, info.shape, top))
-                                top = coef
-                                rows += 1
-                                continue
-                        coef = -(-used // 128) * 128
-                        if coef + info.coef_bytes + info.pixel_bytes <= top - ws_need:
-                            self._codec.jpeg_entropy_decode(blob, stage[coef:coef + info.coef_bytes], info.scale)
-                            used = coef + info.coef_bytes
-                            top -= info.pixel_bytes
-                            jpeg_jobs.append((coef, info, top))
-                            dev_jobs[aa].append((rows, info.shape, top))
-                            rows += 1
+                        if stage.add_jpeg(blob, info, aa, len(plan)) is not None:
                             continue
                         item = self._codec.jpeg_decode(blob, info.scale)
-                    h, w, c = item.shape
-                    if 1 <= h <= hip.RESIZE_MAX_DIM and 1 <= w <= hip.RESIZE_MAX_DIM and c in (1, 3) \
-                            and used + item.size <= top - ws_need:
-                        stage[used:used + item.size] = item.reshape(-1)
-                        dev_jobs[aa].append((rows, item.shape, used))
-                        used += item.size
-                    else:
-                        host_jobs.append((rows, item, aa))
-                    rows += 1
+                    stage.add_raw(item, aa)
             except Exception as e:  # noqa: BLE001 - an undecodable blob fails its own request
-                rows, used, top = mark[:3]
-                ws_need = mark[-1]
-                for jobs, n in zip((dev_jobs[False], dev_jobs[True], jpeg_jobs, host_jobs, huff_jobs, wide_jobs),
-                                   mark[3:-1]):
-                    del jobs[n:]
+                stage.rollback(mark)
                 plan.append(e)
                 continue
-            plan.append((mark[0], rows - mark[0]))
+            plan.append((mark[0], stage.rows - mark[0]))
+        rows = stage.rows
         if rows == 0:
             return plan
         torch = self.torch
@@ -749,55 +666,43 @@ class PreprocessInception(Model):
             out = torch.empty((rows, self.C, self.H, self.W), device=stream.device, dtype=torch.float32)
             base = out.data_ptr()
             src = slot["stage_dev"].data_ptr()
-            if used:
-                hip.memcpy_async(src, slot["stage_host"], used, sh)
-            status = None
-            if huff_jobs:
-                status = torch.empty(len(huff_jobs), device=stream.device, dtype=torch.int32)
-                hip.jpeg_huffman([src + at for at, *_ in huff_jobs], [src + coef for _, coef, *_ in huff_jobs],
-                                 status.data_ptr(), stream=sh)
-            wide_status = None
-            if wide_jobs:
-                wide_status = torch.empty(len(wide_jobs), device=stream.device, dtype=torch.int32)
-                hip.jpeg_huffman_wide([src + j[0] for j in wide_jobs], [src + j[1] for j in wide_jobs],
-                                      [j[6] for j in wide_jobs], wide_status.data_ptr(),
-                                      src + (top - ws_need + 15) // 16 * 16, ws_need - 16, stream=sh)
-            if jpeg_jobs:
-                hip.jpeg_decode([src + coef for coef, _, _ in jpeg_jobs], [info for _, info, _ in jpeg_jobs],
-                                [src + pix for _, _, pix in jpeg_jobs], stream=sh)
-            for aa, jobs in dev_jobs.items():
+            if stage.used:
+                hip.memcpy_async(src, slot["stage_host"], stage.used, sh)
+            ran = jpeg_stage.launch_decode(
+                hip, stage.jpegs, src, src, src + stage.workspace, stage.ws_need - 16,
+                lambda n: torch.empty(n, device=stream.device, dtype=torch.int32), sh)
+            staged = sorted(stage.jpegs + [j for j in stage.raws if j.pix is not None], key=lambda j: j.row)
+            for aa in (False, True):
+                jobs = [j for j in staged if j.antialias == aa]
                 if jobs:
-                    hip.resize_pack([src + off for _, _, off in jobs], [shape for _, shape, _ in jobs],
-                                    [base + row * img_bytes for row, _, _ in jobs], "FP32", "NCHW",
+                    hip.resize_pack([src + j.pix for j in jobs], [j.shape for j in jobs],
+                                    [base + j.row * img_bytes for j in jobs], "FP32", "NCHW",
                                     self.C, self.H, self.W, scale=[1.0 / 127.5] * 3, bias=[-1.0] * 3,
                                     stream=sh, antialias=aa)
-            for row, img, aa in host_jobs:
-                out[row].copy_(torch.from_numpy(inception_preprocess(img, self.H, self.W, "NCHW", antialias=aa)))
+            for j in stage.raws:
+                if j.pix is None:
+                    out[j.row].copy_(torch.from_numpy(inception_preprocess(j.image, self.H, self.W, "NCHW",
+                                                                           antialias=j.antialias)))
             want_host = any(not isinstance(p, Exception) and not getattr(r, "accepts_device_outputs", False)
                             for r, p in zip(requests, plan))
             host_all = out.cpu().numpy() if want_host else None  # synchronises the stream
             hip.stream_synchronize(sh)
-            if status is not None or wide_status is not None:
-                # an image K23 or K24 gave up on: the host decodes it into its row, or its request fails
-                redo = []
-                if status is not None:
-                    redo += [job + (0, 1) for job, st in zip(huff_jobs, self._read_status(status)) if st]
-                if wide_status is not None:
-                    redo += [job for job, st in zip(wide_jobs, self._read_status(wide_status)) if st]
-                for _, _, row, blob, aa, req, _, scale in redo:
-                    if isinstance(plan[req], Exception):
-                        continue
-                    try:
-                        img = inception_preprocess(self._codec.jpeg_decode(blob, scale), self.H, self.W, "NCHW",
-                                                   antialias=aa)
-                    except Exception as e:  # noqa: BLE001 - the host decoder's error fails this request alone
-                        plan[req] = e
-                        continue
-                    out[row].copy_(torch.from_numpy(img))
-                    if host_all is not None:
-                        host_all[row] = img
-                if redo:
-                    hip.stream_synchronize(sh)
+            # an image K23 or K24 gave up on: the host decodes it into its row, or its request fails
+            redo = [j for jobs, status in ran for j, st in zip(jobs, self._read_status(status)) if st]
+            for j in redo:
+                if isinstance(plan[j.request], Exception):
+                    continue
+                try:
+                    img = inception_preprocess(self._codec.jpeg_decode(j.blob, j.info.scale), self.H, self.W, "NCHW",
+                                               antialias=j.antialias)
+                except Exception as e:  # noqa: BLE001 - the host decoder's error fails this request alone
+                    plan[j.request] = e
+                    continue
+                out[j.row].copy_(torch.from_numpy(img))
+                if host_all is not None:
+                    host_all[j.row] = img
+            if redo:
+                hip.stream_synchronize(sh)
         res = []
         for r, p in zip(requests, plan):
             if isinstance(p, Exception):

@@ -7,7 +7,6 @@ numpy only.  Decodes binary PPM (P6) / PGM (P5), a raw ``TCIMG`` container
 baseline JPEG through the host decoder of libtcamd_host.so (csrc/host/jpeg.cc).
 """
 
-import os
 import struct
 
 import numpy as np
@@ -63,19 +62,6 @@ def check_jpeg_scale(value, auto=True):
     if isinstance(value, bool) or not isinstance(value, (int, np.integer)) or int(value) not in allowed:
         raise ValueError("jpeg_scale must be one of %s, not %r" % (", ".join(str(a) for a in allowed), value))
     return int(value)
-
-
-def _jpeg_parse_scaled(blob, jpeg_scale, h_out, w_out):
-    """The parse of a JPEG blob at ``jpeg_scale``; 0 picks the scale for the target."""
-    codec = _jpeg_codec()
-    if jpeg_scale == 1:
-        return codec.jpeg_parse(blob)
-    if jpeg_scale == 0:
-        full = codec.jpeg_parse(blob)
-        jpeg_scale = jpeg_auto_scale(full.h, full.w, h_out, w_out)
-        if jpeg_scale == 1:
-            return full
-    return codec.jpeg_parse(blob, jpeg_scale)
 
 
 def decode_image(blob, jpeg_scale=1):
@@ -263,13 +249,6 @@ def preprocess_batch_device(resized, scaling="INCEPTION", fmt="NCHW", dtype="FP3
     return dst.cpu().numpy()
 
 
-def device_huffman_wide_knob():
-    """``TCAMD_DEVICE_HUFFMAN_WIDE``: the smallest JPEG blob, in bytes, whose
-    Huffman stage the K24 ``jpeg_huffman_wide`` kernels take; 0 (the default)
-    is off, 1 is every JPEG."""
-    return max(0, int(os.environ.get("TCAMD_DEVICE_HUFFMAN_WIDE", "0") or 0))
-
-
 def preprocess_raw_batch_device(images, c, h, w, scaling="INCEPTION", fmt="NCHW", dtype="FP32", device=0,
                                 antialias=False, device_huffman=None, jpeg_scale=1, device_huffman_wide=None):
     """``preprocess`` of a batch of decoded uint8 HWC images of any sizes on
@@ -279,38 +258,37 @@ def preprocess_raw_batch_device(images, c, h, w, scaling="INCEPTION", fmt="NCHW"
     scale, convert and pack them, and the [n, C, H, W] (or [n, H, W, C]) batch
     comes back as numpy.  ``antialias`` runs K21 ``resize_pack_aa`` (the
     device form of :func:`resize_area`) instead of K20.  An element may also be
-    the ``bytes`` of a baseline JPEG file: the host only Huffman-decodes it
-    into the same upload, and K22 ``jpeg_decode`` turns the coefficients into
-    pixels in a device buffer that K20 / K21 read.  With ``device_huffman``
-    (default: ``TCAMD_DEVICE_HUFFMAN=1`` in the environment) the host only
-    packs a JPEG's scan (``HostCodec.jpeg_stream_pack``) into the upload and K23
-    ``jpeg_huffman`` decodes it on the device; a blob the pack declines takes
-    the host's entropy decoder, and if K23 leaves a non-zero status word the
-    whole batch is done again with the host's entropy decoder, which gives the
-    answer or raises the error.  ``jpeg_scale`` 2, 4 or 8 decodes the JPEGs at
-    that fraction of their size (the host stores, and the upload carries, only
-    the coefficients the reduced transform uses), 0 picks
-    :func:`jpeg_auto_scale` per JPEG for the ``h x w`` target; a JPEG decoded
-    at a reduced size never takes K23.  ``device_huffman_wide`` (default:
-    ``TCAMD_DEVICE_HUFFMAN_WIDE`` in the environment; 0 is off) is the smallest
-    JPEG blob, in bytes, that the K24 ``jpeg_huffman_wide`` kernels decode,
-    at any scale and up to 32 MiB of scan, when K23 did not take it: the host
-    packs its scan (``HostCodec.jpeg_stream_pack_wide``) and one
-    ``hip.jpeg_huffman_wide`` call per batch writes the compact coefficient
-    buffers ahead of K22; the fallbacks are K23's.  Returns None when the
-    datatype has no device path (integer models)."""
+    the ``bytes`` of a baseline JPEG file, which takes the first route of
+    ``utils.jpeg_stage`` that the knobs allow: with ``device_huffman`` (default:
+    ``TCAMD_DEVICE_HUFFMAN`` in the environment) K23, with
+    ``device_huffman_wide`` (default: ``TCAMD_DEVICE_HUFFMAN_WIDE`` in the
+    environment; the smallest blob in bytes, 0 is off) K24, and otherwise the
+    host's entropy decoder, straight into the same upload.  K22 ``jpeg_decode``
+    turns the coefficients into pixels in a device buffer that K20 / K21 read.
+    If K23 or K24 leaves a non-zero status word the whole batch is done again
+    with the host's entropy decoder, which gives the answer or raises the
+    error.  ``jpeg_scale`` 2, 4 or 8 decodes the JPEGs at that fraction of
+    their size (the host stores, and the upload carries, only the coefficients
+    the reduced transform uses), 0 picks :func:`jpeg_auto_scale` per JPEG for
+    the ``h x w`` target.  Returns None when the datatype has no device path
+    (integer models)."""
     if dtype not in _DEVICE_DTYPES:
         return None
     import torch
 
-    from triton_client_amd.ops import hip
+    from triton_client_amd.ops import hip, host_codec
+    from triton_client_amd.utils import jpeg_stage
 
     jpeg_scale = check_jpeg_scale(jpeg_scale)
+    if device_huffman is None:
+        device_huffman = jpeg_stage.device_huffman_knob()
+    if device_huffman_wide is None:
+        device_huffman_wide = jpeg_stage.device_huffman_wide_knob()
     items = []  # a uint8 HWC array, or (blob, parse) of a JPEG
     for im in images:
         if isinstance(im, (bytes, bytearray, memoryview)):
             blob = bytes(im)
-            items.append((blob, _jpeg_parse_scaled(blob, jpeg_scale, h, w)))
+            items.append((blob, jpeg_stage.parse_at_scale(_jpeg_codec(), blob, jpeg_scale, h, w)))
             continue
         im = np.ascontiguousarray(im, dtype=np.uint8)
         items.append(im[:, :, None] if im.ndim == 2 else im)
@@ -318,107 +296,62 @@ def preprocess_raw_batch_device(images, c, h, w, scaling="INCEPTION", fmt="NCHW"
            for im in items if not isinstance(im, tuple)):
         return None
     dev = torch.device("cuda", device)
-    from triton_client_amd.ops import host_codec
-
-    if device_huffman is None:
-        device_huffman = os.environ.get("TCAMD_DEVICE_HUFFMAN", "0") == "1"
-    if device_huffman_wide is None:
-        device_huffman_wide = device_huffman_wide_knob()
-    # the upload: arrays as they are, JPEG coefficient buffers at 128-byte boundaries, packed JPEG
-    # streams (device Huffman) at 16-byte boundaries
-    offs, shapes, up, pix = [], [], 0, 0
-    packed = {}  # item index -> its stream buffer (K23)
-    wide = {}  # item index -> (its wide stream buffer, its subsequences) (K24)
-    for k, im in enumerate(items):
-        if isinstance(im, tuple) and device_huffman and im[1].scale == 1:
-            buf = host_codec.aligned_buffer(_jpeg_codec().jpeg_stream_bound(len(im[0])))
-            n = _jpeg_codec().jpeg_stream_pack(im[0], buf)[1]
-            if n is not None:
-                packed[k] = buf[:n]
-                up = -(-up // 16) * 16
-                offs.append(up)
-                up += n
-                pix += im[1].pixel_bytes
-                shapes.append(im[1].shape)
-                continue
-        if isinstance(im, tuple) and device_huffman_wide and len(im[0]) >= device_huffman_wide:
-            buf = host_codec.aligned_buffer(_jpeg_codec().jpeg_stream_bound_wide(len(im[0])))
-            _, n, nsub = _jpeg_codec().jpeg_stream_pack_wide(im[0], buf, im[1].scale)
-            if n is not None:
-                wide[k] = (buf[:n], nsub)
-                up = -(-up // 16) * 16
-                offs.append(up)
-                up += n
-                pix += im[1].pixel_bytes
-                shapes.append(im[1].shape)
-                continue
-        if isinstance(im, tuple):
-            up = -(-up // 128) * 128
-            offs.append(up)
-            up += im[1].coef_bytes
-            pix += im[1].pixel_bytes
-            shapes.append(im[1].shape)
-        else:
-            offs.append(up)
+    # The upload (``up`` bytes): arrays as they are, host-decoded JPEG coefficient buffers at 128-byte
+    # boundaries, packed JPEG streams at 16-byte boundaries.  In a second allocation, on the device only
+    # (``only`` bytes): the coefficient buffers K23 / K24 write, at 128-byte boundaries, and the pixels K22 writes.
+    codec = _jpeg_codec() if any(isinstance(im, tuple) for im in items) else None
+    raws, jobs, up, only = [], [], 0, 0
+    packs = {}  # row -> the stream its pack wrote
+    for row, im in enumerate(items):
+        if not isinstance(im, tuple):
+            raws.append(jpeg_stage.RawImage(row, im, up, antialias))
             up += im.size
-            shapes.append(im.shape)
-    raw = np.empty(up, dtype=np.uint8)
-    for k, (im, o) in enumerate(zip(items, offs)):
-        if k in packed:
-            raw[o:o + packed[k].size] = packed[k]
-        elif k in wide:
-            raw[o:o + wide[k][0].size] = wide[k][0]
-        elif isinstance(im, tuple):
-            _jpeg_codec().jpeg_entropy_decode(im[0], raw[o:o + im[1].coef_bytes], im[1].scale)
+            continue
+        blob, info = im
+        room = None
+        if device_huffman or device_huffman_wide:
+            room = host_codec.aligned_buffer(max(codec.jpeg_stream_bound(len(blob)),
+                                                 codec.jpeg_stream_bound_wide(len(blob))))
+        packed = jpeg_stage.pack_stream(codec, blob, info, room, device_huffman, device_huffman_wide)
+        if packed is not None:
+            route, n, nsub = packed
+            packs[row] = room[:n]
+            at = -(-up // 16) * 16
+            up = at + n
+            coef = -(-only // 128) * 128
+            only = coef + info.coef_bytes
         else:
-            raw[o:o + im.size] = im.reshape(-1)
+            route, nsub, at = jpeg_stage.HOST, 0, None
+            coef = -(-up // 128) * 128
+            up = coef + info.coef_bytes
+        jobs.append(jpeg_stage.JpegJob(route, at, coef, only, info, nsub, row, blob, antialias, 0))
+        only += info.pixel_bytes
+    raw = np.empty(up, dtype=np.uint8)
+    for r in raws:
+        raw[r.pix:r.pix + r.image.size] = r.image.reshape(-1)
+    for j in jobs:
+        if j.route == jpeg_stage.HOST:
+            codec.jpeg_entropy_decode(j.blob, raw[j.coef:j.coef + j.info.coef_bytes], j.info.scale)
+        else:
+            raw[j.stream:j.stream + packs[j.row].size] = packs[j.row]
     src = torch.from_numpy(raw).to(dev, non_blocking=False)
     stream = torch.cuda.current_stream(dev).cuda_stream
-    srcs = [src.data_ptr() + o for o in offs]
-    status = None
-    if packed:
-        # K23: the streams -> coefficient buffers that exist on the device only
-        at = [0]
-        for k in packed:
-            at.append(at[-1] + -(-items[k][1].coef_bytes // 128) * 128)
-        coefs = torch.empty(at[-1], device=dev, dtype=torch.uint8)
-        status = torch.empty(len(packed), device=dev, dtype=torch.int32)
-        hip.jpeg_huffman([srcs[k] for k in packed], [coefs.data_ptr() + a for a in at[:-1]], status.data_ptr(),
-                         stream=stream)
-        for k, a in zip(packed, at):
-            srcs[k] = coefs.data_ptr() + a
-    wide_status = None
-    if wide:
-        # K24: the same, with a workspace
-        at = [0]
-        for k in wide:
-            at.append(at[-1] + -(-items[k][1].coef_bytes // 128) * 128)
-        wide_coefs = torch.empty(at[-1], device=dev, dtype=torch.uint8)
-        wide_status = torch.empty(len(wide), device=dev, dtype=torch.int32)
-        nsubs = [nsub for _, nsub in wide.values()]
-        need = hip.jpeg_huffman_wide_workspace(nsubs)
-        workspace = torch.empty(need, device=dev, dtype=torch.uint8)
-        hip.jpeg_huffman_wide([srcs[k] for k in wide], [wide_coefs.data_ptr() + a for a in at[:-1]], nsubs,
-                              wide_status.data_ptr(), workspace.data_ptr(), need, stream=stream)
-        for k, a in zip(wide, at):
-            srcs[k] = wide_coefs.data_ptr() + a
-    if pix:
-        decoded = torch.empty(pix, device=dev, dtype=torch.uint8)
-        jobs, at = [], decoded.data_ptr()
-        for k, im in enumerate(items):
-            if isinstance(im, tuple):
-                jobs.append((srcs[k], im[1], at))
-                srcs[k] = at
-                at += im[1].pixel_bytes
-        hip.jpeg_decode([j[0] for j in jobs], [j[1] for j in jobs], [j[2] for j in jobs], stream=stream)
+    scratch = torch.empty(only, device=dev, dtype=torch.uint8)
+    nsubs = [j.nsub for j in jobs if j.route == jpeg_stage.K24]
+    need = hip.jpeg_huffman_wide_workspace(nsubs) if nsubs else 0
+    workspace = torch.empty(need, device=dev, dtype=torch.uint8)
+    ran = jpeg_stage.launch_decode(hip, jobs, src.data_ptr(), scratch.data_ptr(), workspace.data_ptr(), need,
+                                   lambda n: torch.empty(n, device=dev, dtype=torch.int32), stream)
+    staged = sorted(jobs + raws, key=lambda j: j.row)
     shape = (len(items), c, h, w) if fmt == "NCHW" else (len(items), h, w, c)
     dst = torch.empty(shape, device=dev, dtype=torch.float32 if dtype == "FP32" else torch.float16)
     scale, bias = _SCALE_BIAS[scaling](c)
     per = c * h * w * dst.element_size()
-    hip.resize_pack(srcs, shapes, [dst.data_ptr() + i * per for i in range(len(items))], dtype, fmt, c, h, w,
+    hip.resize_pack([(scratch if isinstance(j, jpeg_stage.JpegJob) else src).data_ptr() + j.pix for j in staged],
+                    [j.shape for j in staged], [dst.data_ptr() + j.row * per for j in staged], dtype, fmt, c, h, w,
                     scale=scale, bias=bias, stream=stream, antialias=antialias)
     out = dst.cpu().numpy()
-    if any(st is not None and st.cpu().numpy().any() for st in (status, wide_status)):
+    if any(status.cpu().numpy().any() for _, status in ran):
         return preprocess_raw_batch_device(images, c, h, w, scaling, fmt, dtype, device, antialias,
                                            device_huffman=False, jpeg_scale=jpeg_scale, device_huffman_wide=0)
     return out

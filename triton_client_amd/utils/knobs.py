@@ -90,10 +90,10 @@ KNOBS = [
     Knob("TCAMD_DEVICE_PREPROCESS", "python", 1, "server/gpu_models.py",
          "GPU preprocess_inception: K20 resize_pack on the device; 0 = the numpy step",
          "tests/test_preprocess_device_gpu.py::test_knob_off_is_the_numpy_step"),
-    Knob("TCAMD_DEVICE_HUFFMAN", "python", 0, "server/gpu_models.py, utils/image.py",
+    Knob("TCAMD_DEVICE_HUFFMAN", "python", 0, "utils/jpeg_stage.py",
          "JPEG: 1 = the host packs the scan and K23 jpeg_huffman decodes it on the device; 0 = host entropy decode",
          "tests/test_jpeg_huffman_gpu.py::test_the_knob_changes_the_route_and_not_one_bit_of_the_rows"),
-    Knob("TCAMD_DEVICE_HUFFMAN_WIDE", "python", 0, "server/gpu_models.py, utils/image.py",
+    Knob("TCAMD_DEVICE_HUFFMAN_WIDE", "python", 0, "utils/jpeg_stage.py",
          "JPEG: N > 0 = blobs of at least N bytes that K23 did not take are packed by the host and decoded by the "
          "K24 jpeg_huffman_wide kernels, at any jpeg_scale; 0 = off",
          "tests/test_jpeg_huffman_wide_gpu.py::test_the_wide_knob_changes_the_route_and_not_one_bit_of_the_rows"),

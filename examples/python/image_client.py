@@ -5,10 +5,11 @@ Reads model metadata/config to find the input layout, preprocesses images
 (NONE / INCEPTION / VGG scaling, NCHW or NHWC), sends batches over HTTP or
 gRPC (sync, async, or gRPC streaming) and prints the top-k classes returned
 by the server's classification extension.  Images are decoded with PIL when
-available, else with the framework's PPM/raw/JPEG decoder.  With
-``--device-resize`` a JPEG file is not decoded here at all: its bytes go to
-``preprocess_raw_batch_device``, which Huffman-decodes on the host and leaves
-the rest to the K22 jpeg_decode kernel.  ``--jpeg-scale`` decodes JPEG files in
+available, else with the framework's PPM/raw/JPEG/PNG decoder.  With
+``--device-resize`` a JPEG or PNG file is not decoded here at all: its bytes go
+to ``preprocess_raw_batch_device``, which Huffman-decodes a JPEG on the host and
+leaves the rest to the K22 jpeg_decode kernel, and inflates a PNG on the host
+and leaves the rest to the K25 png_unfilter kernel.  ``--jpeg-scale`` decodes JPEG files in
 the DCT domain at 1/2, 1/4 or 1/8 of their size (0: the largest of them that
 the model's input size does not have to upscale), on the host path with the
 framework's decoder and with ``--device-resize`` on the GPU.
@@ -54,9 +55,10 @@ def load_image(path, jpeg_scale=1, h=0, w=0):
 
 
 def load_for_device(path):
-    """A JPEG file's bytes as they are (the device decodes them), any other image decoded."""
+    """A JPEG or PNG file's bytes as they are (the device decodes them), any other image decoded."""
     with open(path, "rb") as f:
-        if f.read(2) == b"\xff\xd8":
+        head = f.read(8)
+        if head[:2] == b"\xff\xd8" or head == b"\x89PNG\r\n\x1a\n":
             f.seek(0)
             return f.read()
     return load_image(path)

@@ -5,6 +5,8 @@
     python tools/ensemble_bench.py --antialias    # either mode with the antialiased resize (K21 resize_pack_aa)
     python tools/ensemble_bench.py --jpeg         # served: the committed 640x480 JPEG fixture instead of a TCIMG blob
     python tools/ensemble_bench.py --kernel --jpeg  # K22 jpeg_decode, K23 jpeg_huffman alone: 8 copies of that fixture
+    python tools/ensemble_bench.py --png          # served: that fixture's pixels as a PNG, TCAMD_DEVICE_PNG 1 against 0
+    python tools/ensemble_bench.py --kernel --png # K25 png_unfilter alone, next to the host's unfilter and inflate
 
 The served mode starts the bench server (densenet_onnx, preprocess_inception
 and the ensemble, 2 instances) as a child process, keeps ``--concurrency``
@@ -29,6 +31,19 @@ compact coefficient buffer (``--kernel --jpeg``; the K23 line is left out: K23
 writes the full layout only).  ``--jpeg-file PATH`` takes another baseline JPEG
 than the fixture, a large photo for instance.  ``TCAMD_DEVICE_HUFFMAN=1`` in the environment of a served run makes
 the server pack the scan and run K23 instead of the host's entropy decode.
+
+``--png`` is the counterpart of ``--jpeg``: the pixels of that fixture (its host
+decode, 640 x 480 RGB) written as a PNG by this tool, with ``--png-filter``
+choosing the filter of every row (``adaptive``, the default, picks per row the
+filter with the smallest sum of absolute differences, as encoders do), or
+``--png-file PATH`` for a file of another writer.  Served, it starts TWO
+servers, ``TCAMD_DEVICE_PNG=1`` and ``=0``, and for ``--reps`` rounds and each
+concurrency loads them in turn (only one at a time), each with the PNG blob and
+with the TCIMG blob of the same pixels: one JSON line per round, concurrency,
+arm and encoding, so that the arms alternate within one session on one box.
+``--kernel --png`` times K25 ``png_unfilter`` on one image and on ``--images``
+copies (HIP events around the launch), next to the host's ``png_unfilter`` and
+``png_inflate`` on the same file.
 """
 
 import argparse
@@ -208,6 +223,160 @@ def jpeg_kernel_time(n, iters, scale=1, path=None):
                                                        round(float(np.mean(pack_ms)), 4)],
                       "host_entropy_decode_ms_min_mean": [round(float(np.min(host["entropy_decode"])), 3),
                                                           round(float(np.mean(host["entropy_decode"])), 3)]}))
+
+
+_PNG_FILTERS = ("none", "sub", "up", "average", "paeth")
+
+
+def write_png(img, how="adaptive"):
+    """An 8-bit RGB or grey PNG of the uint8 HWC array ``img``: filter type ``how`` on every row, or
+    per row the one of the five with the smallest sum of absolute (signed) differences."""
+    import struct
+    import zlib
+
+    import numpy as np
+
+    h, w, c = img.shape
+    raw = img.reshape(h, w * c).astype(np.int16)
+    left = np.concatenate([np.zeros((h, c), np.int16), raw[:, :-c]], axis=1)
+    up = np.concatenate([np.zeros((1, w * c), np.int16), raw[:-1]], axis=0)
+    upleft = np.concatenate([np.zeros((h, c), np.int16), up[:, :-c]], axis=1)
+    p = left + up - upleft
+    pa, pb, pc = np.abs(p - left), np.abs(p - up), np.abs(p - upleft)
+    paeth = np.where((pa <= pb) & (pa <= pc), left, np.where(pb <= pc, up, upleft))
+    cand = np.stack([(raw - pred) & 0xff for pred in (0 * raw, left, up, (left + up) >> 1, paeth)]).astype(np.uint8)
+    if how == "adaptive":
+        pick = np.abs(cand.view(np.int8).astype(np.int32)).sum(axis=2).argmin(axis=0)
+    else:
+        pick = np.full(h, _PNG_FILTERS.index(how))
+    rows = cand[pick, np.arange(h)]
+    filt = np.concatenate([pick[:, None].astype(np.uint8), rows], axis=1).tobytes()
+
+    def chunk(kind, data):
+        return struct.pack(">I", len(data)) + kind + data + struct.pack(">I", zlib.crc32(kind + data) & 0xffffffff)
+
+    return b"\x89PNG\r\n\x1a\n" + chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, 8, 2 if c == 3 else 0, 0, 0, 0)) \
+        + chunk(b"IDAT", zlib.compress(filt, 6)) + chunk(b"IEND", b"")
+
+
+def png_fixture(args):
+    """(the PNG blob, its pixels): ``--png-file``, or the JPEG fixture's host decode written by :func:`write_png`."""
+    from triton_client_amd.ops import host_codec
+
+    hc = host_codec.load()
+    if args.png_file:
+        with open(args.png_file, "rb") as f:
+            blob = f.read()
+    else:
+        blob = write_png(hc.jpeg_decode(jpeg_fixture()), args.png_filter)
+    return blob, hc.png_decode(blob)
+
+
+def _host_ms(fn, n=20):
+    fn()
+    ts = []
+    for _ in range(n):
+        t0 = time.perf_counter()
+        fn()
+        ts.append((time.perf_counter() - t0) * 1e3)
+    return ts
+
+
+def png_kernel_time(args):
+    import numpy as np
+    import torch
+
+    from triton_client_amd.ops import hip, host_codec
+
+    torch.cuda.set_device(0)
+    hc = host_codec.load()
+    blob, want = png_fixture(args)
+    info = hc.png_parse(blob)
+    staged = host_codec.aligned_buffer(info.stage_bytes)
+    inflate = _host_ms(lambda: hc.png_inflate(blob, staged))
+    unfilter = _host_ms(lambda: hc.png_unfilter(staged, info))
+    decode = _host_ms(lambda: hc.png_decode(blob))
+    n = max(1, args.images)
+    stride = -(-info.stage_bytes // 16) * 16
+    src = torch.from_numpy(np.concatenate([np.pad(staged, (0, stride - staged.size))] * n)).cuda()
+    dst = torch.zeros(n, info.pixel_bytes, device="cuda", dtype=torch.uint8)
+    s = torch.cuda.current_stream().cuda_stream
+    srcs = [src.data_ptr() + i * stride for i in range(n)]
+    dsts = [dst[i].data_ptr() for i in range(n)]
+    line = {"kernel": "K25 png_unfilter", "image": list(info.shape), "colour_type": info.ctype, "depth": info.depth,
+            "filter": "file" if args.png_file else args.png_filter, "png_bytes": len(blob),
+            "stage_bytes": int(info.stage_bytes), "pixel_bytes": int(info.pixel_bytes), "timed_launches": args.iters}
+    rows = np.frombuffer(staged[:info.filtered_bytes], dtype=np.uint8).reshape(info.h, -1)[:, 0]
+    line["rows_per_filter_type"] = [int((rows == f).sum()) for f in range(5)]
+    for m in sorted({1, n}):
+        def launch():
+            hip.png_unfilter(srcs[:m], [info] * m, dsts[:m], stream=s)
+
+        for _ in range(5):
+            launch()
+        torch.cuda.synchronize()
+        times = []
+        for _ in range(args.iters):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            launch()
+            b.record()
+            b.synchronize()
+            times.append(a.elapsed_time(b) * 1e3)
+        line["images_%d_us_min_mean_max" % m] = [round(float(f(times)), 1) for f in (np.min, np.mean, np.max)]
+    line["equals_host_decode"] = bool((dst.cpu().numpy().reshape((n,) + want.shape) == want).all())
+    for what, ts in (("host_png_inflate", inflate), ("host_png_unfilter", unfilter), ("host_png_decode", decode)):
+        line[what + "_ms_min_mean"] = [round(float(np.min(ts)), 3), round(float(np.mean(ts)), 3)]
+    print(json.dumps(line), flush=True)
+
+
+def served_png(args):
+    """Two servers, TCAMD_DEVICE_PNG=1 and =0, loaded in turn with the PNG and with its TCIMG twin."""
+    import numpy as np
+
+    import tritonclient.grpc as grpcclient
+    from triton_client_amd.perf.harness import ServerProcess
+    from triton_client_amd.utils.image import encode_raw
+
+    blob, pixels = png_fixture(args)
+    blobs = {"PNG": blob, "TCIMG": encode_raw(pixels)}
+    log = os.path.abspath(args.server_log) if args.server_log else None
+    if log:
+        os.makedirs(os.path.dirname(log), exist_ok=True)
+    servers, clients = {}, {}
+    try:
+        for knob in ("1", "0"):
+            servers[knob] = ServerProcess(device=0, models="densenet_onnx,preprocess_inception,preprocess_inception_ensemble",
+                                          log_path=log and "%s.png%s" % (log, knob), extra_args=["--instance-count", "2"],
+                                          env={"TCAMD_DEVICE_PNG": knob})
+        first = {}
+        for knob, srv in servers.items():
+            srv.wait_ready(timeout=900, model="preprocess_inception_ensemble")
+            clients[knob] = grpcclient.InferenceServerClient(srv.grpc_url)
+        inputs = {}
+        for enc, b in blobs.items():
+            inputs[enc] = grpcclient.InferInput("INPUT", [1, 1], "BYTES")
+            inputs[enc].set_data_from_numpy(np.array([b], dtype=np.object_).reshape(1, 1))
+        params = {"antialias": True} if args.antialias else None
+        for knob, c in clients.items():
+            for enc in blobs:
+                first[knob, enc] = c.infer("preprocess_inception_ensemble", [inputs[enc]], parameters=params).as_numpy("OUTPUT")
+        same = all(np.array_equal(v, first["1", "PNG"]) for v in first.values())
+        for rep_ in range(args.reps):
+            for conc in args.concurrency:
+                for knob in ("1", "0"):
+                    for enc in ("PNG", "TCIMG"):
+                        res = closed_loop(clients[knob], grpcclient, inputs[enc], conc, args.warmup, args.seconds, params)
+                        res.update(round=rep_, device_png=int(knob), encoding=enc, image=list(pixels.shape),
+                                   blob_bytes=len(blobs[enc]), antialias=args.antialias,
+                                   filter="file" if args.png_file else args.png_filter,
+                                   all_four_first_answers_equal=bool(same))
+                        print(json.dumps(res), flush=True)
+        for c in clients.values():
+            c.close()
+    finally:
+        for srv in servers.values():
+            srv.stop()
 
 
 def jpeg_wide_line(hc, hip, blob, info, scale, coef, host, n, iters):
@@ -395,6 +564,13 @@ def main():
     ap.add_argument("--huffman-wide", type=int, default=None, metavar="N",
                     help="served: start the server with TCAMD_DEVICE_HUFFMAN_WIDE=N (JPEG blobs of at least N bytes "
                          "take the K24 jpeg_huffman_wide kernels; 0 = off)")
+    ap.add_argument("--png", action="store_true",
+                    help="the JPEG fixture's pixels as a PNG: served by two servers, TCAMD_DEVICE_PNG=1 and =0, in turn, "
+                         "next to the TCIMG of the same pixels; K25 alone (--kernel)")
+    ap.add_argument("--png-filter", choices=("adaptive",) + _PNG_FILTERS, default="adaptive",
+                    help="--png: the filter type of every row of the PNG this tool writes")
+    ap.add_argument("--png-file", default="", metavar="PATH", help="--png: this PNG file instead")
+    ap.add_argument("--reps", type=int, default=3, help="--png, served: rounds over the concurrencies and arms")
     ap.add_argument("--concurrency", type=int, nargs="+", default=[1, 8])
     ap.add_argument("--height", type=int, default=480)
     ap.add_argument("--width", type=int, default=640)
@@ -404,7 +580,9 @@ def main():
     ap.add_argument("--iters", type=int, default=50, help="--kernel: timed launches (after 10 warm-up)")
     ap.add_argument("--server-log", default="", metavar="PATH", help="keep the server's log in this file")
     args = ap.parse_args()
-    if args.kernel and args.jpeg:
+    if args.png:
+        (png_kernel_time if args.kernel else served_png)(args)
+    elif args.kernel and args.jpeg:
         jpeg_kernel_time(args.images, args.iters, 1 if args.jpeg_scale is None else args.jpeg_scale, args.jpeg_file)
     elif args.kernel:
         kernel_time(args.images, args.height, args.width, args.iters, args.antialias)

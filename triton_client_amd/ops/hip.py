@@ -10,6 +10,7 @@ events, peer access.  Kernels (csrc/kernels/*.hip, gfx950):
 * :func:`jpeg_decode`     K22 dequantise + IDCT + chroma upsample + YCbCr->RGB of entropy-decoded JPEG coefficients
 * :func:`jpeg_huffman`    K23 Huffman decode of packed JPEG scans into the coefficients K22 reads
 * :func:`jpeg_huffman_wide`  K24 the same across workgroups: scans up to 32 MiB, the compact buffer of any scale
+* :func:`png_unfilter`    K25 PNG unfilter + palette / depth / alpha conversion of inflated scanlines
 * :func:`batched_copy`    K7 one-launch gather/concat/scatter of byte ranges
 * :func:`pack_bytes`      K2 BYTES serialisation (LDS block scan + scatter)
 * :func:`index_bytes`     K3 BYTES index walk through an LDS window
@@ -157,6 +158,15 @@ _SIGS = {
         [
             ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_uint32),
             ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, ctypes.c_uint32, ctypes.c_void_p,
+        ],
+        ctypes.c_int,
+    ),
+    "tcamd_png_unfilter_geometry": ([ctypes.POINTER(ctypes.c_int32)], None),
+    "tcamd_png_unfilter": (
+        [
+            ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32),
+            ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32),
+            ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.c_void_p,
         ],
         ctypes.c_int,
     ),
@@ -844,6 +854,39 @@ def jpeg_huffman_wide(streams, coefs, nsubs, status, workspace, workspace_bytes,
     k = (ctypes.c_uint32 * max(n, 1))(*[int(v) for v in nsubs])
     _check(_load().tcamd_jpeg_huffman_wide(s, c, k, _vp(status), _vp(workspace), int(workspace_bytes), n,
                                            int(chunk_subs), _vp(stream)), "jpeg_huffman_wide")
+
+
+def png_unfilter_geometry():
+    """The decomposition of K25 ``png_unfilter``, from the library:
+    ``(rows per wave, rows per pass, units per column chunk)``, a unit being
+    ``bpp`` bytes of a scanline."""
+    g = (ctypes.c_int32 * 3)()
+    _load().tcamd_png_unfilter_geometry(g)
+    return int(g[0]), int(g[1]), int(g[2])
+
+
+def png_unfilter(srcs, infos, dsts, stream=None):
+    """K25: the device half of a PNG decode, unfilter and sample conversion.
+    ``srcs[i]`` is a device pointer, 16-byte aligned, to ``stage_bytes`` of
+    image i: the staged bytes ``ops.host_codec.HostCodec.png_inflate`` wrote
+    (filtered scanlines, the palette of colour type 3) and, for an image of more
+    rows than a pass, the scanline of scratch behind them, which the kernel
+    writes; ``infos[i]`` is its parse, anything with ``h, w, ctype, depth,
+    interlace`` (``host_codec.PngInfo``); ``dsts[i]`` is a device pointer of any
+    alignment that receives its ``h * w * channels`` uint8 HWC pixels, bitwise
+    those of ``HostCodec.png_unfilter``.  Images of mixed size, colour type and
+    depth share a launch, one workgroup each, 64 per launch.  An interlaced
+    parse, a side outside [1, :data:`RESIZE_MAX_DIM`], a colour type / depth
+    pair PNG does not have, or a null or misaligned source raises
+    (hipErrorInvalidValue) without a launch."""
+    n = len(srcs)
+    if len(infos) != n or len(dsts) != n:
+        raise ValueError("png_unfilter: srcs, infos and dsts must have one entry per image")
+    s = (ctypes.c_void_p * max(n, 1))(*[int(p) for p in srcs])
+    d = (ctypes.c_void_p * max(n, 1))(*[int(p) for p in dsts])
+    cols = [(ctypes.c_int32 * max(n, 1))(*[int(getattr(i, f)) for i in infos])
+            for f in ("h", "w", "ctype", "depth", "interlace")]
+    _check(_load().tcamd_png_unfilter(s, *cols, n, d, _vp(stream)), "png_unfilter")
 
 
 def batched_copy(srcs, dsts, sizes, stream=None):

@@ -1,4 +1,4 @@
-"""ctypes binding of libtcamd_host.so (BYTES pack / scan and baseline JPEG on the host)."""
+"""ctypes binding of libtcamd_host.so (BYTES pack / scan, baseline JPEG and PNG on the host)."""
 import ctypes
 import os
 
@@ -26,6 +26,29 @@ class JpegInfo(ctypes.Structure):
     @property
     def pixel_bytes(self):
         return self.h * self.w * self.ncomp
+
+
+class PngInfo(ctypes.Structure):
+    """TcamdPngInfo of csrc/host/png.h: the IHDR fields, ``channels`` of the
+    uint8 output (1 or 3), the unfilter distance ``bpp``, ``row_bytes`` of a
+    scanline without its filter byte, ``filtered_bytes`` that the IDAT stream
+    inflates to, and the layout of the staged bytes K25 ``png_unfilter`` reads
+    (``stage_bytes`` in all): the scanlines, the palette of colour type 3 at
+    ``palette_off``, and for an image of more rows than a pass of K25 one
+    scanline of scratch at ``line_off`` (0 = absent)."""
+
+    _fields_ = [("h", ctypes.c_int32), ("w", ctypes.c_int32), ("depth", ctypes.c_int32), ("ctype", ctypes.c_int32),
+                ("interlace", ctypes.c_int32), ("channels", ctypes.c_int32), ("bpp", ctypes.c_int32),
+                ("row_bytes", ctypes.c_uint32), ("filtered_bytes", ctypes.c_uint64), ("pixel_bytes", ctypes.c_uint64),
+                ("palette_off", ctypes.c_uint64), ("line_off", ctypes.c_uint64), ("stage_bytes", ctypes.c_uint64)]
+
+    @property
+    def shape(self):
+        return (self.h, self.w, self.channels)
+
+
+PNG_SIGNATURE = b"\x89PNG\r\n\x1a\n"
+_PNG_KIND = {1: "unsupported PNG: ", 2: "malformed PNG: "}
 
 
 def aligned_buffer(nbytes, align=16):
@@ -85,6 +108,16 @@ class HostCodec:
         lib.tcamd_host_jpeg_huffman_wide_emulate.restype = ctypes.c_int
         lib.tcamd_host_jpeg_huffman_wide_workspace.argtypes = [ctypes.c_uint64, ctypes.c_uint64]
         lib.tcamd_host_jpeg_huffman_wide_workspace.restype = ctypes.c_uint64
+        lib.tcamd_host_png_parse.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(PngInfo), ctypes.c_char_p,
+                                             ctypes.c_int]
+        lib.tcamd_host_png_parse.restype = ctypes.c_int
+        for fn in (lib.tcamd_host_png_inflate, lib.tcamd_host_png_decode):
+            fn.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_char_p,
+                           ctypes.c_int]
+            fn.restype = ctypes.c_int
+        lib.tcamd_host_png_unfilter.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(PngInfo), ctypes.c_void_p,
+                                                ctypes.c_uint64]
+        lib.tcamd_host_png_unfilter.restype = ctypes.c_int
         lib.tcamd_host_pack_bytes.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]
         lib.tcamd_host_pack_bytes.restype = ctypes.c_int
         lib.tcamd_host_count_bytes.argtypes = [ctypes.c_void_p, ctypes.c_uint64]
@@ -259,6 +292,50 @@ class HostCodec:
         cs = int(chunk_subs) or 1024
         return int(self._lib.tcamd_host_jpeg_huffman_wide_workspace(sum(int(n) for n in nsubs),
                                                                     sum(-(-int(n) // cs) for n in nsubs)))
+
+    # -- PNG (csrc/host/png.cc) ----------------------------------------------------------
+    @staticmethod
+    def _png_check(rc, msg):
+        if rc:
+            raise ValueError(_PNG_KIND.get(rc, "PNG: ") + msg.value.decode())
+
+    def png_parse(self, blob):
+        """The :class:`PngInfo` of a PNG blob, from its chunk headers alone
+        (nothing is inflated); ``ValueError`` ("unsupported PNG: ..." /
+        "malformed PNG: ...") when it cannot be decoded."""
+        info = PngInfo()
+        msg = ctypes.create_string_buffer(96)
+        self._png_check(self._lib.tcamd_host_png_parse(blob, len(blob), ctypes.byref(info), msg, len(msg)), msg)
+        return info
+
+    def png_inflate(self, blob, out):
+        """Inflate the IDAT stream of a non-interlaced ``blob`` straight into
+        the uint8 array ``out`` (at least ``stage_bytes`` of its parse), with no
+        intermediate copy: the filtered scanlines, then for colour type 3 the
+        palette (256 x 3 bytes, zero past the end of PLTE) at the next 16-byte
+        boundary: the staged bytes ``ops.hip.png_unfilter`` reads.  Checks the
+        CRC of the IDAT chunks, the inflated length and the ``h`` filter-type
+        bytes."""
+        msg = ctypes.create_string_buffer(96)
+        self._png_check(self._lib.tcamd_host_png_inflate(blob, len(blob), out.ctypes.data, out.size, msg, len(msg)), msg)
+
+    def png_unfilter(self, staged, info):
+        """K25 ``png_unfilter`` on the host, bitwise: the staged bytes of
+        :meth:`png_inflate` (a uint8 array) -> uint8 [h, w, 1 or 3]."""
+        out = np.empty(info.shape, dtype=np.uint8)
+        staged = np.ascontiguousarray(staged, dtype=np.uint8)
+        if self._lib.tcamd_host_png_unfilter(staged.ctypes.data, staged.size, ctypes.byref(info), out.ctypes.data,
+                                             out.size):
+            raise ValueError("png_unfilter: the staged bytes and the parse do not belong together")
+        return out
+
+    def png_decode(self, blob):
+        """Blob -> uint8 [H, W, 1 or 3], entirely on the host, Adam7 included."""
+        info = self.png_parse(blob)
+        out = np.empty(info.shape, dtype=np.uint8)
+        msg = ctypes.create_string_buffer(96)
+        self._png_check(self._lib.tcamd_host_png_decode(blob, len(blob), out.ctypes.data, out.size, msg, len(msg)), msg)
+        return out
 
 
 _INSTANCE = None

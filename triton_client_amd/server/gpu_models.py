@@ -481,7 +481,7 @@ class DensenetOnnx(Model):
 
 class PreprocessInception(Model):
     """``preprocess_inception`` on the GPU: the same I/O contract as the CPU
-    model of that name (BYTES PPM / PGM / TCIMG / JPEG blobs in, INCEPTION-scaled
+    model of that name (BYTES PPM / PGM / TCIMG / JPEG / PNG blobs in, INCEPTION-scaled
     FP32 NCHW [3,224,224] out), which it replaces on a ``--gpu`` server.
 
     Per batch the host only parses each blob's header and copies its uint8
@@ -511,6 +511,16 @@ class PreprocessInception(Model):
     the stream synchronise) is decoded by the host, which fills its row or
     fails its request, and that request alone, with the host decoder's message.
 
+    A PNG blob that is not interlaced takes the same module's PNG route
+    (``TCAMD_DEVICE_PNG``, read at load; 1 by default): the host parses its
+    headers and inflates its IDAT stream straight into the pinned staging area,
+    the filtered scanlines go up in the batch's one copy, and K25
+    ``png_unfilter`` writes the pixels where K20 / K21 read them, after the JPEG
+    kernels and before the resize on the slot's stream.  An interlaced PNG, one
+    that does not fit, or any PNG with the knob at 0 is decoded by the host and
+    goes on as raw pixels; the rows are the same bit for bit.  A PNG that does
+    not decode fails its own request with the host decoder's message.
+
     The custom request parameter ``antialias`` (bool, default false) selects
     the antialiased resize for that request's images: the batch's device jobs
     are split by the flag into at most one K20 and one K21 ``resize_pack``
@@ -526,7 +536,7 @@ class PreprocessInception(Model):
     pixels (a 12-megapixel 4:2:0 photo needs about 1.7 MB at 1/8 instead of
     72 MB), and K22 decodes the images of all scales of a batch in the same
     ``jpeg_decode`` call.  The host fallbacks decode at the same scale, so
-    every route gives the same rows.  PPM / PGM / TCIMG blobs ignore the parameter;
+    every route gives the same rows.  PPM / PGM / TCIMG / PNG blobs ignore the parameter;
     any other value fails that request alone."""
 
     name = "preprocess_inception"
@@ -556,13 +566,14 @@ class PreprocessInception(Model):
         self.device_path = os.environ.get("TCAMD_DEVICE_PREPROCESS", "1") != "0"
         self.device_huffman = jpeg_stage.device_huffman_knob()
         self.device_huffman_wide = jpeg_stage.device_huffman_wide_knob()
+        self.device_png = jpeg_stage.device_png_knob()
         if not self.device_path:
             return
         import torch
 
         from triton_client_amd.ops import hip, host_codec
 
-        self._codec = host_codec.load()  # the JPEG entropy decoder
+        self._codec = host_codec.load()  # the JPEG entropy decoder and the PNG inflate
 
         if not torch.cuda.is_available():
             raise ServerError("preprocess_inception (GPU) requires a GPU")
@@ -609,13 +620,17 @@ class PreprocessInception(Model):
             return e
 
     def _open(self, blob, scale=1):
-        """A decoded image, or (blob, parse) of a JPEG whose decode is still to be routed;
-        ``scale`` is the request's ``jpeg_scale``, 0 for automatic."""
-        from triton_client_amd.utils.image import decode_image
+        """A decoded image, or (blob, parse) of a JPEG or a non-interlaced PNG whose decode is
+        still to be routed; ``scale`` is the request's ``jpeg_scale``, 0 for automatic."""
+        from triton_client_amd.utils.image import PNG_SIGNATURE, decode_image
 
         blob = bytes(blob)
         if blob[:2] == b"\xff\xd8":
             return blob, jpeg_stage.parse_at_scale(self._codec, blob, scale, self.H, self.W)
+        if self.device_png and blob[:8] == PNG_SIGNATURE:
+            info = self._codec.png_parse(blob)
+            if not info.interlace:
+                return blob, info
         return decode_image(blob)
 
     def _read_status(self, status):
@@ -632,7 +647,7 @@ class PreprocessInception(Model):
             self._release(i)
 
     def _execute(self, slot, requests):
-        from triton_client_amd.ops import hip
+        from triton_client_amd.ops import hip, host_codec
         from triton_client_amd.utils.image import inception_preprocess
 
         img_bytes = self.C * self.H * self.W * 4
@@ -647,9 +662,14 @@ class PreprocessInception(Model):
                 for item in [self._open(b, scale) for b in r.input("INPUT").numpy().reshape(-1)]:
                     if isinstance(item, tuple):
                         blob, info = item
-                        if stage.add_jpeg(blob, info, aa, len(plan)) is not None:
-                            continue
-                        item = self._codec.jpeg_decode(blob, info.scale)
+                        if isinstance(info, host_codec.PngInfo):
+                            if stage.add_png(blob, info, aa, len(plan)) is not None:
+                                continue
+                            item = self._codec.png_decode(blob)
+                        else:
+                            if stage.add_jpeg(blob, info, aa, len(plan)) is not None:
+                                continue
+                            item = self._codec.jpeg_decode(blob, info.scale)
                     stage.add_raw(item, aa)
             except Exception as e:  # noqa: BLE001 - an undecodable blob fails its own request
                 stage.rollback(mark)
@@ -670,8 +690,9 @@ class PreprocessInception(Model):
                 hip.memcpy_async(src, slot["stage_host"], stage.used, sh)
             ran = jpeg_stage.launch_decode(
                 hip, stage.jpegs, src, src, src + stage.workspace, stage.ws_need - 16,
-                lambda n: torch.empty(n, device=stream.device, dtype=torch.int32), sh)
-            staged = sorted(stage.jpegs + [j for j in stage.raws if j.pix is not None], key=lambda j: j.row)
+                lambda n: torch.empty(n, device=stream.device, dtype=torch.int32), sh, pngs=stage.pngs)
+            staged = sorted(stage.jpegs + stage.pngs + [j for j in stage.raws if j.pix is not None],
+                            key=lambda j: j.row)
             for aa in (False, True):
                 jobs = [j for j in staged if j.antialias == aa]
                 if jobs:

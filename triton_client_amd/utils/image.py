@@ -1,10 +1,12 @@
-"""Tiny image codec + classification preprocessing (no PIL/OpenCV on the box).
+"""Image decoding + classification preprocessing without an imaging library.
 
 Mirrors the preprocessing of reference src/python/examples/image_client.py:154-194
 (INCEPTION scaling ``x/127.5 - 1``, VGG mean subtraction, NCHW/NHWC) using
 numpy only.  Decodes binary PPM (P6) / PGM (P5), a raw ``TCIMG`` container
-(``b"TCIMG" + u16 H + u16 W + u8 C + HWC bytes``) used by the examples, and
-baseline JPEG through the host decoder of libtcamd_host.so (csrc/host/jpeg.cc).
+(``b"TCIMG" + u16 H + u16 W + u8 C + HWC bytes``) used by the examples, and,
+through the host decoders of libtcamd_host.so, baseline JPEG (csrc/host/jpeg.cc)
+and PNG of every standard colour type and bit depth, interlaced or not, to 8
+bits per sample without alpha (csrc/host/png.cc).
 """
 
 import struct
@@ -27,6 +29,7 @@ def encode_ppm(img):
 
 
 JPEG_SOI = b"\xff\xd8"
+PNG_SIGNATURE = b"\x89PNG\r\n\x1a\n"
 
 
 def _jpeg_codec():
@@ -36,6 +39,15 @@ def _jpeg_codec():
         return host_codec.load()
     except (OSError, AttributeError) as e:
         raise ValueError("JPEG decoding needs libtcamd_host.so, which is not built (run make): %s" % e) from e
+
+
+def _png_codec():
+    from triton_client_amd.ops import host_codec
+
+    try:
+        return host_codec.load()
+    except (OSError, AttributeError) as e:
+        raise ValueError("PNG decoding needs libtcamd_host.so, which is not built (run make): %s" % e) from e
 
 
 JPEG_SCALES = (1, 2, 4, 8)
@@ -65,12 +77,16 @@ def check_jpeg_scale(value, auto=True):
 
 
 def decode_image(blob, jpeg_scale=1):
-    """PPM / PGM / TCIMG / baseline JPEG blob -> uint8 [H, W, C].  A JPEG the
-    decoder does not cover raises ``ValueError("unsupported JPEG: ...")``, a
-    broken one ``ValueError("malformed JPEG: ...")``.  ``jpeg_scale`` 2, 4 or 8
-    decodes a JPEG in the DCT domain at that fraction of its size,
-    ``ceil(H / s) x ceil(W / s)``; the other encodings ignore it."""
+    """PPM / PGM / TCIMG / baseline JPEG / PNG blob -> uint8 [H, W, C].  A JPEG
+    or PNG the decoder does not cover raises ``ValueError("unsupported JPEG:
+    ...")`` / ``("unsupported PNG: ...")``, a broken one ``("malformed JPEG:
+    ...")`` / ``("malformed PNG: ...")``.  A PNG gives C = 1 for grey and C = 3
+    otherwise: 16-bit samples give their high byte and alpha is dropped.
+    ``jpeg_scale`` 2, 4 or 8 decodes a JPEG in the DCT domain at that fraction
+    of its size, ``ceil(H / s) x ceil(W / s)``; the other encodings ignore it."""
     blob = bytes(blob)
+    if blob[:8] == PNG_SIGNATURE:
+        return _png_codec().png_decode(blob)
     if blob[:2] == JPEG_SOI:
         return _jpeg_codec().jpeg_decode(blob, check_jpeg_scale(jpeg_scale, auto=False))
     if blob[:5] == b"TCIMG":
@@ -94,7 +110,7 @@ def decode_image(blob, jpeg_scale=1):
         w, h, _ = parts
         c = 3 if blob[:2] == b"P6" else 1
         return np.frombuffer(blob, dtype=np.uint8, offset=pos, count=h * w * c).reshape(h, w, c)
-    raise ValueError("unsupported image encoding (expected PPM/PGM/TCIMG/JPEG)")
+    raise ValueError("unsupported image encoding (expected PPM/PGM/TCIMG/JPEG/PNG)")
 
 
 def resize_bilinear(img, h, w):
@@ -250,7 +266,8 @@ def preprocess_batch_device(resized, scaling="INCEPTION", fmt="NCHW", dtype="FP3
 
 
 def preprocess_raw_batch_device(images, c, h, w, scaling="INCEPTION", fmt="NCHW", dtype="FP32", device=0,
-                                antialias=False, device_huffman=None, jpeg_scale=1, device_huffman_wide=None):
+                                antialias=False, device_huffman=None, jpeg_scale=1, device_huffman_wide=None,
+                                device_png=None):
     """``preprocess`` of a batch of decoded uint8 HWC images of any sizes on
     the GPU: the raw pixels go up in ONE uint8 host->device copy (a quarter of
     the bytes of the resized fp32 images, and no host resize), K20
@@ -270,8 +287,14 @@ def preprocess_raw_batch_device(images, c, h, w, scaling="INCEPTION", fmt="NCHW"
     error.  ``jpeg_scale`` 2, 4 or 8 decodes the JPEGs at that fraction of
     their size (the host stores, and the upload carries, only the coefficients
     the reduced transform uses), 0 picks :func:`jpeg_auto_scale` per JPEG for
-    the ``h x w`` target.  Returns None when the datatype has no device path
-    (integer models)."""
+    the ``h x w`` target.  A ``bytes`` element with the PNG signature takes the
+    PNG route of ``utils.jpeg_stage``: with ``device_png`` (default:
+    ``TCAMD_DEVICE_PNG`` in the environment, 1 unless set to 0) and for a file
+    that is not interlaced the host inflates the IDAT stream straight into the
+    upload and K25 ``png_unfilter`` writes the pixels into the device-only
+    allocation; otherwise the host decodes it and the pixels go up like an
+    array's.  The result is the same bit for bit.  Returns None when the
+    datatype has no device path (integer models)."""
     if dtype not in _DEVICE_DTYPES:
         return None
     import torch
@@ -284,10 +307,19 @@ def preprocess_raw_batch_device(images, c, h, w, scaling="INCEPTION", fmt="NCHW"
         device_huffman = jpeg_stage.device_huffman_knob()
     if device_huffman_wide is None:
         device_huffman_wide = jpeg_stage.device_huffman_wide_knob()
-    items = []  # a uint8 HWC array, or (blob, parse) of a JPEG
+    if device_png is None:
+        device_png = jpeg_stage.device_png_knob()
+    items = []  # a uint8 HWC array, or (blob, parse) of a JPEG or of a PNG that K25 takes
     for im in images:
         if isinstance(im, (bytes, bytearray, memoryview)):
             blob = bytes(im)
+            if blob[:8] == PNG_SIGNATURE:
+                info = _png_codec().png_parse(blob)
+                if device_png and not info.interlace:
+                    items.append((blob, info))
+                else:
+                    items.append(_png_codec().png_decode(blob))
+                continue
             items.append((blob, jpeg_stage.parse_at_scale(_jpeg_codec(), blob, jpeg_scale, h, w)))
             continue
         im = np.ascontiguousarray(im, dtype=np.uint8)
@@ -297,10 +329,11 @@ def preprocess_raw_batch_device(images, c, h, w, scaling="INCEPTION", fmt="NCHW"
         return None
     dev = torch.device("cuda", device)
     # The upload (``up`` bytes): arrays as they are, host-decoded JPEG coefficient buffers at 128-byte
-    # boundaries, packed JPEG streams at 16-byte boundaries.  In a second allocation, on the device only
-    # (``only`` bytes): the coefficient buffers K23 / K24 write, at 128-byte boundaries, and the pixels K22 writes.
+    # boundaries, packed JPEG streams and the staged bytes of PNGs at 16-byte boundaries.  In a second
+    # allocation, on the device only (``only`` bytes): the coefficient buffers K23 / K24 write, at 128-byte
+    # boundaries, and the pixels K22 / K25 write.
     codec = _jpeg_codec() if any(isinstance(im, tuple) for im in items) else None
-    raws, jobs, up, only = [], [], 0, 0
+    raws, jobs, pngs, up, only = [], [], [], 0, 0
     packs = {}  # row -> the stream its pack wrote
     for row, im in enumerate(items):
         if not isinstance(im, tuple):
@@ -308,6 +341,12 @@ def preprocess_raw_batch_device(images, c, h, w, scaling="INCEPTION", fmt="NCHW"
             up += im.size
             continue
         blob, info = im
+        if isinstance(info, host_codec.PngInfo):
+            at = -(-up // 16) * 16
+            up = at + info.stage_bytes
+            pngs.append(jpeg_stage.PngJob(at, only, info, row, blob, antialias, 0))
+            only += info.pixel_bytes
+            continue
         room = None
         if device_huffman or device_huffman_wide:
             room = host_codec.aligned_buffer(max(codec.jpeg_stream_bound(len(blob)),
@@ -334,6 +373,8 @@ def preprocess_raw_batch_device(images, c, h, w, scaling="INCEPTION", fmt="NCHW"
             codec.jpeg_entropy_decode(j.blob, raw[j.coef:j.coef + j.info.coef_bytes], j.info.scale)
         else:
             raw[j.stream:j.stream + packs[j.row].size] = packs[j.row]
+    for j in pngs:
+        codec.png_inflate(j.blob, raw[j.stream:j.stream + j.info.stage_bytes])
     src = torch.from_numpy(raw).to(dev, non_blocking=False)
     stream = torch.cuda.current_stream(dev).cuda_stream
     scratch = torch.empty(only, device=dev, dtype=torch.uint8)
@@ -341,17 +382,18 @@ def preprocess_raw_batch_device(images, c, h, w, scaling="INCEPTION", fmt="NCHW"
     need = hip.jpeg_huffman_wide_workspace(nsubs) if nsubs else 0
     workspace = torch.empty(need, device=dev, dtype=torch.uint8)
     ran = jpeg_stage.launch_decode(hip, jobs, src.data_ptr(), scratch.data_ptr(), workspace.data_ptr(), need,
-                                   lambda n: torch.empty(n, device=dev, dtype=torch.int32), stream)
-    staged = sorted(jobs + raws, key=lambda j: j.row)
+                                   lambda n: torch.empty(n, device=dev, dtype=torch.int32), stream, pngs=pngs)
+    staged = sorted(jobs + pngs + raws, key=lambda j: j.row)
     shape = (len(items), c, h, w) if fmt == "NCHW" else (len(items), h, w, c)
     dst = torch.empty(shape, device=dev, dtype=torch.float32 if dtype == "FP32" else torch.float16)
     scale, bias = _SCALE_BIAS[scaling](c)
     per = c * h * w * dst.element_size()
-    hip.resize_pack([(scratch if isinstance(j, jpeg_stage.JpegJob) else src).data_ptr() + j.pix for j in staged],
+    hip.resize_pack([(src if isinstance(j, jpeg_stage.RawImage) else scratch).data_ptr() + j.pix for j in staged],
                     [j.shape for j in staged], [dst.data_ptr() + j.row * per for j in staged], dtype, fmt, c, h, w,
                     scale=scale, bias=bias, stream=stream, antialias=antialias)
     out = dst.cpu().numpy()
     if any(status.cpu().numpy().any() for _, status in ran):
         return preprocess_raw_batch_device(images, c, h, w, scaling, fmt, dtype, device, antialias,
-                                           device_huffman=False, jpeg_scale=jpeg_scale, device_huffman_wide=0)
+                                           device_huffman=False, jpeg_scale=jpeg_scale, device_huffman_wide=0,
+                                           device_png=device_png)
     return out

@@ -1,5 +1,5 @@
-"""The route a JPEG takes to the device and the layout of the staging area it
-is routed into: the one place where both are decided, for the GPU
+"""The route a JPEG or a PNG takes to the device and the layout of the staging area
+it is routed into: the one place where both are decided, for the GPU
 ``preprocess_inception`` (server/gpu_models.py) and for
 ``utils.image.preprocess_raw_batch_device``.  Planning is integer arithmetic
 and calls into a ``HostCodec`` (ops/host_codec.py), so it runs, and is tested
@@ -22,16 +22,27 @@ The routes of a JPEG, tried in this order:
 
 K22 ``jpeg_decode`` turns the coefficients of every route into pixels.
 
+A PNG has one device route, under ``TCAMD_DEVICE_PNG=1`` and for a file that is
+not interlaced: ``HostCodec.png_inflate`` inflates the IDAT stream straight
+into the staging area (filtered scanlines, then the palette of colour type 3,
+then, for an image of more rows than a pass of the kernel, one scanline of
+scratch that only the kernel touches), and K25 ``png_unfilter`` reverses the
+filters and converts the samples into pixels.  The fit test needs the parse
+alone, so a PNG that does not fit is never inflated twice: like an interlaced
+one, or any PNG with the knob off, the caller decodes it on the host
+(``HostCodec.png_decode``) and offers the pixels as a raw image.
+
 The staging area of a :class:`StagePlan` is ``capacity`` bytes that exist on
 the host (the view) and on the device:
 
 * the *upload region* ``[0, used)`` is what the host writes and the H2D copy
   carries: raw pixels at any alignment, ``HOST`` coefficient buffers at
-  multiples of 128, packed streams at multiples of 16;
+  multiples of 128, packed streams and the staged bytes of a PNG at multiples
+  of 16;
 * the *device-only region* ``[top, capacity)`` is written by kernels alone: for
   a ``K23`` or ``K24`` JPEG the pixels at ``top - pixel_bytes`` and the
   coefficients at ``(top - pixel_bytes - coef_bytes) // 128 * 128``, which is
-  the new ``top``; for a ``HOST`` JPEG only the pixels;
+  the new ``top``; for a ``HOST`` JPEG and for a PNG only the pixels;
 * K24's workspace, ``ws_need = 16 + workspace(the K24 subsequence counts so
   far)`` bytes (16: it starts at a 16-byte boundary), lies below ``top`` at
   :attr:`StagePlan.workspace` once the plan is complete, so at every step
@@ -59,6 +70,13 @@ def device_huffman_wide_knob():
     return max(0, int(os.environ.get("TCAMD_DEVICE_HUFFMAN_WIDE", "0") or 0))
 
 
+def device_png_knob():
+    """``TCAMD_DEVICE_PNG``: 1 (the default) = the host inflates a
+    non-interlaced PNG into the staging area and K25 ``png_unfilter`` makes the
+    pixels on the device; 0 = the host decodes it and the pixels go up."""
+    return os.environ.get("TCAMD_DEVICE_PNG", "1") != "0"
+
+
 def parse_at_scale(codec, blob, jpeg_scale, h_out, w_out):
     """The parse of a JPEG blob at ``jpeg_scale`` (1, 2, 4 or 8); 0 picks
     :func:`utils.image.jpeg_auto_scale` for an ``h_out x w_out`` target."""
@@ -75,6 +93,18 @@ class JpegJob(namedtuple("JpegJob", "route stream coef pix info nsub row blob an
     (None on ``HOST``), its coefficients and its pixels; its parse; its K24
     subsequences (0 on the other routes); its row of the batch, its blob, its
     antialias flag and the index of its request."""
+
+    __slots__ = ()
+
+    @property
+    def shape(self):
+        return self.info.shape
+
+
+class PngJob(namedtuple("PngJob", "stream pix info row blob antialias request")):
+    """A staged PNG: the offsets of its staged bytes (``info.stage_bytes`` in
+    the upload region) and of its pixels; its parse; its row of the batch, its
+    blob, its antialias flag and the index of its request."""
 
     __slots__ = ()
 
@@ -114,16 +144,16 @@ class StagePlan:
     """The plan of one batch over ``stage``, a uint8 numpy view whose first
     byte is 16-byte aligned and whose size is the capacity (the layout: the
     module's docstring).  ``huffman`` and ``huffman_wide`` are the two knobs,
-    ``max_dim`` the largest image side the device resize takes.  ``jpegs`` and
-    ``raws`` list the batch's images in the order they were added; ``rows``
-    counts them."""
+    ``max_dim`` the largest image side the device resize takes.  ``jpegs``,
+    ``pngs`` and ``raws`` list the batch's images in the order they were added;
+    ``rows`` counts them."""
 
     def __init__(self, stage, codec, huffman=False, huffman_wide=0, max_dim=16384):
         self.stage, self.codec = stage, codec
         self.huffman, self.huffman_wide, self.max_dim = huffman, huffman_wide, max_dim
         self.rows = self.used = self.ws_need = 0
         self.top = stage.size
-        self.jpegs, self.raws = [], []
+        self.jpegs, self.raws, self.pngs = [], [], []
 
     @property
     def workspace(self):
@@ -131,12 +161,12 @@ class StagePlan:
         return (self.top - self.ws_need + 15) // 16 * 16
 
     def mark(self):
-        return self.rows, self.used, self.top, self.ws_need, len(self.jpegs), len(self.raws)
+        return self.rows, self.used, self.top, self.ws_need, len(self.jpegs), len(self.raws), len(self.pngs)
 
     def rollback(self, mark):
         """Forget everything added since ``mark``."""
         self.rows, self.used, self.top, self.ws_need = mark[:4]
-        del self.jpegs[mark[4]:], self.raws[mark[5]:]
+        del self.jpegs[mark[4]:], self.raws[mark[5]:], self.pngs[mark[6]:]
 
     def add_raw(self, image, antialias=False):
         """Stage a uint8 HWC array if the device resize takes it and it fits."""
@@ -184,9 +214,27 @@ class StagePlan:
         return job
 
 
-def launch_decode(hip, jobs, upload, device_only, workspace, workspace_bytes, alloc_status, stream):
-    """Issue K23, then K24, then K22 for the :class:`JpegJob` list ``jobs`` on
-    ``stream``.  ``upload`` and ``device_only`` are the device addresses that
+    def add_png(self, blob, info, antialias=False, request=0):
+        """Stage a non-interlaced PNG blob with parse ``info`` for K25: None,
+        with nothing inflated, when its staged bytes and its pixels do not fit
+        (or the device resize does not take its size).  A blob that does not
+        inflate raises the host decoder's error and leaves the plan as it was."""
+        at = -(-self.used // 16) * 16
+        if info.interlace or not (1 <= info.h <= self.max_dim and 1 <= info.w <= self.max_dim) \
+                or at + info.stage_bytes > self.top - info.pixel_bytes - self.ws_need:
+            return None
+        self.codec.png_inflate(blob, self.stage[at:at + info.stage_bytes])
+        self.used = at + info.stage_bytes
+        self.top -= info.pixel_bytes
+        job = PngJob(at, self.top, info, self.rows, blob, antialias, request)
+        self.pngs.append(job)
+        self.rows += 1
+        return job
+
+
+def launch_decode(hip, jobs, upload, device_only, workspace, workspace_bytes, alloc_status, stream, pngs=()):
+    """Issue K23, then K24, then K22 for the :class:`JpegJob` list ``jobs`` and
+    K25, once, for the :class:`PngJob` list ``pngs`` on ``stream``.  ``upload`` and ``device_only`` are the device addresses that
     the offsets of the two regions count from (the same address for a
     :class:`StagePlan`); ``workspace`` is the device address of K24's
     ``workspace_bytes``; ``alloc_status(n)`` gives ``n`` int32 status words on
@@ -209,4 +257,7 @@ def launch_decode(hip, jobs, upload, device_only, workspace, workspace_bytes, al
     if jobs:
         hip.jpeg_decode([(upload if j.route == HOST else device_only) + j.coef for j in jobs],
                         [j.info for j in jobs], [device_only + j.pix for j in jobs], stream=stream)
+    if pngs:
+        hip.png_unfilter([upload + j.stream for j in pngs], [j.info for j in pngs],
+                         [device_only + j.pix for j in pngs], stream=stream)
     return ran

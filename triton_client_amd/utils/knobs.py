@@ -97,6 +97,10 @@ KNOBS = [
          "JPEG: N > 0 = blobs of at least N bytes that K23 did not take are packed by the host and decoded by the "
          "K24 jpeg_huffman_wide kernels, at any jpeg_scale; 0 = off",
          "tests/test_jpeg_huffman_wide_gpu.py::test_the_wide_knob_changes_the_route_and_not_one_bit_of_the_rows"),
+    Knob("TCAMD_DEVICE_PNG", "python", 1, "utils/jpeg_stage.py",
+         "PNG: 1 = the host inflates a non-interlaced file into the staging area and K25 png_unfilter reverses the "
+         "filters and converts the samples on the device; 0 = the host decodes it and the pixels go up",
+         "tests/test_png_gpu.py::test_the_png_knob_changes_the_route_and_not_one_bit_of_the_rows"),
     Knob("TCAMD_BYTES_HOST_MAX", "python", 8192, "tritonclient/utils/hip_shared_memory",
          "BYTES set with bytes_path=auto: host codec up to this many elements, K2 above",
          "tests/test_knobs.py::test_bytes_auto_path_knobs"),

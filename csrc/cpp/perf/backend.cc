@@ -372,6 +372,12 @@ F HipKernel(const char* sym)
 
 }  // namespace
 
+void* HipKernelSymbol(const char* sym)
+{
+  void* h = HipKernelLib();
+  return h ? dlsym(h, sym) : nullptr;
+}
+
 DataSet::~DataSet()
 {
   for (auto& v : inputs_)
@@ -381,9 +387,19 @@ DataSet::~DataSet()
     for (auto* o : v) delete o;
 }
 
-const std::vector<const InferRequestedOutput*>& DataSet::Outputs(size_t slot) const
+const std::vector<const InferRequestedOutput*>& DataSet::Outputs(size_t slot, int set) const
 {
-  return outputs_c_[slot % outputs_c_.size()];
+  const size_t nslot = outputs_c_.size() / sets_;
+  return outputs_c_[(slot % nslot) * sets_ + set % sets_];
+}
+
+void* DataSet::OutputPtr(size_t slot, int set, size_t output, size_t* capacity) const
+{
+  if (out_regions_.empty()) return nullptr;
+  const size_t nslot = out_regions_.size() / sets_;
+  const Region& r = regions_[out_regions_[(slot % nslot) * sets_ + set % sets_][output]];
+  *capacity = r.bytes;
+  return r.device ? r.dev : r.host;
 }
 
 Error DataSet::MakeRegion(Backend* be, const std::string& name, size_t bytes, bool device, Region* r)
@@ -462,7 +478,9 @@ Error DataSet::FillHost(const TensorSpec& t, const std::vector<int64_t>& shape, 
   return Error::Success;
 }
 
-static Error LoadJsonData(const std::string& path, std::vector<js::Value>* entries)
+// "data" and, when present, "validation_data" (parallel to it, flattened alike)
+static Error LoadJsonData(const std::string& path, std::vector<js::Value>* entries,
+                          std::vector<js::Value>* validation, bool* has_validation)
 {
   std::ifstream f(path);
   if (!f) return Error("cannot open --input-data file " + path);
@@ -481,6 +499,99 @@ static Error LoadJsonData(const std::string& path, std::vector<js::Value>* entri
     else
       entries->push_back(e);
   }
+  const js::Value* vd = v.Find("validation_data");
+  *has_validation = vd != nullptr;
+  if (vd) {
+    if (!vd->IsArray()) return Error("--input-data: \"validation_data\" must be an array");
+    for (const auto& e : vd->Elements()) {
+      if (e.IsArray())
+        for (const auto& x : e.Elements()) validation->push_back(x);
+      else
+        validation->push_back(e);
+    }
+    if (validation->size() != entries->size())
+      return Error("--input-data: \"validation_data\" has " + std::to_string(validation->size()) + " entries, \"data\" has " +
+                   std::to_string(entries->size()));
+  }
+  return Error::Success;
+}
+
+// One sample of an expected output from its JSON content, in wire format
+// (BYTES serialized, FP16 rounded to nearest even, BF16 truncated); *count is
+// the number of elements.
+static Error ExpectedBytes(const TensorSpec& t, const js::Value& content, std::vector<uint8_t>* out, int64_t* count)
+{
+  out->clear();
+  *count = static_cast<int64_t>(content.Size());
+  const size_t es = DtypeSize(t.datatype);
+  if (t.datatype != "BYTES" && es == 0) return Error("validation_data: unsupported datatype " + t.datatype);
+  std::vector<float> narrow;
+  for (const auto& x : content.Elements()) {
+    if (t.datatype == "BYTES") {
+      const std::string str = x.AsString();
+      const uint32_t len = static_cast<uint32_t>(str.size());
+      const uint8_t* lp = reinterpret_cast<const uint8_t*>(&len);
+      out->insert(out->end(), lp, lp + 4);
+      out->insert(out->end(), str.begin(), str.end());
+      continue;
+    }
+    if (NarrowFloat(t.datatype)) {
+      narrow.push_back(static_cast<float>(x.AsDouble()));
+      continue;
+    }
+    uint8_t buf[8] = {0};
+    if (t.datatype == "FP32") { float f = static_cast<float>(x.AsDouble()); memcpy(buf, &f, 4); }
+    else if (t.datatype == "FP64") { double f = x.AsDouble(); memcpy(buf, &f, 8); }
+    else if (t.datatype == "BOOL") { buf[0] = x.AsBool() ? 1 : 0; }
+    else { int64_t iv = x.AsInt(); memcpy(buf, &iv, es); }
+    out->insert(out->end(), buf, buf + es);
+  }
+  if (NarrowFloat(t.datatype)) NarrowOnHost(t.datatype, narrow, out);
+  return Error::Success;
+}
+
+Error DataSet::LoadExpectations(const ModelInfo& info, const void* json_entries, int bs)
+{
+  const auto& vals = *static_cast<const std::vector<js::Value>*>(json_entries);
+  for (size_t ent = 0; ent < vals.size(); ++ent) {
+    const js::Value& jd = vals[ent];
+    if (!jd.IsObject()) return Error("validation_data entry " + std::to_string(ent) + " is not an object");
+    for (const auto& kv : jd.Members()) {
+      size_t oi = 0;
+      while (oi < info.outputs.size() && info.outputs[oi].name != kv.first) ++oi;
+      if (oi == info.outputs.size())
+        return Error("validation_data entry " + std::to_string(ent) + " names '" + kv.first +
+                     "', which is not an output of the model");
+      const TensorSpec& t = info.outputs[oi];
+      const js::Value& v = kv.second;
+      const js::Value* content = v.IsObject() ? v.Find("content") : &v;
+      if (!content || !content->IsArray()) return Error("validation_data: bad content for " + t.name);
+      std::vector<int64_t> shape = t.shape;
+      bool known = true;
+      if (v.IsObject() && v.Find("shape")) {
+        shape.clear();
+        for (const auto& x : v.Find("shape")->Elements()) shape.push_back(x.AsInt());
+      }
+      for (auto d : shape) known = known && d >= 0;
+      std::vector<uint8_t> sample;
+      int64_t count = 0;
+      Error e = ExpectedBytes(t, *content, &sample, &count);
+      if (!e.IsOk()) return e;
+      if (known && count != Elements(shape))
+        return Error("validation_data entry " + std::to_string(ent) + ": " + t.name + " has " + std::to_string(count) +
+                     " elements, its shape has " + std::to_string(Elements(shape)));
+      Expectation& x = expect_[ent][oi];
+      x.named = x.have = true;
+      for (int b = 0; b < bs; ++b) x.bytes.insert(x.bytes.end(), sample.begin(), sample.end());
+      x.size = x.bytes.size();
+      if (o_.shared_memory == "hip" && x.size) {
+        hipError_t he = hipSetDevice(o_.device);
+        if (he == hipSuccess) he = hipMalloc(&x.dev, x.size);
+        if (he == hipSuccess) he = hipMemcpy(x.dev, x.bytes.data(), x.size, hipMemcpyHostToDevice);
+        if (he != hipSuccess) return Error(std::string("expectation upload failed: ") + hipGetErrorString(he));
+      }
+    }
+  }
   return Error::Success;
 }
 
@@ -495,11 +606,19 @@ Error DataSet::Init(const Options& o, const ModelInfo& info, Backend* be, size_t
   const bool shm = o.shared_memory != "none";
   const bool dev = o.shared_memory == "hip";
   const bool json_data = o.input_data != "random" && o.input_data != "zero";
-  std::vector<js::Value> entries;
+  std::vector<js::Value> entries, validation;
+  bool has_validation = false;
   if (json_data) {
-    Error e = LoadJsonData(o.input_data, &entries);
+    Error e = LoadJsonData(o.input_data, &entries, &validation, &has_validation);
     if (!e.IsOk()) return e;
   }
+  if (has_validation && o.validate_outputs == "first")
+    return Error("--validate-outputs first cannot be combined with \"validation_data\" in the --input-data JSON");
+  validating_ = has_validation || o.validate_outputs == "first";
+  if (validating_ && !o.preregistered_outputs.empty())
+    return Error("output validation needs output regions of its own: drop --shared-memory-output");
+  sets_ = validating_ && dev ? 2 : 1;
+  out_specs_ = info.outputs;
   size_t n_entries = json_data ? entries.size() : 1;
   for (const auto& kv : o.preregistered_input_lists) n_entries = std::max(n_entries, kv.second.size());
   slot_entries_ = !o.preregistered_input_lists.empty();
@@ -700,10 +819,23 @@ Error DataSet::Init(const Options& o, const ModelInfo& info, Backend* be, size_t
       in->SetSharedMemory(r.name, r.bytes, 0);
     }
   }
-  // outputs: one region per slot per output in shm mode
-  const size_t nslot = shm ? std::max<size_t>(1, max_slots) : 1;
+  if (validating_) {
+    expect_.assign(n_entries, std::vector<Expectation>(info.outputs.size()));
+    if (has_validation) {
+      Error e = LoadExpectations(info, &validation, bs);
+      if (!e.IsOk()) return e;
+    } else {
+      for (auto& ent : expect_)
+        for (auto& x : ent) x.named = true;  // "first": every output, expectation captured on the way
+    }
+  }
+  // outputs: one region per slot per output in shm mode (two when validating
+  // on HIP shm: a slot alternates, so the compare of one response can still be
+  // reading while the server writes the next)
+  const size_t nslot = (shm ? std::max<size_t>(1, max_slots) : 1) * sets_;
   outputs_.resize(nslot);
   outputs_c_.resize(nslot);
+  if (shm && validating_) out_regions_.resize(nslot);
   for (size_t s = 0; s < nslot; ++s) {
     for (const auto& t : info.outputs) {
       InferRequestedOutput* out;
@@ -736,6 +868,7 @@ Error DataSet::Init(const Options& o, const ModelInfo& info, Backend* be, size_t
       e = MakeRegion(be, prefix_ + "out_" + t.name + "_" + std::to_string(s), bytes, dev, &r);
       regions_.push_back(r);
       if (!e.IsOk()) return e;
+      if (validating_) out_regions_[s].push_back(regions_.size() - 1);
       out->SetSharedMemory(r.name, r.bytes, 0);
     }
   }
@@ -753,6 +886,14 @@ Error DataSet::Init(const Options& o, const ModelInfo& info, Backend* be, size_t
   if (o.compression != "none") d2 << ", " << o.compression << " compression";
   if (!o.request_parameters.empty()) d2 << ", " << o.request_parameters.size() << " request parameter(s)";
   if (!fill_inputs && !input_regions_.empty()) d2 << ", inputs replicated by fan-out";
+  if (validating_) {
+    d2 << ", outputs validated against " << (has_validation ? "validation_data" : "each entry's first response");
+    if (o.validation_atol > 0 || o.validation_rtol > 0)
+      d2 << " (atol " << o.validation_atol << ", rtol " << o.validation_rtol << ")";
+    else
+      d2 << " (exact)";
+    if (dev) d2 << " on the device by K26";
+  }
   if (!desc.str().empty()) d2 << "; " << desc.str();
   describe_ = d2.str();
   return Error::Success;
@@ -770,6 +911,11 @@ std::vector<DataSet::RegionView> DataSet::InputRegions() const
 
 void DataSet::Release(Backend* be)
 {
+  for (auto& ent : expect_)
+    for (auto& x : ent) {
+      if (x.dev) (void)hipFree(x.dev);
+      x.dev = nullptr;
+    }
   for (auto& r : regions_) {
     if (be) {
       if (r.device) be->UnregisterDevice(r.name);

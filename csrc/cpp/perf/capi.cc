@@ -159,6 +159,7 @@ int tcperf_profile(void* h, double load, double* out, char* err, int errlen)
   tcperf::PointResult p;
   tcperf::Error e = prof.Profile(load, &p);
   s->engine->SetConcurrency(0);
+  if (e.IsOk() && p.validation_failed) e = tcperf::Error("output validation failed: " + p.validation_error);
   if (!e.IsOk()) {
     SetErr(err, errlen, e.Message());
     return 1;
@@ -167,6 +168,26 @@ int tcperf_profile(void* h, double load, double* out, char* err, int errlen)
                         p.throughput, p.avg_us, p.p50_us, p.p90_us, p.p95_us, p.p99_us, p.client_send_us,
                         p.client_recv_us};
   memcpy(out, v, sizeof(v));
+  return 0;
+}
+
+// Output validation (--validate-outputs / "validation_data"): reads back what
+// the engine compared so far; out[0..2]: 1 when validation is on, responses
+// validated, responses that failed (all time).  `msg` gets the line about the
+// first failure ("" when none).
+int tcperf_validation(void* h, uint64_t* out, char* msg, int msglen)
+{
+  auto* s = static_cast<tcperf::Session*>(h);
+  out[0] = out[1] = out[2] = 0;
+  SetErr(msg, msglen, "");
+  tcperf::Validator* v = s->engine->Validation();
+  if (!v) return 0;
+  uint64_t a = 0, b = 0;
+  v->Collect(&a, &b);
+  out[0] = 1;
+  out[1] = v->Validated();
+  out[2] = v->Failed();
+  SetErr(msg, msglen, v->FirstFailure());
   return 0;
 }
 

@@ -38,6 +38,10 @@ LoadEngine::LoadEngine(const Options& o, Backend* be, DataSet* data, size_t max_
       owned_.push_back(std::move(b));
     }
   }
+  if (data_->Validating()) {
+    validator_.reset(new Validator(o, data_, slots_.size()));
+    if (!validator_->SetupError().empty()) first_error_ = validator_->SetupError();
+  }
   if (o.async || o.streaming) worker_ = std::thread(&LoadEngine::Worker, this);
 }
 
@@ -52,6 +56,7 @@ LoadEngine::~LoadEngine()
   if (worker_.joinable()) worker_.join();
   clients_.clear();
   owned_.clear();  // after the worker: completions may still reference them
+  validator_.reset();
 }
 
 void LoadEngine::Stop()
@@ -94,15 +99,30 @@ void LoadEngine::PrepareSequence(Slot* s)
   s->seq_pos = (s->seq_pos + 1) % o_.sequence_length;
 }
 
-void LoadEngine::OnComplete(size_t slot, uint64_t start_ns, InferResult* r)
+// The request's data entry and, when validating on HIP shm, which of the
+// slot's two output sets it writes to (the slot alternates).
+LoadEngine::Sent LoadEngine::Prepare(size_t slot)
 {
-  Record rec{start_ns, NowNs(), true};
+  Slot& s = slots_[slot];
+  Sent sent{slot, 0, data_->EntryOf(issued_++, slot), s.next_set};
+  if (data_->OutputSets() > 1) s.next_set ^= 1;
+  sent.start_ns = NowNs();
+  return sent;
+}
+
+void LoadEngine::OnComplete(const Sent& sent, InferResult* r)
+{
+  const size_t slot = sent.slot;
+  Record rec{sent.start_ns, NowNs(), true};
   if (r) {
     Error e = r->RequestStatus();
     if (!e.IsOk()) {
       rec.ok = false;
       std::lock_guard<std::mutex> lk(rec_mu_);
       if (first_error_.empty()) first_error_ = e.Message();
+    } else if (validator_) {
+      // after the latency is taken, before the slot can be issued again
+      validator_->Check(slot, sent.set, sent.entry, r);
     }
     delete r;
   } else {
@@ -119,7 +139,8 @@ Error LoadEngine::Issue(size_t slot)
 {
   Slot& s = slots_[slot];
   PrepareSequence(&s);
-  const uint64_t t = NowNs();
+  const Sent sent = Prepare(slot);
+  const auto& inputs = data_->Inputs(sent.entry);  // entry e is Inputs(e): EntryOf() already chose it
   in_flight_++;
   Error e;
   if (streaming_) {
@@ -127,25 +148,25 @@ Error LoadEngine::Issue(size_t slot)
     {
       std::lock_guard<std::mutex> lk(stream_mu_);
       id = std::to_string(++stream_counter_);
-      stream_ids_[id] = {slot, t};
+      stream_ids_[id] = sent;
     }
     s.opt.request_id_ = id;
-    e = be_->StreamInfer(s.opt, data_->Inputs(issued_++, slot), data_->Outputs(slot));
+    e = be_->StreamInfer(s.opt, inputs, data_->Outputs(slot, sent.set));
     if (!e.IsOk()) {
       std::lock_guard<std::mutex> lk(stream_mu_);
       stream_ids_.erase(id);
     }
   } else {
     Backend* be = clients_.empty() ? be_ : clients_[slot % clients_.size()];
-    e = be->AsyncInfer([this, slot, t](InferResult* r) { OnComplete(slot, t, r); }, s.opt, data_->Inputs(issued_++, slot),
-                       data_->Outputs(slot));
+    e = be->AsyncInfer([this, sent](InferResult* r) { OnComplete(sent, r); }, s.opt, inputs,
+                       data_->Outputs(slot, sent.set));
   }
   if (!e.IsOk()) {
     {
       std::lock_guard<std::mutex> lk(rec_mu_);
       if (first_error_.empty()) first_error_ = e.Message();
     }
-    OnComplete(slot, t, nullptr);  // counts as a failed request; keeps the accounting whole
+    OnComplete(sent, nullptr);  // counts as a failed request; keeps the accounting whole
   }
   return e;
 }
@@ -156,21 +177,19 @@ Error LoadEngine::EnsureStream()
   Error e = be_->StartStream([this](InferResult* r) {
     std::string id;
     if (r) r->Id(&id);
-    size_t slot = 0;
-    uint64_t t = 0;
+    Sent sent{0, 0, 0, 0};
     bool found = false;
     {
       std::lock_guard<std::mutex> lk(stream_mu_);
       auto it = stream_ids_.find(id);
       if (it != stream_ids_.end()) {
-        slot = it->second.first;
-        t = it->second.second;
+        sent = it->second;
         stream_ids_.erase(it);
         found = true;
       }
     }
     if (found) {
-      OnComplete(slot, t, r);
+      OnComplete(sent, r);
     } else {
       delete r;  // extra responses of a decoupled model
     }
@@ -240,12 +259,13 @@ void LoadEngine::SyncLoop(size_t slot)
     Slot& s = slots_[slot];
     PrepareSequence(&s);
     InferResult* r = nullptr;
-    const uint64_t t = NowNs();
+    const Sent sent = Prepare(slot);
     in_flight_++;
-    e = be->SyncInfer(&r, s.opt, data_->Inputs(issued_++, slot), data_->Outputs(slot));
-    Record rec{t, NowNs(), e.IsOk()};
+    e = be->SyncInfer(&r, s.opt, data_->Inputs(sent.entry), data_->Outputs(slot, sent.set));
+    Record rec{sent.start_ns, NowNs(), e.IsOk()};
     if (r) {
       if (!r->RequestStatus().IsOk()) rec.ok = false;
+      else if (rec.ok && validator_) validator_->Check(slot, sent.set, sent.entry, r);
       delete r;
     }
     in_flight_--;

@@ -64,6 +64,12 @@ int main(int argc, char** argv)
     // checkpoint after every point: a killed sweep resumes with --resume
     tcperf::Error ce = tcperf::WriteJson(o, pts, desc);
     if (!ce.IsOk()) fprintf(stderr, "error: %s\n", ce.Message().c_str());
+    if (p.validation_failed) {
+      // the point is reported, then the run ends: the outputs were wrong
+      fprintf(stderr, "error: output validation failed: %s\n", p.validation_error.c_str());
+      rc = 1;
+      break;
+    }
     const double lat = o.percentile > 0 ? p.p99_us : p.avg_us;
     if (o.latency_threshold_ms && lat > o.latency_threshold_ms * 1000.0) {
       printf("Measured latency went over the set limit of %lu msec.\n",

@@ -18,7 +18,7 @@ enum LongOnly {
   OPT_NUM_CLIENTS, OPT_NO_SERVER_STATS, OPT_GPUS, OPT_DEVICES, OPT_FANOUT, OPT_LOAD_PER_GPU, OPT_MEAS_INTERVAL, OPT_STABILITY, OPT_MAX_TRIALS, OPT_LAT_THRESH,
   OPT_SSL_GRPC_USE, OPT_SSL_GRPC_ROOT, OPT_SSL_GRPC_KEY, OPT_SSL_GRPC_CHAIN, OPT_SSL_HTTPS_PEER, OPT_SSL_HTTPS_HOST,
   OPT_SSL_HTTPS_CA, OPT_SSL_HTTPS_CERT, OPT_SSL_HTTPS_CERT_TYPE, OPT_SSL_HTTPS_KEY, OPT_SSL_HTTPS_KEY_TYPE,
-  OPT_IN_FORMAT, OPT_OUT_FORMAT, OPT_GRPC_COMPRESSION, OPT_COMPRESSION, OPT_REQUEST_PARAM,
+  OPT_IN_FORMAT, OPT_OUT_FORMAT, OPT_GRPC_COMPRESSION, OPT_COMPRESSION, OPT_REQUEST_PARAM, OPT_VALIDATE, OPT_VALIDATION_TOL,
 };
 
 bool ParseU64(const std::string& s, uint64_t* v)
@@ -77,6 +77,17 @@ std::string Usage()
       "  --sequence-length <n>            requests per sequence for sequence models (default 20)\n"
       "  --sequence-id-range s[:e]        sequence ids to use\n"
       "  --input-data random|zero|<file.json>\n"
+      "                                   a JSON file may carry \"validation_data\" next to \"data\": per entry,\n"
+      "                                   output name -> content (or {content, shape}); every response is then\n"
+      "                                   checked against the expectation of the entry its request carried\n"
+      "  [ext] --validate-outputs first   without expected data: the first response of each data entry is the\n"
+      "                                   expectation of its later ones (works on device-filled synthetic data);\n"
+      "                                   not together with \"validation_data\"\n"
+      "  --validation-tolerance ATOL[,RTOL]  FP16/BF16/FP32/FP64 outputs pass when |got - exp| <= ATOL + RTOL * |exp|\n"
+      "                                   (two NaNs pass, an infinity only against itself); default 0,0: every\n"
+      "                                   byte must be equal, as for all other datatypes.  HIP shm outputs are\n"
+      "                                   compared on the device (K26); the first failure ends the run after its\n"
+      "                                   window with exit status 1 and a line naming output, entry and element\n"
       "  --string-length <n> / --string-data <s>   BYTES synthetic data\n"
       "  --shared-memory none|system|cuda|hip      tensor transport (cuda is an alias of hip)\n"
       "  --output-shared-memory-size <bytes>       per-output region size (default 102400)\n"
@@ -187,6 +198,8 @@ Error ParseOptions(int argc, char** argv, Options* o, bool* help)
       {"grpc-compression-algorithm", required_argument, nullptr, OPT_GRPC_COMPRESSION},
       {"compression-algorithm", required_argument, nullptr, OPT_COMPRESSION},
       {"request-parameter", required_argument, nullptr, OPT_REQUEST_PARAM},
+      {"validate-outputs", required_argument, nullptr, OPT_VALIDATE},
+      {"validation-tolerance", required_argument, nullptr, OPT_VALIDATION_TOL},
       {"verbose", no_argument, nullptr, 'v'},
       {"help", no_argument, nullptr, 'h'},
       {nullptr, 0, nullptr, 0}};
@@ -447,6 +460,20 @@ Error ParseOptions(int argc, char** argv, Options* o, bool* help)
           if (rp.value.empty() || *end) return Error("--request-parameter: bad double '" + rp.value + "'");
         }
         o->request_parameters[rp.name] = rp;
+        break;
+      }
+      case OPT_VALIDATE:
+        if (arg != "first") return Error("--validate-outputs expects 'first'");
+        o->validate_outputs = arg;
+        break;
+      case OPT_VALIDATION_TOL: {
+        auto parts = Split(arg, ',');
+        o->validation_rtol = 0;
+        if (parts.size() > 2 || !ParseDouble(parts[0], &o->validation_atol) ||
+            (parts.size() > 1 && !ParseDouble(parts[1], &o->validation_rtol)) ||
+            !(o->validation_atol >= 0 && o->validation_rtol >= 0 && o->validation_atol < 1e300 &&
+              o->validation_rtol < 1e300))
+          return Error("--validation-tolerance expects ATOL[,RTOL], finite and not negative");
         break;
       }
       case 'v': o->verbose = true; break;

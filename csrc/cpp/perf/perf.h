@@ -10,6 +10,7 @@
 //                --request-rate-range --request-distribution
 //                --request-intervals --sequence-length --sequence-id-range
 //                --input-data --string-length --string-data
+//                --validate-outputs --validation-tolerance
 //                --shared-memory none|system|cuda|hip
 //                --output-shared-memory-size --measurement-interval/-p
 //                --measurement-mode --measurement-request-count
@@ -25,6 +26,11 @@
 //   Profiler     measurement windows, 3-window stability, percentiles,
 //                server-side breakdown from ModelInferenceStatistics deltas
 //   Reporter     perf_analyzer-style stdout, CSV (-f) and JSON reports
+//   Validator    (validate.cc) --input-data "validation_data" / --validate-outputs
+//                first: every response's outputs against the expectation of the
+//                data entry its request carried, by the rule of
+//                kernels/compare_math.h; on the host for in-band and system-shm
+//                outputs, by one K26 launch on the lane's stream for HIP shm
 //   MultiSession (multigpu.cc) --gpus N / --devices: one Session (client,
 //                regions, LoadEngine worker thread, HIP stream) per GPU; the
 //                synthetic batch is made ONCE (K1 on the first GPU) and
@@ -132,6 +138,9 @@ struct Options {
   std::string output_tensor_format = "binary";
   std::string compression = "none";              // none | gzip | deflate (gRPC messages / HTTP bodies)
   std::map<std::string, triton::client::RequestParameter> request_parameters;
+  // output validation: "" (only when the --input-data JSON has "validation_data") or "first"
+  std::string validate_outputs;
+  double validation_atol = 0, validation_rtol = 0;
 };
 
 /// Parse perf_analyzer flags.  Returns an error for unknown/invalid flags;
@@ -237,7 +246,28 @@ class DataSet {
   std::vector<RegionView> InputRegions() const;
   /// The lane's HIP stream (K1 fill, fan-out copies), null when not HIP.
   void* Stream() const { return stream_; }
-  const std::vector<const InferRequestedOutput*>& Outputs(size_t slot) const;
+  /// Requested outputs of slot `slot`; `set` picks one of OutputSets() sets of regions.
+  const std::vector<const InferRequestedOutput*>& Outputs(size_t slot, int set = 0) const;
+  /// Data entry that Inputs(seq, slot) carries.
+  size_t EntryOf(uint64_t seq, size_t slot) const { return (slot_entries_ ? slot : seq) % inputs_.size(); }
+  /// Output validation ("validation_data" of the JSON, or --validate-outputs first).
+  struct Expectation {
+    bool named = false;          // the entry names this output (or mode "first")
+    bool have = false;           // bytes / dev are filled ("first": after the entry's first response)
+    std::vector<uint8_t> bytes;  // the whole batch, host copy (in-band and system shm)
+    void* dev = nullptr;         // the lane's device copy (HIP shm)
+    size_t size = 0;
+  };
+  bool Validating() const { return validating_; }
+  bool ValidateFirst() const { return o_.validate_outputs == "first"; }
+  bool DeviceOutputs() const { return o_.shared_memory == "hip"; }
+  bool SharedOutputs() const { return o_.shared_memory != "none"; }
+  int OutputSets() const { return sets_; }
+  const std::vector<TensorSpec>& OutputSpecs() const { return out_specs_; }
+  Expectation& Expect(size_t entry, size_t output) { return expect_[entry][output]; }
+  /// Start and capacity of the region output `output` of (slot, set) lands in (shm modes).
+  void* OutputPtr(size_t slot, int set, size_t output, size_t* capacity) const;
+  int Device() const { return o_.device; }
   std::string Describe() const { return describe_; }
   void Release(Backend* be);
 
@@ -255,6 +285,7 @@ class DataSet {
   Error MakeRegion(Backend* be, const std::string& name, size_t bytes, bool device, Region* r);
   Error FillHost(const TensorSpec& t, const std::vector<int64_t>& shape, std::vector<uint8_t>* bytes,
                  std::vector<std::string>* strs);
+  Error LoadExpectations(const ModelInfo& info, const void* json_entries, int bs);
   Options o_;
   std::string prefix_;  // region names: unique per DataSet (several sessions may share one server)
   std::vector<std::vector<InferInput*>> inputs_;              // [entry][input]
@@ -265,8 +296,61 @@ class DataSet {
   std::vector<size_t> input_regions_;  // indices into regions_
   void* stream_ = nullptr;             // hipStream_t on o_.device
   bool slot_entries_ = false;          // entries pinned to slots (caller region lists)
+  bool validating_ = false;
+  int sets_ = 1;                       // output region sets per slot (2: validating on HIP shm)
+  std::vector<TensorSpec> out_specs_;
+  std::vector<std::vector<Expectation>> expect_;     // [entry][output]
+  std::vector<std::vector<size_t>> out_regions_;     // [slot * sets_ + set][output] -> regions_ index
   std::string describe_;
 };
+
+// ---------------------------------------------------------------------------
+/// Checks responses against the expectations of a DataSet.  Check() runs on the
+/// thread a response completes on; Collect() on the profiler's, once per window.
+class Validator {
+ public:
+  Validator(const Options& o, DataSet* data, size_t slots);
+  ~Validator();
+  /// Empty, or why validation cannot run in this configuration.
+  const std::string& SetupError() const { return setup_error_; }
+  /// The response `r` of the request that slot `slot` sent with data entry
+  /// `entry` into output set `set`.  Never blocks on the device but for the
+  /// slot's own event, which the compare before last recorded.
+  void Check(size_t slot, int set, size_t entry, const InferResult* r);
+  /// Reads back what the device compared since the last call (one stream
+  /// synchronisation) and adds the responses validated / failed since then,
+  /// and the largest |got - expected| over finite float pairs seen in them.
+  void Collect(uint64_t* validated, uint64_t* failed, double* max_abs_diff = nullptr);
+  /// All time totals, after a Collect().
+  uint64_t Validated() const { return validated_total_; }
+  uint64_t Failed() const { return failed_total_; }
+  /// One line about the first failing response ("" when none).
+  std::string FirstFailure();
+
+ private:
+  struct Pending;  // one response's K26 launch
+  void Fail(const std::string& line);
+  void Drain();    // mu_ held
+  Options o_;
+  DataSet* data_;
+  std::string setup_error_;
+  std::mutex mu_;
+  uint64_t validated_ = 0, failed_ = 0;  // since the last Collect
+  double max_diff_ = 0;
+  uint64_t validated_total_ = 0, failed_total_ = 0;
+  std::string first_failure_;
+  // HIP shm
+  void* compare_fn_ = nullptr;       // tcamd_compare_expected
+  std::vector<void*> events_;        // hipEvent_t per slot: the slot's latest compare
+  std::vector<uint8_t> event_set_;  // bytes: slots complete on different threads
+  void* dev_records_ = nullptr;      // ring of records, device and pinned host
+  void* host_records_ = nullptr;
+  std::vector<Pending> ring_;
+  uint64_t head_ = 0, tail_ = 0;
+};
+
+/// A symbol of the framework's libtcamd_hip.so (null when the library or the symbol is missing).
+void* HipKernelSymbol(const char* sym);
 
 // ---------------------------------------------------------------------------
 struct Record {
@@ -305,6 +389,8 @@ class LoadEngine {
   size_t CompletedCount();
   std::string FirstError();
   size_t InFlight() const { return in_flight_.load(); }
+  /// The output validator (null when validation is off).
+  Validator* Validation() const { return validator_.get(); }
 
   struct Slot {
     InferOptions opt{""};
@@ -312,6 +398,7 @@ class LoadEngine {
     int seq_pos = 0;
     uint64_t sent_ns = 0;
     bool busy = false;
+    int next_set = 0;  // validating on HIP shm: the output set of the next request
   };
   void SetSequenceModel(bool v) { seq_model_ = v; }
 
@@ -322,7 +409,15 @@ class LoadEngine {
   Error EnsureStream();
   void PrepareSequence(Slot* s);
   void RateLoop(double rate, uint64_t gen);
-  void OnComplete(size_t slot, uint64_t start_ns, InferResult* r);
+  // what a request carried: its slot, send time, data entry and output set
+  struct Sent {
+    size_t slot;
+    uint64_t start_ns;
+    size_t entry;
+    int set;
+  };
+  Sent Prepare(size_t slot);
+  void OnComplete(const Sent& s, InferResult* r);
 
   Options o_;
   Backend* be_;
@@ -357,9 +452,10 @@ class LoadEngine {
   std::atomic<uint64_t> issued_{0};  // request counter (selects the JSON data entry)
   std::string first_error_;
   std::vector<uint64_t> intervals_ns_;
-  // streaming: request id -> (slot, send time)
+  std::unique_ptr<Validator> validator_;
+  // streaming: request id -> what was sent
   std::mutex stream_mu_;
-  std::map<std::string, std::pair<size_t, uint64_t>> stream_ids_;
+  std::map<std::string, Sent> stream_ids_;
   uint64_t stream_counter_ = 0;
 };
 
@@ -378,6 +474,10 @@ struct PointResult {
   bool has_server = false;
   bool has_gpu = false;  // --collect-metrics
   double gpu_util_pct = 0, gpu_power_w = 0, gpu_mem_mib = 0;
+  bool has_validation = false;       // output validation was on
+  uint64_t validated = 0, validation_failed = 0;  // responses
+  double validation_max_diff = 0;    // largest |got - expected| over finite float pairs
+  std::string validation_error;      // the first failure: the run stops after this point
   int gpu = -1;                      // lane device (per-GPU rows), -1 = aggregate / single
   std::vector<PointResult> per_gpu;  // multi-GPU: one row per lane
 };

@@ -165,6 +165,12 @@ Error Profiler::Window(std::vector<PointResult>* w, std::vector<std::vector<uint
       if (rc.ok) (*lat)[i].push_back(rc.end_ns - rc.start_ns);
       else r.errors++;
     }
+    if (Validator* v = L.eng->Validation()) {
+      // one read-back per window: what the lane validated since the last one
+      r.has_validation = true;
+      v->Collect(&r.validated, &r.validation_failed, &r.validation_max_diff);
+      if (r.validation_failed) r.validation_error = v->FirstFailure();
+    }
     r.request_count = (*lat)[i].size();
     r.window_s = (t1 - t0) * 1e-9;
     r.throughput = r.window_s > 0 ? r.request_count * static_cast<double>(o_.batch) / r.window_s : 0;
@@ -192,6 +198,11 @@ static PointResult Aggregate(const std::vector<PointResult>& rows, const std::ve
     a.request_count += r.request_count;
     a.throughput += r.throughput;
     a.errors += r.errors;
+    a.has_validation = a.has_validation || r.has_validation;
+    a.validated += r.validated;
+    a.validation_failed += r.validation_failed;
+    a.validation_max_diff = std::max(a.validation_max_diff, r.validation_max_diff);
+    if (a.validation_error.empty()) a.validation_error = r.validation_error;
     sends += r.client_send_us * r.request_count;
     recvs += r.client_recv_us * r.request_count;
     if (r.has_server && count_server[k]) {
@@ -258,6 +269,7 @@ Error Profiler::Profile(double load, PointResult* out)
     wins.push_back(agg);
     lane_wins.push_back(std::move(w));
     lats.push_back(std::move(lat));
+    if (wins.back().validation_failed) break;  // the run stops at the end of the window that saw a failure
     if (wins.size() >= 3) {
       const size_t m = wins.size();
       double tsum = 0, lsum = 0;
@@ -287,6 +299,11 @@ Error Profiler::Profile(double load, PointResult* out)
       dst->request_count += r.request_count;
       dst->window_s += r.window_s;
       dst->errors += r.errors;
+      dst->has_validation = dst->has_validation || r.has_validation;
+      dst->validated += r.validated;
+      dst->validation_failed += r.validation_failed;
+      dst->validation_max_diff = std::max(dst->validation_max_diff, r.validation_max_diff);
+      if (dst->validation_error.empty()) dst->validation_error = r.validation_error;
       dst->client_send_us += r.client_send_us / (m - from);
       dst->client_recv_us += r.client_recv_us / (m - from);
       if (r.has_server) {
@@ -383,6 +400,10 @@ void PrintPoint(const Options& o, const PointResult& p)
          o.protocol == "grpc" ? "gRPC" : "HTTP", p.client_send_us + p.client_recv_us, p.client_send_us,
          p.client_recv_us);
   if (p.errors) printf("    Failed requests: %lu\n", static_cast<unsigned long>(p.errors));
+  if (p.has_validation)
+    printf("    Validated responses: %lu (failed validation: %lu), largest difference %g\n",
+           static_cast<unsigned long>(p.validated), static_cast<unsigned long>(p.validation_failed),
+           p.validation_max_diff);
   if (p.has_server) {
     const ServerStats& s = p.server;
     const double n = s.success_count ? static_cast<double>(s.success_count) : 1.0;
@@ -411,6 +432,9 @@ void PrintPoint(const Options& o, const PointResult& p)
         printf(", server batches %lu (avg %.1f rows)", static_cast<unsigned long>(g.server.execution_count),
                static_cast<double>(g.server.inference_count) / g.server.execution_count);
       if (g.has_gpu) printf(", GPU util %.1f%%", g.gpu_util_pct);
+      if (g.has_validation)
+        printf(", validated %lu (failed %lu)", static_cast<unsigned long>(g.validated),
+               static_cast<unsigned long>(g.validation_failed));
       printf("\n");
     }
   }
@@ -441,6 +465,10 @@ Error WriteCsv(const Options& o, const std::vector<PointResult>& pts)
        "Avg latency,request/response,response wait";
   if (o.collect_metrics) f << ",Avg GPU Utilization,Avg GPU Power Usage,Max GPU Memory Usage";
   if (o.verbose_csv) f << ",Failed requests,Stable";
+  // only when validation was on: reports of other runs keep their columns
+  bool validation = false;
+  for (const auto& p : pts) validation = validation || p.has_validation;
+  if (validation) f << ",Validated,Validation Failed";
   f << "\n";
   auto row = [&](const PointResult& p, const std::string& gpu) {
     const ServerStats& s = p.server;
@@ -461,6 +489,7 @@ Error WriteCsv(const Options& o, const std::vector<PointResult>& pts)
       f << g;
     }
     if (o.verbose_csv) f << "," << p.errors << "," << (p.stable ? 1 : 0);
+    if (validation) f << "," << p.validated << "," << p.validation_failed;
     f << "\n";
   };
   for (const auto& p : pts) {
@@ -496,6 +525,17 @@ Error WriteJson(const Options& o, const std::vector<PointResult>& pts, const std
              static_cast<unsigned long>(s.queue_ns), static_cast<unsigned long>(s.compute_input_ns),
              static_cast<unsigned long>(s.compute_infer_ns), static_cast<unsigned long>(s.compute_output_ns));
     std::string pt(buf);
+    auto validation = [](const PointResult& r) {
+      char v[192];
+      snprintf(v, sizeof(v), ",\"validation\":{\"validated\":%lu,\"validation_failed\":%lu,\"max_abs_diff\":%.9g}}",
+               static_cast<unsigned long>(r.validated), static_cast<unsigned long>(r.validation_failed),
+               std::isfinite(r.validation_max_diff) ? r.validation_max_diff : 1.7976931348623157e308);
+      return std::string(v);
+    };
+    if (p.has_validation) {
+      pt.pop_back();  // reopen the point object
+      pt += validation(p);
+    }
     if (p.has_gpu) {
       char g[200];
       snprintf(g, sizeof(g), ",\"gpu\":{\"util_pct\":%.2f,\"power_w\":%.2f,\"mem_mib\":%.1f}}", p.gpu_util_pct,
@@ -517,6 +557,10 @@ Error WriteJson(const Options& o, const std::vector<PointResult>& pts, const std
                  static_cast<unsigned long>(g.server.inference_count),
                  static_cast<unsigned long>(g.server.execution_count), "");
         rows += r;
+        if (g.has_validation) {
+          rows.pop_back();
+          rows += validation(g);
+        }
       }
       rows += "]}";
       pt.pop_back();
@@ -581,6 +625,12 @@ Error LoadCheckpoint(const Options& o, std::vector<PointResult>* pts)
       p.server.compute_infer_ns = static_cast<uint64_t>(num(*sv, "compute_infer_ns"));
       p.server.compute_output_ns = static_cast<uint64_t>(num(*sv, "compute_output_ns"));
     }
+    if (const js::Value* vd = e.Find("validation")) {
+      p.has_validation = true;
+      p.validated = static_cast<uint64_t>(num(*vd, "validated"));
+      p.validation_failed = static_cast<uint64_t>(num(*vd, "validation_failed"));
+      p.validation_max_diff = num(*vd, "max_abs_diff");
+    }
     if (const js::Value* g = e.Find("gpu")) {
       p.has_gpu = true;
       p.gpu_util_pct = num(*g, "util_pct");
@@ -612,6 +662,12 @@ Error Session::Create(const Options& o, std::unique_ptr<Session>* out, bool fill
     return e;
   }
   s->engine.reset(new LoadEngine(o, s->backend.get(), s->data.get(), s->max_slots));
+  if (s->engine->Validation() && !s->engine->Validation()->SetupError().empty()) {
+    const std::string err = s->engine->Validation()->SetupError();
+    s->engine.reset();
+    s->data->Release(s->backend.get());
+    return Error(err);
+  }
   s->engine->SetSequenceModel(s->info.sequential);
   *out = std::move(s);
   return Error::Success;

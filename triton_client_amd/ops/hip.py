@@ -11,6 +11,7 @@ events, peer access.  Kernels (csrc/kernels/*.hip, gfx950):
 * :func:`jpeg_huffman`    K23 Huffman decode of packed JPEG scans into the coefficients K22 reads
 * :func:`jpeg_huffman_wide`  K24 the same across workgroups: scans up to 32 MiB, the compact buffer of any scale
 * :func:`png_unfilter`    K25 PNG unfilter + palette / depth / alpha conversion of inflated scanlines
+* :func:`compare_expected` K26 outputs against expectations on the device: mismatches, first index, largest difference
 * :func:`batched_copy`    K7 one-launch gather/concat/scatter of byte ranges
 * :func:`pack_bytes`      K2 BYTES serialisation (LDS block scan + scatter)
 * :func:`index_bytes`     K3 BYTES index walk through an LDS window
@@ -168,6 +169,12 @@ _SIGS = {
             ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32),
             ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.c_void_p,
         ],
+        ctypes.c_int,
+    ),
+    "tcamd_compare_geometry": ([ctypes.POINTER(ctypes.c_uint64)], None),
+    "tcamd_compare_expected": (
+        [ctypes.POINTER(dtypes.ComparePair), ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_void_p,
+         ctypes.c_void_p],
         ctypes.c_int,
     ),
     "tcamd_batched_copy": (
@@ -887,6 +894,44 @@ def png_unfilter(srcs, infos, dsts, stream=None):
     cols = [(ctypes.c_int32 * max(n, 1))(*[int(getattr(i, f)) for i in infos])
             for f in ("h", "w", "ctype", "depth", "interlace")]
     _check(_load().tcamd_png_unfilter(s, *cols, n, d, _vp(stream)), "png_unfilter")
+
+
+COMPARE_MAX_PAIRS = dtypes.COMPARE_MAX_PAIRS
+COMPARE_NO_INDEX = dtypes.COMPARE_NO_INDEX
+COMPARE_RECORD_BYTES = ctypes.sizeof(dtypes.CompareRecord)
+
+
+def compare_geometry():
+    """The decomposition of K26 ``compare_expected``, from the library: ``(bytes
+    of got a lane reads per step, bytes per workgroup, workgroups per pair at
+    most)``."""
+    g = (ctypes.c_uint64 * 3)()
+    _load().tcamd_compare_geometry(g)
+    return int(g[0]), int(g[1]), int(g[2])
+
+
+def compare_expected(pairs, records, atol=0.0, rtol=0.0, stream=None):
+    """K26: compare device-resident outputs with their expectations without
+    copying either to the host.  ``pairs`` is up to :data:`COMPARE_MAX_PAIRS`
+    tuples ``(got, expected, count, datatype)``: two device pointers at any
+    element-aligned address (they need not be misaligned alike), the element
+    count (0 is legal) and the datatype name; BYTES goes in as UINT8 over its
+    serialized bytes.  ``records`` is a device pointer to ``len(pairs)`` records
+    of :data:`COMPARE_RECORD_BYTES` (``dtypes.CompareRecord``), written in stream
+    order: mismatches, lowest mismatching index (:data:`COMPARE_NO_INDEX` when
+    none), largest ``|got - exp|`` over the finite pairs of a float type, and the
+    bits of the two elements at that index.
+
+    With ``atol == rtol == 0``, and always for the integer, BOOL and FP8 types,
+    an element passes iff its bytes are identical.  Otherwise FP16 / BF16 / FP32
+    (in fp32) and FP64 (in fp64) pass on equal bits, on two NaNs, or when both
+    are finite and ``|got - exp| <= atol + rtol * |exp|``.  One launch when every
+    pair fits a workgroup (``compare_geometry()[1]`` bytes), three otherwise.  A
+    null or misaligned pointer, an unknown datatype or a negative or non-finite
+    tolerance raises (hipErrorInvalidValue) without a launch."""
+    tab = dtypes.compare_table(pairs)
+    _check(_load().tcamd_compare_expected(tab, len(pairs), float(atol), float(rtol), _vp(records), _vp(stream)),
+           "compare_expected")
 
 
 def batched_copy(srcs, dsts, sizes, stream=None):

@@ -1,8 +1,10 @@
-"""ctypes binding of libtcamd_host.so (BYTES pack / scan, baseline JPEG and PNG on the host)."""
+"""ctypes binding of libtcamd_host.so (BYTES pack / scan, baseline JPEG and PNG on the host, the compare rule)."""
 import ctypes
 import os
 
 import numpy as np
+
+from . import dtypes
 
 _PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libtcamd_host.so")
 
@@ -118,6 +120,9 @@ class HostCodec:
         lib.tcamd_host_png_unfilter.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(PngInfo), ctypes.c_void_p,
                                                 ctypes.c_uint64]
         lib.tcamd_host_png_unfilter.restype = ctypes.c_int
+        lib.tcamd_host_compare_expected.argtypes = [ctypes.POINTER(dtypes.ComparePair), ctypes.c_int, ctypes.c_double,
+                                                    ctypes.c_double, ctypes.POINTER(dtypes.CompareRecord)]
+        lib.tcamd_host_compare_expected.restype = ctypes.c_int
         lib.tcamd_host_pack_bytes.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]
         lib.tcamd_host_pack_bytes.restype = ctypes.c_int
         lib.tcamd_host_count_bytes.argtypes = [ctypes.c_void_p, ctypes.c_uint64]
@@ -159,6 +164,27 @@ class HostCodec:
                                                    cap, ctypes.byref(consumed))
         return int(n), int(consumed.value)
 
+
+    # -- the compare rule (csrc/kernels/compare_math.h) ---------------------------------
+    def compare_expected(self, pairs, atol=0.0, rtol=0.0):
+        """K26 ``compare_expected`` on the host, field for field: ``pairs`` is up
+        to 64 tuples ``(got, expected, datatype)`` of numpy arrays of equal size
+        (any dtype of the datatype's width; only their bytes are read).  Returns
+        one ``(mismatches, first_index, max_abs_diff, got_bits, expected_bits)``
+        per pair, ``first_index`` ``dtypes.COMPARE_NO_INDEX`` when nothing
+        mismatches."""
+        keep, tab = [], []
+        for got, exp, dt in pairs:
+            g, e = np.ascontiguousarray(got).reshape(-1), np.ascontiguousarray(exp).reshape(-1)
+            dtypes.code(dt)  # ValueError for a datatype the kernels do not know
+            if g.nbytes != e.nbytes or g.nbytes % dtypes.SIZES[dt]:
+                raise ValueError("compare_expected: got and expected must hold the same whole number of %s" % dt)
+            keep.append((g, e))
+            tab.append((g.ctypes.data, e.ctypes.data, g.nbytes // dtypes.SIZES[dt], dt))
+        rec = (dtypes.CompareRecord * max(len(tab), 1))()
+        if self._lib.tcamd_host_compare_expected(dtypes.compare_table(tab), len(tab), float(atol), float(rtol), rec):
+            raise ValueError("compare_expected: a pointer, datatype or tolerance the rule refuses")
+        return [rec[i].astuple() for i in range(len(tab))]
 
     # -- baseline JPEG (csrc/host/jpeg.cc) ---------------------------------------------
     @staticmethod

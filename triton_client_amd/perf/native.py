@@ -174,6 +174,22 @@ class PerfSession:
             raise PerfError(err.value.decode(errors="replace"))
         return dict(zip(POINT_KEYS, list(out)))
 
+    def validation(self):
+        """Output validation of the session (``--validate-outputs`` or the
+        ``validation_data`` of the input JSON): ``None`` when it is off, else
+        ``{"validated", "validation_failed", "first_failure"}`` over every
+        response so far."""
+        lib = _load()
+        lib.tcperf_validation.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64), ctypes.c_char_p, ctypes.c_int]
+        lib.tcperf_validation.restype = ctypes.c_int
+        out = (ctypes.c_uint64 * 3)()
+        msg = ctypes.create_string_buffer(1024)
+        lib.tcperf_validation(self._h, out, msg, 1024)
+        if not out[0]:
+            return None
+        return {"validated": int(out[1]), "validation_failed": int(out[2]),
+                "first_failure": msg.value.decode(errors="replace")}
+
     def describe(self):
         buf = ctypes.create_string_buffer(1024)
         _load().tcperf_describe(self._h, buf, 1024)

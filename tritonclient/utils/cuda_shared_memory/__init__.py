@@ -11,6 +11,7 @@ from ..hip_shared_memory import (  # noqa: F401
     HipSharedMemoryRegion as CudaSharedMemoryRegion,
     allocated_shared_memory_regions,
     as_shared_memory_tensor,
+    compare_shared_memory_region,
     create_shared_memory_region,
     destroy_shared_memory_region,
     get_contents_as_numpy,

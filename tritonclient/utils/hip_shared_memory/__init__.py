@@ -28,7 +28,9 @@ Differences by design:
     wire format of ``serialize_bf16_tensor``);
   - ``get_contents_as_numpy(..., datatype=...)``: a BF16/FP16/FP8 region read
     back as float32, widened on the device;
-  - ``fill_synthetic_data`` (K1 Philox).
+  - ``fill_synthetic_data`` (K1 Philox);
+  - ``compare_shared_memory_region``: a device-resident output checked against
+    expected arrays by K26 on the device, nothing copied back but the verdict.
 
 BYTES semantics are the reference's (``__init__.py:199-231``): an object array
 is the output of ``serialize_byte_tensor`` (its bytes are copied as-is; a
@@ -37,6 +39,7 @@ multi-element object array is concatenated, like the system-shm module) and an
 """
 
 import base64
+import ctypes
 import os
 
 import numpy as np
@@ -464,6 +467,97 @@ def get_contents_as_numpy(cuda_shm_handle, datatype, shape, offset=0, region_dat
     mv = memoryview(host)
     out[:] = [bytes(mv[o:o + ln]) for o, ln in zip(offs.tolist(), lens.tolist())]
     return out.reshape(shape)
+
+
+_NP_DATATYPE = {"?": "BOOL", "i1": "INT8", "i2": "INT16", "i4": "INT32", "i8": "INT64", "u1": "UINT8", "u2": "UINT16",
+                "u4": "UINT32", "u8": "UINT64", "f2": "FP16", "f4": "FP32", "f8": "FP64"}
+
+
+def compare_shared_memory_region(cuda_shm_handle, expected_arrays, atol=0.0, rtol=0.0, offset=0, datatype=None):
+    """Check a device-resident output against ``expected_arrays`` without
+    copying it to the host: the arrays are taken to lie back-to-back in the
+    region from ``offset`` on (as :func:`set_shared_memory_region` lays them
+    out), go up once, and K26 ``compare_expected`` compares all of them in one
+    call on the device.  Returns one ``(mismatches, first_index, max_abs_diff)``
+    per array: the elements that do not pass, the lowest such index (-1 when
+    there is none) and the largest ``|got - expected|`` over the finite pairs of
+    a float type (0.0 for the others).
+
+    With ``atol == rtol == 0`` an element passes iff its bytes are identical
+    (``-0.0`` against ``+0.0`` fails, a NaN passes only against the same bits).
+    Otherwise FP16 / BF16 / FP32 (in fp32) and FP64 (in fp64) elements pass on
+    equal bits, on two NaNs, or when both are finite and ``|got - expected| <=
+    atol + rtol * |expected|``; integer, BOOL and FP8 elements are always
+    compared by their bytes.  BYTES arrays are compared over their serialized
+    bytes, element index = byte index (an object array is the output of
+    ``serialize_byte_tensor``, as for :func:`set_shared_memory_region`).
+    ``datatype`` in BF16 / FP16 / FP8_E4M3 / FP8_E5M2 says what the region
+    holds, as in :func:`set_shared_memory_region`: float arrays are converted on
+    the GPU on the way up (BF16 by truncation), arrays of the type's own width
+    (``uint16`` bit patterns of BF16, ``float16``) go up as they are."""
+    _check_handle(cuda_shm_handle)
+    if not isinstance(expected_arrays, (list, tuple)):
+        raise CudaSharedMemoryException("expected_arrays must be specified as a list/tuple of numpy arrays")
+    for v in expected_arrays:
+        if not isinstance(v, np.ndarray):
+            raise CudaSharedMemoryException("expected_arrays must be specified as a list/tuple of numpy arrays")
+    if datatype is not None and datatype not in _NARROW:
+        raise CudaSharedMemoryException("datatype must be one of %s" % (sorted(_NARROW),))
+    if not (atol >= 0 and rtol >= 0 and atol != float("inf") and rtol != float("inf")):
+        raise CudaSharedMemoryException("atol and rtol must be finite and not negative")
+    hip = _hip()
+    from triton_client_amd.ops import dtypes
+
+    if len(expected_arrays) > hip.COMPARE_MAX_PAIRS:
+        raise CudaSharedMemoryException("at most %d arrays per call" % hip.COMPARE_MAX_PAIRS)
+    plan = []  # (convert?, host array, datatype name, element count, bytes in the region)
+    for v in expected_arrays:
+        if v.dtype == np.object_ or v.dtype.type == np.bytes_:
+            b = _as_bytes(v)
+            plan.append((False, b, "UINT8", b.size, b.size))
+        elif datatype is not None and v.dtype.kind == "f" and v.dtype != _NARROW[datatype]:
+            a = np.ascontiguousarray(v, dtype=np.float32).reshape(-1)
+            plan.append((True, a, datatype, a.size, a.size * dtypes.SIZES[datatype]))
+        else:
+            a = np.ascontiguousarray(v).reshape(-1)
+            key = a.dtype.str.lstrip("<>|=")
+            if datatype is not None and a.dtype.itemsize == dtypes.SIZES[datatype]:
+                name = datatype
+            elif key in _NP_DATATYPE:
+                name = _NP_DATATYPE[key]
+            else:
+                raise CudaSharedMemoryException("no Triton datatype for numpy dtype %s" % a.dtype)
+            plan.append((False, a.view(np.uint8), name, a.size, a.nbytes))
+    if offset + sum(p[4] for p in plan) > cuda_shm_handle._byte_size:
+        raise CudaSharedMemoryException("the expected arrays run past the end of the region")
+    if not plan:
+        return []
+    pad = lambda n: (n + 255) & ~255  # noqa: E731
+    ctx = _ctx(cuda_shm_handle)
+    try:
+        with ctx.lock:
+            total = sum(pad(p[4]) + (pad(4 * p[3]) if p[0] else 0) for p in plan) + pad(hip.COMPARE_RECORD_BYTES * len(plan))
+            base = ctx.scratch(total)
+            s = ctx.stream.handle
+            pairs, cur, got = [], base, cuda_shm_handle._base_addr + offset
+            for cvt, a, name, count, nb in plan:
+                if cvt and count:
+                    hip.memcpy_async(cur, a.ctypes.data, 4 * count, s)
+                    hip.convert(cur, "FP32", cur + pad(4 * count), name, count, "trunc", s)
+                    cur += pad(4 * count)
+                elif nb:
+                    hip.memcpy_async(cur, a.ctypes.data, nb, s)
+                pairs.append((got, cur, count, name))
+                cur += pad(nb)
+                got += nb
+            hip.compare_expected(pairs, cur, atol, rtol, s)
+            rec = (dtypes.CompareRecord * len(plan))()
+            hip.memcpy_async(ctypes.addressof(rec), cur, ctypes.sizeof(rec), s)
+            ctx.stream.synchronize()  # the host arrays above must outlive the async copies
+    except Exception as ex:
+        raise CudaSharedMemoryException("unable to compare cuda shared memory contents") from ex
+    return [(int(r.mismatches), -1 if r.first_index == dtypes.COMPARE_NO_INDEX else int(r.first_index),
+             float(r.max_abs_diff)) for r in rec]
 
 
 def set_shared_memory_region_from_dlpack(cuda_shm_handle, input_values, offset=0):

@@ -1,0 +1,226 @@
+#!/usr/bin/env python3
+"""Answer spans served against answer spans computed by the client, and K27
+``qa_spans`` alone.
+
+Served (default): one server with ``bert_large``, ``qa_spans`` and
+``bert_qa_ensemble``; a closed loop over gRPC at each ``--concurrency``, in two
+modes on that same server, alternating ``--reps`` times:
+
+  ensemble  ``bert_qa_ensemble``, asking only for ``spans``, ``scores`` and
+            ``null_score``: the logits never leave the device
+  client    ``bert_large`` raw, then the numpy routine of utils/qa.py on every
+            row of the response, inside the loop: what a user has to do
+            without the ``qa_spans`` model
+
+One JSON line per (mode, concurrency, rep): answered requests per second and
+latency percentiles, the latency including the client's span computation.
+
+``--kernel``: K27 alone on random logits, timed with HIP events around each
+launch after a warm-up, at (rows, n_best, max_answer_length) = (128, 20, 30),
+(128, 64, 384) and (1, 20, 30); next to it the host twin on the same rows.
+"""
+
+import argparse
+import json
+import os
+import sys
+import threading
+import time
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if REPO not in sys.path:
+    sys.path.insert(0, REPO)
+
+SEQ = 384
+KERNEL_POINTS = ((128, 20, 30), (128, 64, 384), (1, 20, 30))
+
+
+def make_inputs(rows, seed):
+    import numpy as np
+
+    rng = np.random.default_rng(seed)
+    ids = rng.integers(1000, 30000, size=(rows, SEQ), dtype=np.int32)
+    mask = np.ones((rows, SEQ), dtype=np.int32)
+    tt = np.zeros((rows, SEQ), dtype=np.int32)
+    for i in range(rows):
+        n = SEQ if i % 3 == 0 else int(rng.integers(32, SEQ))
+        q = int(rng.integers(8, max(9, n // 3)))
+        mask[i, n:] = 0
+        ids[i, n:] = 0
+        tt[i, q:n] = 1
+    return ids, mask, tt
+
+
+def kernel_time(iters):
+    import numpy as np
+    import torch
+
+    from triton_client_amd.ops import hip, host_codec
+
+    torch.cuda.set_device(0)
+    hc = host_codec.load()
+    s = torch.cuda.current_stream().cuda_stream
+    for rows, k, L in KERNEL_POINTS:
+        rng = np.random.default_rng(rows + k)
+        _, mask, tt = make_inputs(rows, 1)
+        st = rng.standard_normal((rows, SEQ)).astype(np.float32)
+        en = rng.standard_normal((rows, SEQ)).astype(np.float32)
+        d = [torch.from_numpy(a).cuda() for a in (st, en, mask, tt)]
+        k_row = torch.full((rows,), k, dtype=torch.int32, device="cuda")
+        len_row = torch.full((rows,), L, dtype=torch.int32, device="cuda")
+        spans = torch.zeros(rows, k, 2, dtype=torch.int32, device="cuda")
+        scores = torch.zeros(rows, k, dtype=torch.float32, device="cuda")
+        null = torch.zeros(rows, dtype=torch.float32, device="cuda")
+
+        def launch():
+            hip.qa_spans(d[0].data_ptr(), d[1].data_ptr(), SEQ * 4, d[2].data_ptr(), d[3].data_ptr(), SEQ * 4, rows,
+                         SEQ, k_row.data_ptr(), len_row.data_ptr(), k, spans.data_ptr(), scores.data_ptr(),
+                         null.data_ptr(), stream=s)
+
+        for _ in range(10):
+            launch()
+        torch.cuda.synchronize()
+        times = []
+        for _ in range(iters):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            launch()
+            b.record()
+            b.synchronize()
+            times.append(a.elapsed_time(b) * 1e3)
+        host = []
+        for _ in range(5):
+            t0 = time.perf_counter()
+            w_spans, w_scores, w_null = hc.qa_spans(st, en, mask, tt, [k] * rows, [L] * rows, k)
+            host.append((time.perf_counter() - t0) * 1e3)
+        same = (np.array_equal(spans.cpu().numpy(), w_spans)
+                and np.array_equal(scores.cpu().numpy().view(np.uint32), w_scores.view(np.uint32))
+                and np.array_equal(null.cpu().numpy().view(np.uint32), w_null.view(np.uint32)))
+        ok = (mask >= 1) & (tt == 1)
+        cands = sum(int(ok[r, i:i + L].sum()) for r in range(rows) for i in range(SEQ) if ok[r, i])
+        print(json.dumps({"kernel": "K27 qa_spans", "rows": rows, "n_best": k, "max_answer_length": L, "S": SEQ,
+                          "candidates": cands, "launches": iters, "mean_us": round(float(np.mean(times)), 2),
+                          "min_us": round(float(np.min(times)), 2), "max_us": round(float(np.max(times)), 2),
+                          "host_twin_ms_min": round(float(np.min(host)), 3), "equals_host_twin": bool(same)}),
+              flush=True)
+
+
+def closed_loop(c, mod, model, ins, outputs, conc, warmup, seconds, post):
+    """``conc`` requests in flight; ``post(result)`` runs in the callback, inside the measured latency."""
+    lock = threading.Lock()
+    done = threading.Event()
+    state = {"lat": [], "errors": 0, "stop": False, "inflight": conc, "measure": False}
+    outs = [mod.InferRequestedOutput(n) for n in outputs]
+
+    def send():
+        t0 = time.perf_counter()
+
+        def cb(result, error):
+            if error is None:
+                post(result)
+            t1 = time.perf_counter()
+            with lock:
+                if error is not None:
+                    state["errors"] += 1
+                elif state["measure"]:
+                    state["lat"].append(t1 - t0)
+                again = not state["stop"]
+                if not again:
+                    state["inflight"] -= 1
+                    if state["inflight"] == 0:
+                        done.set()
+            if again:
+                send()
+
+        c.async_infer(model, ins, callback=cb, outputs=outs)
+
+    for _ in range(conc):
+        send()
+    time.sleep(warmup)
+    with lock:
+        state["measure"] = True
+        state["lat"] = []
+    t0 = time.perf_counter()
+    time.sleep(seconds)
+    with lock:
+        lat = sorted(state["lat"])
+        state["measure"] = False
+    dt = time.perf_counter() - t0
+    with lock:
+        state["stop"] = True
+    done.wait(60)
+    n = len(lat)
+    return {"model": model, "concurrency": conc, "seconds": round(dt, 2), "requests": n, "errors": state["errors"],
+            "infer_per_s": round(n / dt, 1), "p50_ms": round(lat[n // 2] * 1e3, 3) if n else None,
+            "p99_ms": round(lat[min(n - 1, int(n * 0.99))] * 1e3, 3) if n else None}
+
+
+def served(args):
+    import numpy as np
+
+    import tritonclient.grpc as grpcclient
+    from triton_client_amd.perf.harness import ServerProcess
+    from triton_client_amd.utils import qa
+
+    log = os.path.abspath(args.server_log) if args.server_log else None
+    if log:
+        os.makedirs(os.path.dirname(log), exist_ok=True)
+    srv = ServerProcess(device=0, models="bert_large,qa_spans,bert_qa_ensemble", log_path=log,
+                        extra_args=["--native-grpc", args.native_grpc])
+    try:
+        srv.wait_ready(timeout=900, model="bert_qa_ensemble")
+        ids, mask, tt = make_inputs(args.rows, 0)
+        c = grpcclient.InferenceServerClient(srv.grpc_url)
+        ins = []
+        for name, a in (("input_ids", ids), ("attention_mask", mask), ("token_type_ids", tt)):
+            x = grpcclient.InferInput(name, list(a.shape), "INT32")
+            x.set_data_from_numpy(a)
+            ins.append(x)
+
+        def client_spans(result):
+            st, en = result.as_numpy("start_logits"), result.as_numpy("end_logits")
+            return [qa.n_best_spans(st[i], en[i], mask[i], tt[i], 20, 30) for i in range(args.rows)]
+
+        # the two modes answer alike: the ensemble's spans are the client's routine on the ensemble's own logits
+        r = c.infer("bert_qa_ensemble", ins)
+        mine = client_spans(r)
+        agree = all(np.array_equal(r.as_numpy("spans")[i], mine[i][0])
+                    and np.array_equal(r.as_numpy("scores")[i].view(np.uint32), mine[i][1].view(np.uint32))
+                    for i in range(args.rows))
+        modes = {"ensemble": ("bert_qa_ensemble", ["spans", "scores", "null_score"], lambda result: None),
+                 "client": ("bert_large", ["start_logits", "end_logits"], client_spans)}
+        for rep in range(args.reps):
+            for conc in args.concurrency:
+                for mode, (model, outputs, post) in modes.items():
+                    res = closed_loop(c, grpcclient, model, ins, outputs, conc, args.warmup, args.seconds, post)
+                    res.update(mode=mode, rep=rep, rows_per_request=args.rows, n_best=20, max_answer_length=30,
+                               ensemble_equals_client_routine=bool(agree), native_grpc=args.native_grpc,
+                               device_qa_spans=os.environ.get("TCAMD_DEVICE_QA_SPANS", "1") != "0")
+                    print(json.dumps(res), flush=True)
+        c.close()
+    finally:
+        srv.stop()
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--kernel", action="store_true", help="time K27 alone instead of the served loops")
+    ap.add_argument("--iters", type=int, default=200, help="--kernel: timed launches per point (after 10 warm-up)")
+    ap.add_argument("--concurrency", type=int, nargs="+", default=[1, 8])
+    ap.add_argument("--rows", type=int, default=1, help="rows per request")
+    ap.add_argument("--reps", type=int, default=2, help="rounds over the concurrencies and modes")
+    ap.add_argument("--seconds", type=float, default=8.0)
+    ap.add_argument("--warmup", type=float, default=2.0)
+    ap.add_argument("--native-grpc", default="auto", choices=["auto", "on", "off"],
+                    help="the server's gRPC front end: the native one answers bert_large itself and relays an "
+                         "ensemble to the Python one; off = the Python front end answers both modes")
+    ap.add_argument("--server-log", default="", metavar="PATH", help="keep the server's log in this file")
+    args = ap.parse_args()
+    if args.kernel:
+        kernel_time(args.iters)
+    else:
+        served(args)
+
+
+if __name__ == "__main__":
+    main()

@@ -16,6 +16,7 @@ events, peer access.  Kernels (csrc/kernels/*.hip, gfx950):
 * :func:`pack_bytes`      K2 BYTES serialisation (LDS block scan + scatter)
 * :func:`index_bytes`     K3 BYTES index walk through an LDS window
 * :func:`topk_rows`       K19 per-row top-K {score, index} pairs (classification)
+* :func:`qa_spans`        K27 per-row n best answer spans of question-answering logits
 
 Pointers are plain ints (device addresses).  ``stream`` is a hipStream_t as an
 int (``torch.cuda.current_stream().cuda_stream`` works) or None for the
@@ -188,6 +189,14 @@ _SIGS = {
         [
             ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32,
             ctypes.c_void_p, ctypes.c_void_p,
+        ],
+        ctypes.c_int,
+    ),
+    "tcamd_qa_spans": (
+        [
+            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64,
+            ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p,
+            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
         ],
         ctypes.c_int,
     ),
@@ -956,6 +965,33 @@ def topk_rows(x_ptr, row_stride_bytes, rows, C, k_row_ptr, kmax, pairs_ptr, stre
     ``kmax`` above :data:`TOPK_KMAX` raises (hipErrorInvalidValue) without a launch."""
     _check(_load().tcamd_topk_rows(_vp(x_ptr), int(row_stride_bytes), int(rows), int(C), _vp(k_row_ptr), int(kmax),
                                    _vp(pairs_ptr), _vp(stream)), "topk_rows")
+
+
+QA_SPANS_KMAX = 64  # tcamd_qa::kKMax (csrc/kernels/qa_span_math.h)
+QA_SPANS_MAX_SEQ = 1024  # tcamd_qa::kMaxSeq
+
+
+def qa_spans(start_ptr, end_ptr, logit_stride_bytes, mask_ptr, token_type_ptr, ids_stride_bytes, rows, S, k_row_ptr,
+             len_row_ptr, kmax, spans_ptr, scores_ptr, null_score_ptr, stream=None):
+    """K27: the n best answer spans of each row of question-answering logits.
+    ``start`` / ``end`` are device fp32 rows of ``S`` values ``logit_stride_bytes``
+    apart, ``mask`` / ``token_type`` device int32 rows ``ids_stride_bytes`` apart;
+    ``k_row`` and ``len_row`` are device int32 arrays, the answers wanted of each
+    row and its longest answer in tokens.  A candidate is a pair ``s <= e`` with
+    ``e - s < len_row[r]`` of tokens with ``mask >= 1`` and ``token_type == 1``;
+    its score is ``start[s] + end[e]``; candidates order like K19 with the index
+    ``s * S + e`` (csrc/kernels/qa_span_math.h).  Row ``r`` gets its first
+    ``min(k_row[r], kmax)`` ranks as int32 ``spans[r][:kmax][2]`` and fp32
+    ``scores[r][:kmax]``, ranks past its candidates as ``(-1, -1)`` and
+    ``-FLT_MAX``, and ``null_score[r] = start[0] + end[0]``; ``k_row[r] < 1``
+    skips the row and slots past a row's count are left untouched.  ``S`` outside
+    1..:data:`QA_SPANS_MAX_SEQ`, ``kmax`` outside 1..:data:`QA_SPANS_KMAX`, a null
+    or misaligned pointer, a stride that is no multiple of 4 or shorter than a
+    row, or negative ``rows`` raises (hipErrorInvalidValue) without a launch."""
+    _check(_load().tcamd_qa_spans(_vp(start_ptr), _vp(end_ptr), int(logit_stride_bytes), _vp(mask_ptr),
+                                  _vp(token_type_ptr), int(ids_stride_bytes), int(rows), int(S), _vp(k_row_ptr),
+                                  _vp(len_row_ptr), int(kmax), _vp(spans_ptr), _vp(scores_ptr), _vp(null_score_ptr),
+                                  _vp(stream)), "qa_spans")
 
 
 def dn_conv1x1(x, ldx, M, K, in_scale, in_bias, w, N, out_bias, relu_out, y, ldy, pool=0, H=0, W=0, stream=None,

@@ -1,4 +1,5 @@
-"""ctypes binding of libtcamd_host.so (BYTES pack / scan, baseline JPEG and PNG on the host, the compare rule)."""
+"""ctypes binding of libtcamd_host.so (BYTES pack / scan, baseline JPEG and PNG on the host, the compare rule,
+the answer-span rule)."""
 import ctypes
 import os
 
@@ -123,6 +124,11 @@ class HostCodec:
         lib.tcamd_host_compare_expected.argtypes = [ctypes.POINTER(dtypes.ComparePair), ctypes.c_int, ctypes.c_double,
                                                     ctypes.c_double, ctypes.POINTER(dtypes.CompareRecord)]
         lib.tcamd_host_compare_expected.restype = ctypes.c_int
+        lib.tcamd_host_qa_spans.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
+                                            ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int32, ctypes.c_int32,
+                                            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p,
+                                            ctypes.c_void_p, ctypes.c_void_p]
+        lib.tcamd_host_qa_spans.restype = ctypes.c_int
         lib.tcamd_host_pack_bytes.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]
         lib.tcamd_host_pack_bytes.restype = ctypes.c_int
         lib.tcamd_host_count_bytes.argtypes = [ctypes.c_void_p, ctypes.c_uint64]
@@ -185,6 +191,48 @@ class HostCodec:
         if self._lib.tcamd_host_compare_expected(dtypes.compare_table(tab), len(tab), float(atol), float(rtol), rec):
             raise ValueError("compare_expected: a pointer, datatype or tolerance the rule refuses")
         return [rec[i].astuple() for i in range(len(tab))]
+
+    # -- the answer-span rule (csrc/kernels/qa_span_math.h) ------------------------------
+    def qa_spans_raw(self, start_ptr, end_ptr, logit_stride_bytes, mask_ptr, token_type_ptr, ids_stride_bytes, rows, S,
+                     k_row_ptr, len_row_ptr, kmax, spans_ptr, scores_ptr, null_score_ptr):
+        """``ops.hip.qa_spans`` on host addresses, argument for argument (no
+        stream); ``ValueError`` for what the device entry refuses."""
+        if self._lib.tcamd_host_qa_spans(start_ptr, end_ptr, int(logit_stride_bytes), mask_ptr, token_type_ptr,
+                                         int(ids_stride_bytes), int(rows), int(S), k_row_ptr, len_row_ptr, int(kmax),
+                                         spans_ptr, scores_ptr, null_score_ptr):
+            raise ValueError("qa_spans: a size, pointer or stride the rule refuses")
+
+    def qa_spans(self, start, end, attention_mask, token_type_ids, k_row, len_row, kmax=None):
+        """K27 ``qa_spans`` on the host, bit for bit: ``start`` / ``end`` fp32
+        ``[rows, S]``, ``attention_mask`` / ``token_type_ids`` int32 ``[rows, S]``,
+        ``k_row`` / ``len_row`` int32 ``[rows]`` (the answers wanted and the
+        longest answer of each row), ``kmax`` the ranks of the outputs (default:
+        the largest ``k_row``, at least 1).  Returns ``(spans, scores,
+        null_score)``: int32 ``[rows, kmax, 2]``, fp32 ``[rows, kmax]`` and fp32
+        ``[rows]``.  Ranks past a row's candidates hold ``(-1, -1)`` and
+        ``-FLT_MAX``; ranks past ``k_row[r]``, and everything of a row with
+        ``k_row[r] < 1``, hold zeros (the routine does not write them)."""
+        st = np.ascontiguousarray(start, dtype=np.float32)
+        en = np.ascontiguousarray(end, dtype=np.float32)
+        mk = np.ascontiguousarray(attention_mask, dtype=np.int32)
+        tt = np.ascontiguousarray(token_type_ids, dtype=np.int32)
+        if st.ndim != 2 or not (st.shape == en.shape == mk.shape == tt.shape):
+            raise ValueError("qa_spans: the four inputs must be [rows, S] arrays of one shape")
+        rows, S = st.shape
+        k = np.ascontiguousarray(k_row, dtype=np.int32).reshape(-1)
+        ln = np.ascontiguousarray(len_row, dtype=np.int32).reshape(-1)
+        if k.size != rows or ln.size != rows:
+            raise ValueError("qa_spans: k_row and len_row must have one entry per row")
+        if kmax is None:
+            kmax = max(1, int(k.max())) if rows else 1
+        spans = np.zeros((rows, kmax, 2), dtype=np.int32)
+        scores = np.zeros((rows, kmax), dtype=np.float32)
+        null = np.zeros((max(rows, 1),), dtype=np.float32)
+        one = np.zeros(1, dtype=np.int32)  # rows == 0: the entry still wants non-null pointers
+        ptr = lambda a: a.ctypes.data if a.size else one.ctypes.data  # noqa: E731
+        self.qa_spans_raw(ptr(st), ptr(en), S * 4, ptr(mk), ptr(tt), S * 4, rows, S, ptr(k), ptr(ln), kmax,
+                          ptr(spans), ptr(scores), null.ctypes.data)
+        return spans, scores, null[:rows]
 
     # -- baseline JPEG (csrc/host/jpeg.cc) ---------------------------------------------
     @staticmethod

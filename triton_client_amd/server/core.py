@@ -842,7 +842,10 @@ class InferenceServer:
                     ens = omap[o.name]
                     tensors[ens] = InputTensor(ens, o.datatype, list(o.shape), o.data)
         outs = []
+        wanted = {ro.name for ro in request.outputs}
         for spec in inst.outputs:
+            if wanted and spec.name not in wanted:
+                continue  # not asked for: a tensor a step left on the device is never copied down
             t = tensors.get(spec.name)
             if t is None:
                 raise internal("ensemble output '%s' was not produced" % spec.name)

@@ -16,6 +16,9 @@ Behaviour is pinned by the reference's example/test expectations:
   (simple_grpc_custom_repeat.py:78-152).
 * ``preprocess_inception`` + ``preprocess_inception_ensemble`` — BYTES image ->
   tensor -> classifier ensemble (ensemble_image_client.py).
+
+Not from the reference: ``qa_spans``, the answer-span step behind ``bert_large``
+(examples/python/bert_qa_client.py), here on the host twin of K27.
 """
 
 import threading
@@ -436,7 +439,106 @@ class BertSink(Model):
         b.timing_ns[0] = b.timing_ns[1] = b.timing_ns[2] = 0
 
 
+class QaSpans(Model):
+    """``qa_spans`` — the n best answer spans of question-answering logits, the
+    step after ``bert_large``: FP32 [384] ``start_logits`` / ``end_logits`` and
+    INT32 [384] ``attention_mask`` / ``token_type_ids`` in; per row INT32
+    ``spans`` [n_best, 2] (first and last token), FP32 ``scores`` [n_best] and
+    FP32 ``null_score`` [1] (``start[0] + end[0]``, the SQuAD-v2 no-answer
+    score) out.  The rule is csrc/kernels/qa_span_math.h: both ends on context
+    tokens (``attention_mask >= 1`` and ``token_type_ids == 1``), at most
+    ``max_answer_length`` tokens, scores descending, ties to the lower start
+    and then the lower end; ranks past the candidates hold ``(-1, -1)`` and
+    ``-FLT_MAX``.  This class runs the host twin of K27 (``HostCodec.qa_spans``),
+    one call per batch; server/gpu_models.py QaSpans runs the kernel.
+
+    Custom request parameters: ``n_best`` (int64, 1..64, default 20) and
+    ``max_answer_length`` (int64, 1..384, default 30).  Requests of different
+    ``n_best`` share a batch.  A value out of range or of another type fails
+    its own request."""
+
+    name = "qa_spans"
+    max_batch_size = 128
+    SEQ = 384
+    N_BEST, N_BEST_MAX = 20, 64
+    MAX_ANSWER, MAX_ANSWER_MAX = 30, 384
+    inputs = (TensorSpec("start_logits", "FP32", [384]), TensorSpec("end_logits", "FP32", [384]),
+              TensorSpec("attention_mask", "INT32", [384]), TensorSpec("token_type_ids", "INT32", [384]))
+    outputs = (TensorSpec("spans", "INT32", [-1, 2]), TensorSpec("scores", "FP32", [-1]),
+               TensorSpec("null_score", "FP32", [1]))
+    dynamic_batching = {"preferred": [], "max_queue_delay_us": 100}
+    INPUT_DTYPES = (np.float32, np.float32, np.int32, np.int32)
+
+    @staticmethod
+    def _int_param(request, name, default, lo, hi):
+        v = request.parameters.get(name, default)
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= v <= hi:
+            raise ServerError("request parameter %s must be an int64 in [%d, %d], not %r" % (name, lo, hi, v))
+        return int(v)
+
+    @classmethod
+    def plan(cls, requests):
+        """Per request ``(first_row, rows, n_best, max_answer_length)``, or the
+        ServerError of its parameters; and the rows of the batch."""
+        out, total = [], 0
+        for r in requests:
+            try:
+                k = cls._int_param(r, "n_best", cls.N_BEST, 1, cls.N_BEST_MAX)
+                ln = cls._int_param(r, "max_answer_length", cls.MAX_ANSWER, 1, cls.MAX_ANSWER_MAX)
+            except ServerError as e:
+                out.append(e)
+                continue
+            n = int(r.input("start_logits").shape[0])
+            out.append((total, n, k, ln))
+            total += n
+        return out, total
+
+    @staticmethod
+    def row_params(plan, total):
+        """(k_row, len_row, kmax) of a batch's plan."""
+        k_row, len_row = np.zeros(total, dtype=np.int32), np.zeros(total, dtype=np.int32)
+        for p in plan:
+            if not isinstance(p, Exception):
+                first, n, k, ln = p
+                k_row[first:first + n] = k
+                len_row[first:first + n] = ln
+        return k_row, len_row, int(k_row.max()) if total else 1
+
+    def results(self, plan, spans, scores, null):
+        """The per-request outputs from the batch's [rows, kmax(, 2)] arrays."""
+        res = []
+        for p in plan:
+            if isinstance(p, Exception):
+                res.append(p)
+                continue
+            first, n, k, _ = p
+            res.append([self.out("spans", np.ascontiguousarray(spans[first:first + n, :k])),
+                        self.out("scores", np.ascontiguousarray(scores[first:first + n, :k])),
+                        self.out("null_score", np.ascontiguousarray(null[first:first + n]).reshape(n, 1))])
+        return res
+
+    def load(self):
+        from triton_client_amd.ops import host_codec
+
+        self._codec = host_codec.load()
+
+    def run_host(self, requests, plan, total):
+        names = [s.name for s in self.inputs]
+        good = [r for r, p in zip(requests, plan) if not isinstance(p, Exception)]
+        cols = [np.concatenate([np.asarray(r.input(nm).numpy(), dtype=dt).reshape(-1, self.SEQ) for r in good])
+                for nm, dt in zip(names, self.INPUT_DTYPES)]
+        k_row, len_row, kmax = self.row_params(plan, total)
+        return self._codec.qa_spans(*cols, k_row, len_row, kmax)
+
+    def execute(self, requests):
+        plan, total = self.plan(requests)
+        if total == 0:
+            return plan
+        return self.results(plan, *self.run_host(requests, plan, total))
+
+
 CPU_MODELS = [
+    QaSpans,
     FrontendSink,
     BertSink,
     SimpleAddSub,

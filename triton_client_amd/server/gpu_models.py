@@ -1028,6 +1028,8 @@ class BertLarge(Model):
                     a = np.ascontiguousarray(t.data, dtype=np.int32)
                     keep.append(a)
                     srcs[k].append((0, a.ctypes.data, n))
+        if all(getattr(r, "accepts_device_outputs", False) for r in requests):
+            return self._execute_device_outputs(requests, plan, srcs, total)
         # outputs come back to host; shm targets are filled by the server (deliver_to_shm)
         res = np.empty((2, total, self.SEQ), dtype=np.float32)
         outs = [[(0, res[k].ctypes.data, 0, total)] for k in range(2)]
@@ -1041,6 +1043,37 @@ class BertLarge(Model):
         del ctypes
         return [[OutputTensor("start_logits", "FP32", [n, self.SEQ], res[0, f:f + n]),
                  OutputTensor("end_logits", "FP32", [n, self.SEQ], res[1, f:f + n])] for _, f, n in plan]
+
+    def _execute_device_outputs(self, requests, plan, srcs, total):
+        """A batch of ensemble steps (``accepts_device_outputs`` on every request,
+        core._infer_ensemble): the logits stay on the device.  The rows go from
+        the slot's output buffers, which the next batch overwrites, into a tensor
+        of this batch's own (K7 batched_copy on the slot's stream, inside
+        _run_batch), and each request gets its rows of it as ``DeviceView`` with
+        the tensor as ``owner``."""
+        torch = self.torch
+        row = self.SEQ * 4
+        i = self._acquire()
+        try:
+            slot = self._slots[i]
+            with torch.cuda.stream(slot["stream"]):
+                res = torch.empty((2, total, self.SEQ), device=slot["stream"].device, dtype=torch.float32)
+            outs = [[(1, res[k].data_ptr(), 0, total)] for k in range(2)]
+            t = self._run_batch(slot, srcs, outs, total)  # ends with a stream synchronise
+        finally:
+            self._release(i)
+        if self._batch_stats is not None:
+            self._batch_stats(total, len(requests), *t)
+        out = []
+        for _, f, n in plan:
+            tensors = []
+            for k, nm in enumerate(("start_logits", "end_logits")):
+                o = OutputTensor(nm, "FP32", [n, self.SEQ],
+                                 DeviceView(res[k].data_ptr() + f * row, n * row, self.device_id))
+                o.owner = res  # keeps the device memory alive while the ensemble holds the tensor
+                tensors.append(o)
+            out.append(tensors)
+        return out
 
     _batch_stats = None
     reports_batch_stats = True
@@ -1070,7 +1103,207 @@ class BertLargeFP32(BertLarge):
         return bert.prepare_x3(bert.build(device=dev, dtype=torch.float32, layers=self.layers))
 
 
-GPU_MODELS = [DensenetOnnx, PreprocessInception, PreprocessInceptionEnsemble, BertLarge]
+class QaSpans(Model):
+    """``qa_spans`` on the GPU: the same I/O contract, request parameters and
+    rule as the CPU model of that name (server/cpu_models.py QaSpans), which it
+    replaces on a ``--gpu`` server and whose parameter checks it uses.
+
+    Per batch, K27 ``qa_spans`` (csrc/kernels/qa_spans.hip) picks every row's
+    spans on the slot's stream; requests of different ``n_best`` and
+    ``max_answer_length`` share the launch through the kernel's per-row
+    ``k_row`` / ``len_row`` arrays.  An input that arrives as ``DeviceView`` (a
+    HIP shm region, or the logits ``bert_large`` left on the device for the
+    ensemble) is read in place; a host input goes up through the slot's pinned
+    staging buffer, one copy per tensor.  The kernel reads rows at one stride
+    from one base, so a batch is launched once per run of requests whose four
+    tensors each follow the previous request's in memory: once when everything
+    is staged or comes from one ``bert_large`` batch in order.  The outputs of
+    the batch come back in one copy of ``rows * (kmax * 12 + 4)`` bytes.
+    ``TCAMD_DEVICE_QA_SPANS=0`` (read at load) runs the host twin instead."""
+
+    name = "qa_spans"
+    max_batch_size = 128
+    SEQ = 384
+    inputs = (TensorSpec("start_logits", "FP32", [384]), TensorSpec("end_logits", "FP32", [384]),
+              TensorSpec("attention_mask", "INT32", [384]), TensorSpec("token_type_ids", "INT32", [384]))
+    outputs = (TensorSpec("spans", "INT32", [-1, 2]), TensorSpec("scores", "FP32", [-1]),
+               TensorSpec("null_score", "FP32", [1]))
+    dynamic_batching = {"preferred": [], "max_queue_delay_us": 100}
+    instance_kind = "KIND_GPU"
+    instance_count = 2
+    gpus = (0,)
+
+    def __init__(self, version=1, device_id=0, **kw):
+        super().__init__(version, **kw)
+        self.device_id = int(kw.get("device", device_id))
+        self._slots = []
+        self._free = []
+        self._cv = threading.Condition()
+        self._host = None
+
+    def load(self):
+        from .cpu_models import QaSpans as HostQaSpans
+
+        self._host = HostQaSpans(self.version)
+        self._host.load()
+        self.device_path = os.environ.get("TCAMD_DEVICE_QA_SPANS", "1") != "0"
+        if not self.device_path:
+            return
+        import torch
+
+        from triton_client_amd.ops import hip
+
+        if not torch.cuda.is_available():
+            raise ServerError("qa_spans (GPU) requires a GPU")
+        hip.lib()  # fail loudly if the native kernels are missing
+        self.torch = torch
+        dev = torch.device("cuda", self.device_id)
+        n, row = self.max_batch_size, self.SEQ * 4
+        self.in_bytes = 4 * n * row + 2 * n * 4  # the four tensors, then k_row and len_row
+        self.out_bytes = n * (hip.QA_SPANS_KMAX * 12 + 4)
+        for _ in range(max(1, self.instance_count)):
+            self._slots.append({
+                "stream": torch.cuda.Stream(device=dev),
+                "in_host": hip.host_alloc(self.in_bytes),
+                "out_host": hip.host_alloc(self.out_bytes),
+                "in_dev": torch.zeros(self.in_bytes, device=dev, dtype=torch.uint8),
+                "out_dev": torch.zeros(self.out_bytes, device=dev, dtype=torch.uint8),
+            })
+        self._free = list(range(len(self._slots)))
+
+    def unload(self):
+        from triton_client_amd.ops import hip
+
+        for s in self._slots:
+            for k in ("in_host", "out_host"):
+                try:
+                    hip.host_free(s[k])
+                except Exception:
+                    pass
+        self._slots = []
+        self._free = []
+
+    def _acquire(self):
+        with self._cv:
+            while not self._free:
+                self._cv.wait()
+            return self._free.pop()
+
+    def _release(self, i):
+        with self._cv:
+            self._free.append(i)
+            self._cv.notify()
+
+    def execute(self, requests):
+        plan, total = self._host.plan(requests)
+        if total == 0:
+            return plan
+        if total > self.max_batch_size:
+            return [ServerError("batch of %d rows exceeds max_batch_size" % total)] * len(requests)
+        if not self.device_path:
+            return self._host.results(plan, *self._host.run_host(requests, plan, total))
+        from triton_client_amd.ops import hip
+
+        i = self._acquire()
+        try:
+            return self._host.results(plan, *self._execute(self._slots[i], requests, plan, total))
+        except (ServerError, hip.HipError) as e:
+            err = e if isinstance(e, ServerError) else ServerError("qa_spans: %s" % e)
+            return [p if isinstance(p, Exception) else err for p in plan]
+        finally:
+            self._release(i)
+
+    def _execute(self, slot, requests, plan, total):
+        import ctypes
+
+        from triton_client_amd.ops import hip
+
+        n_max, row = self.max_batch_size, self.SEQ * 4
+        sh = slot["stream"].cuda_stream
+        in_host, in_dev = slot["in_host"], slot["in_dev"].data_ptr()
+        k_row, len_row, kmax = self._host.row_params(plan, total)
+        par = 4 * n_max * row  # k_row and len_row: one copy
+        pars = np.ctypeslib.as_array((ctypes.c_int32 * (2 * n_max)).from_address(in_host + par))
+        pars[:total] = k_row
+        pars[n_max:n_max + total] = len_row
+        hip.memcpy_async(in_dev + par, in_host + par, 2 * n_max * 4, sh)
+        good = [(r, p) for r, p in zip(requests, plan) if not isinstance(p, Exception)]
+        at = []  # per tensor: where each good request's rows are on the device
+        for c, spec in enumerate(self.inputs):
+            base = c * n_max * row
+            dt = np.float32 if spec.datatype == "FP32" else np.int32
+            stage = np.ctypeslib.as_array((ctypes.c_uint8 * (n_max * row)).from_address(in_host + base)).view(dt)
+            lo, hi, where = None, 0, []
+            for r, (first, n, _, _) in good:
+                t = r.input(spec.name)
+                if isinstance(t.data, DeviceView):
+                    if t.data.nbytes < n * row:
+                        raise ServerError("input region too small for %s" % spec.name)
+                    where.append(t.data.ptr)
+                    continue
+                stage[first * self.SEQ:(first + n) * self.SEQ] = np.asarray(t.data, dtype=dt).reshape(-1)
+                lo, hi = first if lo is None else lo, first + n
+                where.append(in_dev + base + first * row)
+            if lo is not None:
+                hip.memcpy_async(in_dev + base + lo * row, in_host + base + lo * row, (hi - lo) * row, sh)
+            at.append(where)
+        out_dev = slot["out_dev"].data_ptr()
+        o_scores, o_null = total * kmax * 8, total * kmax * 12
+        # one launch per run of requests that follow each other in memory, tensor by tensor
+        g = 0
+        while g < len(good):
+            first = good[g][1][0]
+            h, rows = g + 1, good[g][1][1]
+            while h < len(good) and all(w[h] == w[g] + (good[h][1][0] - first) * row for w in at):
+                rows += good[h][1][1]
+                h += 1
+            hip.qa_spans(at[0][g], at[1][g], row, at[2][g], at[3][g], row, rows, self.SEQ,
+                         in_dev + par + first * 4, in_dev + par + (n_max + first) * 4, kmax,
+                         out_dev + first * kmax * 8, out_dev + o_scores + first * kmax * 4,
+                         out_dev + o_null + first * 4, stream=sh)
+            g = h
+        nbytes = total * (kmax * 12 + 4)
+        hip.memcpy_async(slot["out_host"], out_dev, nbytes, sh)
+        hip.stream_synchronize(sh)
+        raw = np.ctypeslib.as_array((ctypes.c_uint8 * nbytes).from_address(slot["out_host"])).copy()
+        return (raw[:o_scores].view(np.int32).reshape(total, kmax, 2),
+                raw[o_scores:o_null].view(np.float32).reshape(total, kmax),
+                raw[o_null:].view(np.float32))
+
+
+class BertQaEnsemble(Model):
+    """Ensemble: token ids -> ``bert_large`` -> ``qa_spans``.  The logits stay
+    on the device between the steps (``bert_large`` hands them over as
+    ``DeviceView``, K27 reads them in place); the second step takes the
+    request's own ``attention_mask`` and ``token_type_ids``.  ``n_best`` and
+    ``max_answer_length`` reach ``qa_spans`` as the ensemble's custom request
+    parameters.  ``start_logits`` / ``end_logits`` are outputs too, so a client
+    can see the logits its spans were picked from; a request that does not ask
+    for them does not pay for their copy."""
+
+    name = "bert_qa_ensemble"
+    platform = "ensemble"
+    backend = ""
+    max_batch_size = 128
+    inputs = BertLarge.inputs
+    outputs = QaSpans.outputs + BertLarge.outputs
+    ensemble_steps = [
+        ("bert_large", {"input_ids": "input_ids", "attention_mask": "attention_mask",
+                        "token_type_ids": "token_type_ids"},
+         {"start_logits": "start_logits", "end_logits": "end_logits"}),
+        ("qa_spans", {"start_logits": "start_logits", "end_logits": "end_logits", "attention_mask": "attention_mask",
+                      "token_type_ids": "token_type_ids"},
+         {"spans": "spans", "scores": "scores", "null_score": "null_score"}),
+    ]
+
+    def load(self):
+        pass
+
+    def execute(self, requests):  # pragma: no cover - the server runs ensembles step by step
+        raise ServerError("ensemble models are scheduled by the server")
+
+
+GPU_MODELS = [DensenetOnnx, PreprocessInception, PreprocessInceptionEnsemble, BertLarge, QaSpans, BertQaEnsemble]
 # loaded only when --models names them: bert_large_fp32 adds ~2 GB of bf16x3
 # weights and 28 captured HIP graphs per instance (round-5 advisor finding)
 OPT_IN_GPU_MODELS = [BertLargeFP32]

@@ -101,6 +101,9 @@ KNOBS = [
          "PNG: 1 = the host inflates a non-interlaced file into the staging area and K25 png_unfilter reverses the "
          "filters and converts the samples on the device; 0 = the host decodes it and the pixels go up",
          "tests/test_png_gpu.py::test_the_png_knob_changes_the_route_and_not_one_bit_of_the_rows"),
+    Knob("TCAMD_DEVICE_QA_SPANS", "python", 1, "server/gpu_models.py",
+         "GPU qa_spans: K27 qa_spans picks the answer spans on the device; 0 = the host twin of the same rule",
+         "tests/test_qa_spans_gpu.py::test_the_knob_changes_the_route_and_not_one_bit_of_the_spans"),
     Knob("TCAMD_BYTES_HOST_MAX", "python", 8192, "tritonclient/utils/hip_shared_memory",
          "BYTES set with bytes_path=auto: host codec up to this many elements, K2 above",
          "tests/test_knobs.py::test_bytes_auto_path_knobs"),

@@ -657,8 +657,7 @@ __global__ void __launch_bounds__(64 * NW) attention_x3_kernel(const float* __re
   __syncthreads();
   const int nch = S / 64;
   for (int ci = 0; ci < nch; ++ci) {
-    uint8_t* const kh = ldsa + (ci & 1) * kBufAX;
-    uint8_t* const kl = kh + 64 * kXR;
+    uint8_t* const kh = ldsa + (ci & 1) * kBufAX;  // K lo follows at kh + 64 * kXR
     uint8_t* const vth = kh + 128 * kXR;
     uint8_t* const vtl = kh + 192 * kXR;
     const float* const kb = reinterpret_cast<const float*>(kh + 256 * kXR);

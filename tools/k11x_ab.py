@@ -4,6 +4,9 @@ interleaved (v1, v3, v1, v3, ...) so box drift hits both arms alike, and
 check every version against v1's output.
 
     python tools/k11x_ab.py --shapes 56:64,56:224,28:128,28:480 --imgs 128 --versions 1,3
+
+Version 5 is the K11w probe (tools/probes/k11w.hip): it needs TCAMD_HIP_LIB to
+name a library that exports its entry point (tools/probes/k11w.py says how).
 """
 import argparse
 import json
@@ -30,8 +33,13 @@ def main():
 
     dev = "cuda"
     st = torch.cuda.current_stream().cuda_stream
-    fns = {1: hip.x3_dense_fused, 3: hip.x3_dense_fused3, 5: hip.x3_dense_fused_ws}
+    fns = {1: hip.x3_dense_fused, 3: hip.x3_dense_fused3}
     vers = [int(v) for v in a.versions.split(",")]
+    if 5 in vers:
+        sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "probes"))
+        import k11w
+
+        fns[5] = k11w.require()  # exits with the build instructions when the symbol is missing
     rows = []
     for imgs in [int(v) for v in a.imgs.split(",")]:
         for sh in a.shapes.split(","):

@@ -1,22 +1,22 @@
 #!/usr/bin/env python3
-"""Build timing-ablation variants of the K11w kernel into k12ab/ (git-ignored
-scratch libraries, never the production one): each patches the source in a
-temporary copy, compiles densenet_x3.hip and links it with the tree's other
-kernel objects.  tools/probes/k11w_ablate.sh times them with k11x_ab.py.
+"""Build timing-ablation variants of the K11w probe kernel into k12ab/
+(git-ignored scratch libraries, never the production one): each patches
+tools/probes/k11w.hip in a temporary copy and links it in place of
+densenet_x3.o with the tree's other kernel objects (build_variant.py; make
+must have run).  tools/probes/k11w_ablate.sh times them with k11x_ab.py.
 
   noconv : producers skip the conversion (no VALU, no stage writes)
   nomma1 : consumers skip the 1x1 MFMAs (operand reads kept)
   no3x3  : consumers skip the 3x3 MFMAs (operand reads kept)
   pf4/pf6: producer X steps in flight; noprio: producers without s_setprio 1
 """
-import glob
 import os
-import subprocess
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-SRC = os.path.join(ROOT, "csrc/kernels/densenet_x3.hip")
-HIPCC = "/opt/rocm/bin/hipcc"
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import build_variant  # noqa: E402
+
+SRC = os.path.join(build_variant.ROOT, "tools/probes/k11w.hip")
 
 
 def patch_last(s, old, new):
@@ -42,26 +42,12 @@ def variants(s):
 
 def main():
     s = open(SRC).read()
-    objs = [o for o in glob.glob(os.path.join(ROOT, "build/*/*.o")) if not o.endswith("/densenet_x3.o")]
-    out = os.path.join(ROOT, "k12ab")
-    os.makedirs(out, exist_ok=True)
     only = set(sys.argv[1].split(",")) if len(sys.argv) > 1 else None
     for name, text in variants(s):
         if only and name not in only:
             continue
         assert text != s, name
-        tmp = os.path.join(ROOT, "csrc/kernels", "_abl_%s.hip" % name)
-        try:
-            open(tmp, "w").write(text)
-            obj = "/tmp/_abl_%s.o" % name
-            subprocess.run([HIPCC, "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-I",
-                            os.path.join(ROOT, "csrc"), "-c", "-o", obj, tmp], check=True)
-        finally:
-            os.remove(tmp)
-        lib = os.path.join(out, "libtcamd_hip_k11w_%s.so" % name)
-        subprocess.run([HIPCC, "-shared", "-fPIC", "--offload-arch=gfx950", "-o", lib, obj, *objs,
-                        "-L/opt/rocm/lib", "-lamdhip64"], check=True)
-        print(lib, flush=True)
+        print(build_variant.build("k11w_%s" % name, SRC, text, "densenet_x3"), flush=True)
 
 
 if __name__ == "__main__":

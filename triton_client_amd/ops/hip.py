@@ -318,14 +318,6 @@ _SIGS = {
     "tcamd_x3_dense_small_pair_supported": ([ctypes.c_int, ctypes.c_int], ctypes.c_int),
     "tcamd_x3_small_tiles": ([ctypes.c_int, ctypes.c_int], ctypes.c_int),
     "tcamd_x3_small_tiles_shared": ([ctypes.c_int, ctypes.c_int, ctypes.c_int], ctypes.c_int),
-    "tcamd_x3_dense_fused_ws": (
-        [
-            ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
-            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-            ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
-        ],
-        ctypes.c_int,
-    ),
     "tcamd_x3_dense_fused3": (
         [
             ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
@@ -1173,13 +1165,18 @@ def x3_w3f_fragments(w):
     return w.reshape(2, 16, 9, 4, 4, 8).permute(2, 3, 0, 4, 1, 5).contiguous().reshape(32, 9 * 128)
 
 
+def _x3_dense_fused(name, x, ldx, imgs, H, W, K, s1, t1, w1_hi, w1_lo, b1, w2_hi, w2_lo, y, ldy, stream):
+    """The K11x entry point ``tcamd_<name>``: every version takes the same arguments."""
+    _check(getattr(_load(), "tcamd_" + name)(x, int(ldx), int(imgs), int(H), int(W), int(K), s1, t1, w1_hi, w1_lo, b1,
+                                             w2_hi, w2_lo, y, int(ldy), _vp(stream)), name)
+
+
 def x3_dense_fused(x, ldx, imgs, H, W, K, s1, t1, w1_hi, w1_lo, b1, w2_hi, w2_lo, y, ldy, stream=None):
     """K11x: one fp32-parity dense layer in ONE kernel, the 128-channel
     bottleneck kept in LDS (never written to HBM).  ``w1_*`` in the
     x3_w1_fragments layout, ``w2_*`` in x3_w3f_fragments; 16 <= W <= 56, K a multiple
     of 32 in 64..224."""
-    _check(_load().tcamd_x3_dense_fused(x, int(ldx), int(imgs), int(H), int(W), int(K), s1, t1, w1_hi, w1_lo, b1,
-                                        w2_hi, w2_lo, y, int(ldy), _vp(stream)), "x3_dense_fused")
+    _x3_dense_fused("x3_dense_fused", x, ldx, imgs, H, W, K, s1, t1, w1_hi, w1_lo, b1, w2_hi, w2_lo, y, ldy, stream)
 
 
 def x3_dense_small(x, ldx, imgs, H, W, K, s1, t1, w1f_hi, w1f_lo, b1, w2_hi, w2_lo, y, ldy, stream=None, tiles=0):
@@ -1224,16 +1221,7 @@ def x3_small_tiles_shared(imgs, W, streams):
 def x3_dense_fused3(x, ldx, imgs, H, W, K, s1, t1, w1_hi, w1_lo, b1, w2_hi, w2_lo, y, ldy, stream=None):
     """K11x v3: v1's roles and fragment layouts (``w2_*`` in x3_w3f_fragments),
     with the next chunk's 1x1 K steps interleaved into each tile's 3x3."""
-    _check(_load().tcamd_x3_dense_fused3(x, int(ldx), int(imgs), int(H), int(W), int(K), s1, t1, w1_hi, w1_lo, b1,
-                                         w2_hi, w2_lo, y, int(ldy), _vp(stream)), "x3_dense_fused3")
-
-
-def x3_dense_fused_ws(x, ldx, imgs, H, W, K, s1, t1, w1_hi, w1_lo, b1, w2_hi, w2_lo, y, ldy, stream=None):
-    """K11w: v1's layer (same fragments, same products in the same order) on
-    768 threads: producer waves convert X into LDS stages, consumer waves run
-    the MFMAs (csrc/kernels/densenet_x3.hip)."""
-    _check(_load().tcamd_x3_dense_fused_ws(x, int(ldx), int(imgs), int(H), int(W), int(K), s1, t1, w1_hi, w1_lo,
-                                           b1, w2_hi, w2_lo, y, int(ldy), _vp(stream)), "x3_dense_fused_ws")
+    _x3_dense_fused("x3_dense_fused3", x, ldx, imgs, H, W, K, s1, t1, w1_hi, w1_lo, b1, w2_hi, w2_lo, y, ldy, stream)
 
 
 def x3_cat(x, out, rows, K, stream=None):

@@ -18,6 +18,22 @@ latency percentiles, the latency including the client's span computation.
 ``--kernel``: K27 alone on random logits, timed with HIP events around each
 launch after a warm-up, at (rows, n_best, max_answer_length) = (128, 20, 30),
 (128, 64, 384) and (1, 20, 30); next to it the host twin on the same rows.
+
+``--text``: the same two for the text route.  Served: one server with
+``bert_tokenizer``, ``bert_large``, ``qa_spans`` and both ensembles, in two modes:
+
+  text      ``bert_qa_text_ensemble`` on a question of 40 bytes and a context of
+            1.5 KB per row, asking for ``spans``, ``scores``, ``null_score``,
+            ``offsets`` and ``overflow``: ids and logits never leave the device
+  client    the Python twin of the tokenizer (tests/wordpiece_cases.py) on the
+            client, inside the loop, then ``bert_qa_ensemble`` on its ids: what a
+            user had to do before there was a text route
+
+``--device-tokenizer 0|1`` starts that server with ``TCAMD_DEVICE_TOKENIZER`` set,
+to hold K28 against the host twin behind the same ensemble.  ``--text --kernel``:
+K28 ``wordpiece_tokenize`` alone (its ten launches between two events) at 1, 8
+and 128 rows of such texts and at 128 rows of 64 KB contexts, next to the host
+twin on one core and, where it is installed, ``tokenizers``' ``encode_batch``.
 """
 
 import argparse
@@ -105,8 +121,164 @@ def kernel_time(iters):
               flush=True)
 
 
+_WORDS = ("the kernel folds every code point through one table and matches pieces greedily from the left while "
+          "the host twin walks each text front to back and both agree on every id and every byte offset of a "
+          "context piece so a span of tokens becomes an answer again").split()
+TEXT_POINTS = ((1, 1500), (8, 1500), (128, 1500), (128, 65536))
+
+
+def make_texts(rows, context_bytes, seed=0):
+    """``rows`` questions of 40 bytes and contexts of ``context_bytes`` bytes: English words and punctuation."""
+    import random
+
+    rng = random.Random(seed)
+
+    def text(n, end):
+        out = []
+        while sum(len(w) + 1 for w in out) < n:
+            out.append(rng.choice(_WORDS) + (rng.choice([",", ".", ""]) if rng.random() < 0.15 else ""))
+        return (" ".join(out)[:n - 1] + end).encode()
+
+    return [text(40, "?") for _ in range(rows)], [text(context_bytes, ".") for _ in range(rows)]
+
+
+def text_kernel_time(iters):
+    import numpy as np
+    import torch
+
+    from triton_client_amd.ops import hip, host_codec
+    from triton_client_amd.utils import wordpiece
+
+    torch.cuda.set_device(0)
+    hc = host_codec.load()
+    vocab = wordpiece.Vocab.load(wordpiece.default_vocab_path())
+    vocab_dev = torch.from_numpy(vocab.image.view(np.int32).copy()).cuda()
+    s = torch.cuda.current_stream().cuda_stream
+    try:
+        from tests import wordpiece_cases as wc
+
+        lib = wc.library_tokenizer(wordpiece.default_vocab_path())
+    except ImportError:
+        lib = None
+    for rows, ctx_bytes in TEXT_POINTS:
+        qs, cs = make_texts(rows, ctx_bytes, rows)
+        buf, table = wordpiece.pack_texts(qs, cs)
+        text = torch.from_numpy(np.array(buf)).cuda()
+        tab = torch.from_numpy(table.view(np.int32).copy()).cuda()
+        mq = torch.full((rows,), 64, dtype=torch.int32, device="cuda")
+        ws_bytes = hip.wordpiece_workspace(rows, buf.size)
+        ws = torch.zeros(ws_bytes, dtype=torch.uint8, device="cuda")
+        ids, mask, tt = (torch.zeros(rows, SEQ, dtype=torch.int32, device="cuda") for _ in range(3))
+        offsets = torch.zeros(rows, SEQ, 2, dtype=torch.int32, device="cuda")
+        overflow, status = (torch.zeros(rows, dtype=torch.int32, device="cuda") for _ in range(2))
+
+        def launch():
+            hip.wordpiece_tokenize(text.data_ptr(), buf.size, tab.data_ptr(), mq.data_ptr(), rows, SEQ,
+                                   vocab_dev.data_ptr(), vocab.image.size, ws.data_ptr(), ws_bytes, ids.data_ptr(),
+                                   mask.data_ptr(), tt.data_ptr(), offsets.data_ptr(), overflow.data_ptr(),
+                                   status.data_ptr(), stream=s)
+
+        n_iter = iters if ctx_bytes < 65536 else max(10, iters // 10)
+        for _ in range(5):
+            launch()
+        torch.cuda.synchronize()
+        times = []
+        for _ in range(n_iter):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            launch()
+            b.record()
+            b.synchronize()
+            times.append(a.elapsed_time(b) * 1e3)
+        host = []
+        for _ in range(3):
+            t0 = time.perf_counter()
+            want = hc.wordpiece_tokenize(qs, cs, vocab, 64)
+            host.append((time.perf_counter() - t0) * 1e3)
+        got = (ids, mask, tt, offsets, overflow, status)
+        same = all(np.array_equal(g.cpu().numpy().view(np.uint32), np.asarray(w).view(np.uint32))
+                   for g, w in zip(got, want))
+        res = {"kernel": "K28 wordpiece_tokenize", "rows": rows, "question_bytes": 40, "context_bytes": ctx_bytes,
+               "text_bytes": int(buf.size), "launches": n_iter, "mean_us": round(float(np.mean(times)), 2),
+               "min_us": round(float(np.min(times)), 2), "max_us": round(float(np.max(times)), 2),
+               "host_twin_ms_min": round(float(np.min(host)), 3), "equals_host_twin": bool(same),
+               "overflow_rows": int((want[4] > 0).sum())}
+        if lib is not None:
+            pairs = [(q.decode(), c.decode()) for q, c in zip(qs, cs)]
+            enc = []
+            for _ in range(3):
+                t0 = time.perf_counter()
+                lib.encode_batch(pairs, add_special_tokens=False)
+                enc.append((time.perf_counter() - t0) * 1e3)
+            res["tokenizers_encode_batch_ms_min"] = round(float(np.min(enc)), 3)
+        print(json.dumps(res), flush=True)
+
+
+def text_served(args):
+    import numpy as np
+
+    import tritonclient.grpc as grpcclient
+    from tests import wordpiece_cases as wc
+    from triton_client_amd.perf.harness import ServerProcess
+    from triton_client_amd.utils import wordpiece
+
+    log = os.path.abspath(args.server_log) if args.server_log else None
+    if log:
+        os.makedirs(os.path.dirname(log), exist_ok=True)
+    env = {"TCAMD_DEVICE_TOKENIZER": str(args.device_tokenizer)} if args.device_tokenizer is not None else {}
+    srv = ServerProcess(device=0, models="bert_tokenizer,bert_large,qa_spans,bert_qa_ensemble,bert_qa_text_ensemble",
+                        log_path=log, extra_args=["--native-grpc", args.native_grpc], env=env)
+    try:
+        srv.wait_ready(timeout=900, model="bert_qa_text_ensemble")
+        qs, cs = make_texts(args.rows, 1500, 0)
+        twin_vocab = wc.TwinVocab(wordpiece.default_vocab_path())
+        c = grpcclient.InferenceServerClient(srv.grpc_url)
+        text_ins = []
+        for name, col in (("question", qs), ("context", cs)):
+            x = grpcclient.InferInput(name, [args.rows, 1], "BYTES")
+            x.set_data_from_numpy(np.array(col, dtype=object).reshape(-1, 1))
+            text_ins.append(x)
+
+        def id_inputs():
+            ids, mask, tt, _, _, _ = wc.tokenize_rows(qs, cs, twin_vocab, 64)
+            ins = []
+            for name, a in (("input_ids", ids), ("attention_mask", mask), ("token_type_ids", tt)):
+                x = grpcclient.InferInput(name, list(a.shape), "INT32")
+                x.set_data_from_numpy(a)
+                ins.append(x)
+            return ins
+
+        r = c.infer("bert_qa_text_ensemble", text_ins)
+        ref = c.infer("bert_qa_ensemble", id_inputs())
+        agree = all(np.array_equal(r.as_numpy(n).view(np.uint32), ref.as_numpy(n).view(np.uint32))
+                    for n in ("spans", "scores", "null_score"))
+        t0 = time.perf_counter()
+        for _ in range(3):
+            id_inputs()
+        twin_ms = (time.perf_counter() - t0) / 3 * 1e3
+        text_out = ["spans", "scores", "null_score", "offsets", "overflow"]
+        for rep in range(args.reps):
+            for conc in args.concurrency:
+                res = closed_loop(c, grpcclient, "bert_qa_text_ensemble", text_ins, text_out, conc, args.warmup,
+                                  args.seconds, lambda result: None)
+                res.update(mode="text")
+                # the client tokenizes every request anew, before it is sent: inside the measured latency
+                res2 = closed_loop(c, grpcclient, "bert_qa_ensemble", id_inputs, ["spans", "scores", "null_score"],
+                                   conc, args.warmup, args.seconds, lambda result: None)
+                res2.update(mode="client", python_twin_ms_per_request=round(twin_ms, 3))
+                for x in (res, res2):
+                    x.update(rep=rep, rows_per_request=args.rows, context_bytes=1500,
+                             text_equals_id_ensemble=bool(agree), native_grpc=args.native_grpc,
+                             device_tokenizer=args.device_tokenizer)
+                    print(json.dumps(x), flush=True)
+        c.close()
+    finally:
+        srv.stop()
+
+
 def closed_loop(c, mod, model, ins, outputs, conc, warmup, seconds, post):
-    """``conc`` requests in flight; ``post(result)`` runs in the callback, inside the measured latency."""
+    """``conc`` requests in flight; ``post(result)`` runs in the callback, inside the measured latency;
+    ``ins`` may be a function that makes a request's inputs, called inside it too."""
     lock = threading.Lock()
     done = threading.Event()
     state = {"lat": [], "errors": 0, "stop": False, "inflight": conc, "measure": False}
@@ -132,7 +304,7 @@ def closed_loop(c, mod, model, ins, outputs, conc, warmup, seconds, post):
             if again:
                 send()
 
-        c.async_infer(model, ins, callback=cb, outputs=outs)
+        c.async_infer(model, ins() if callable(ins) else ins, callback=cb, outputs=outs)
 
     for _ in range(conc):
         send()
@@ -205,6 +377,9 @@ def served(args):
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--kernel", action="store_true", help="time K27 alone instead of the served loops")
+    ap.add_argument("--text", action="store_true", help="the text route: K28 / bert_qa_text_ensemble (see above)")
+    ap.add_argument("--device-tokenizer", type=int, default=None, choices=[0, 1],
+                    help="--text: TCAMD_DEVICE_TOKENIZER of the server (default: the knob's default)")
     ap.add_argument("--iters", type=int, default=200, help="--kernel: timed launches per point (after 10 warm-up)")
     ap.add_argument("--concurrency", type=int, nargs="+", default=[1, 8])
     ap.add_argument("--rows", type=int, default=1, help="rows per request")
@@ -216,7 +391,9 @@ def main():
                          "ensemble to the Python one; off = the Python front end answers both modes")
     ap.add_argument("--server-log", default="", metavar="PATH", help="keep the server's log in this file")
     args = ap.parse_args()
-    if args.kernel:
+    if args.text:
+        text_kernel_time(args.iters) if args.kernel else text_served(args)
+    elif args.kernel:
         kernel_time(args.iters)
     else:
         served(args)

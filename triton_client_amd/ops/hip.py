@@ -17,6 +17,7 @@ events, peer access.  Kernels (csrc/kernels/*.hip, gfx950):
 * :func:`index_bytes`     K3 BYTES index walk through an LDS window
 * :func:`topk_rows`       K19 per-row top-K {score, index} pairs (classification)
 * :func:`qa_spans`        K27 per-row n best answer spans of question-answering logits
+* :func:`wordpiece_tokenize`  K28 UTF-8 text to BERT question-answering rows (WordPiece)
 
 Pointers are plain ints (device addresses).  ``stream`` is a hipStream_t as an
 int (``torch.cuda.current_stream().cuda_stream`` works) or None for the
@@ -200,6 +201,16 @@ _SIGS = {
         ],
         ctypes.c_int,
     ),
+    "tcamd_wordpiece_tokenize": (
+        [
+            ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32,
+            ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p,
+            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+        ],
+        ctypes.c_int,
+    ),
+    "tcamd_wordpiece_workspace": ([ctypes.c_int32, ctypes.c_uint64], ctypes.c_uint64),
+    "tcamd_wordpiece_geometry": ([ctypes.POINTER(ctypes.c_int32)], None),
     # fused DenseNet kernels (csrc/kernels/densenet.hip)
     "tcamd_dn_conv1x1": (
         [
@@ -984,6 +995,51 @@ def qa_spans(start_ptr, end_ptr, logit_stride_bytes, mask_ptr, token_type_ptr, i
                                   _vp(token_type_ptr), int(ids_stride_bytes), int(rows), int(S), _vp(k_row_ptr),
                                   _vp(len_row_ptr), int(kmax), _vp(spans_ptr), _vp(scores_ptr), _vp(null_score_ptr),
                                   _vp(stream)), "qa_spans")
+
+
+WORDPIECE_GEOMETRY = ("chunk", "block", "max_text_bytes", "max_word_chars", "max_rows", "max_chunks")
+
+
+def wordpiece_geometry():
+    """The decomposition of K28 ``wordpiece_tokenize``, from the library, as a
+    dict: ``chunk`` (the bytes, and then the folded positions, of a text one
+    workgroup owns), ``block`` (threads of a workgroup; a thread takes ``chunk
+    / block`` consecutive bytes), ``max_text_bytes``, ``max_word_chars``,
+    ``max_rows`` per call and ``max_chunks`` per text."""
+    g = (ctypes.c_int32 * 6)()
+    _load().tcamd_wordpiece_geometry(g)
+    return dict(zip(WORDPIECE_GEOMETRY, (int(x) for x in g)))
+
+
+def wordpiece_workspace(rows, text_bytes):
+    """Bytes of device workspace :func:`wordpiece_tokenize` needs for ``rows``
+    rows whose texts have ``text_bytes`` bytes in all."""
+    return int(_load().tcamd_wordpiece_workspace(int(rows), int(text_bytes)))
+
+
+def wordpiece_tokenize(text_ptr, text_bytes, row_table_ptr, maxq_row_ptr, rows, S, vocab_ptr, vocab_words,
+                       workspace_ptr, workspace_bytes, ids_ptr, mask_ptr, type_ids_ptr, offsets_ptr, overflow_ptr,
+                       status_ptr, stream=None):
+    """K28: UTF-8 questions and contexts to BERT question-answering rows, by the
+    rule of csrc/kernels/wordpiece_core.h.  ``text`` is a device buffer of
+    ``text_bytes`` bytes holding every text, ``row_table`` device uint32
+    ``[rows, 4]`` = ``{question_off, question_len, context_off, context_len}``
+    into it (``utils.wordpiece.pack_texts``), ``maxq_row`` device int32
+    ``[rows]``, ``vocab`` the device copy of ``utils.wordpiece.Vocab.image``
+    (``vocab_words`` 32-bit words), ``workspace`` at least
+    :func:`wordpiece_workspace` bytes.  Row ``r`` gets int32 ``ids`` / ``mask``
+    / ``type_ids`` ``[S]``, ``offsets`` ``[S, 2]`` (byte offsets into its
+    context, on the context pieces), ``overflow`` and a uint32 ``status`` (0, or
+    why the row is all zeros: ``utils.wordpiece.status_error``).  At most
+    ``wordpiece_geometry()["max_rows"]`` rows, ``S`` in 4..1024; those, a null
+    or misaligned pointer or a workspace below its fixed part raise
+    (hipErrorInvalidValue) without a launch.  Ten launches on ``stream``,
+    nothing on the host."""
+    _check(_load().tcamd_wordpiece_tokenize(_vp(text_ptr), int(text_bytes), _vp(row_table_ptr), _vp(maxq_row_ptr),
+                                            int(rows), int(S), _vp(vocab_ptr), int(vocab_words), _vp(workspace_ptr),
+                                            int(workspace_bytes), _vp(ids_ptr), _vp(mask_ptr), _vp(type_ids_ptr),
+                                            _vp(offsets_ptr), _vp(overflow_ptr), _vp(status_ptr), _vp(stream)),
+           "wordpiece_tokenize")
 
 
 def dn_conv1x1(x, ldx, M, K, in_scale, in_bias, w, N, out_bias, relu_out, y, ldy, pool=0, H=0, W=0, stream=None,

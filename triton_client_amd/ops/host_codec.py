@@ -1,5 +1,5 @@
 """ctypes binding of libtcamd_host.so (BYTES pack / scan, baseline JPEG and PNG on the host, the compare rule,
-the answer-span rule)."""
+the answer-span rule, the BERT tokenizer)."""
 import ctypes
 import os
 
@@ -129,6 +129,21 @@ class HostCodec:
                                             ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p,
                                             ctypes.c_void_p, ctypes.c_void_p]
         lib.tcamd_host_qa_spans.restype = ctypes.c_int
+        wp = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32,
+              ctypes.c_void_p, ctypes.c_uint64]
+        outs = [ctypes.c_void_p] * 6
+        lib.tcamd_host_wordpiece_tokenize.argtypes = wp + outs
+        lib.tcamd_host_wordpiece_tokenize.restype = ctypes.c_int
+        lib.tcamd_host_wordpiece_emulate.argtypes = wp + [ctypes.c_void_p, ctypes.c_uint64] + outs
+        lib.tcamd_host_wordpiece_emulate.restype = ctypes.c_int
+        lib.tcamd_host_wordpiece_workspace.argtypes = [ctypes.c_int32, ctypes.c_uint64]
+        lib.tcamd_host_wordpiece_workspace.restype = ctypes.c_uint64
+        lib.tcamd_host_wordpiece_geometry.argtypes = [ctypes.POINTER(ctypes.c_int32)]
+        lib.tcamd_host_wordpiece_geometry.restype = None
+        lib.tcamd_host_wordpiece_fold.argtypes = [ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32)]
+        lib.tcamd_host_wordpiece_fold.restype = ctypes.c_int
+        lib.tcamd_host_wordpiece_vocab_check.argtypes = [ctypes.c_void_p, ctypes.c_uint64]
+        lib.tcamd_host_wordpiece_vocab_check.restype = ctypes.c_int
         lib.tcamd_host_pack_bytes.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]
         lib.tcamd_host_pack_bytes.restype = ctypes.c_int
         lib.tcamd_host_count_bytes.argtypes = [ctypes.c_void_p, ctypes.c_uint64]
@@ -233,6 +248,66 @@ class HostCodec:
         self.qa_spans_raw(ptr(st), ptr(en), S * 4, ptr(mk), ptr(tt), S * 4, rows, S, ptr(k), ptr(ln), kmax,
                           ptr(spans), ptr(scores), null.ctypes.data)
         return spans, scores, null[:rows]
+
+    # -- the BERT tokenizer (csrc/kernels/wordpiece_core.h) -------------------------------
+    WORDPIECE_GEOMETRY = ("chunk", "block", "max_text_bytes", "max_word_chars", "max_rows", "max_chunks")
+
+    def wordpiece_geometry(self):
+        """``ops.hip.wordpiece_geometry`` without the device library."""
+        g = (ctypes.c_int32 * 6)()
+        self._lib.tcamd_host_wordpiece_geometry(g)
+        return dict(zip(self.WORDPIECE_GEOMETRY, (int(x) for x in g)))
+
+    def wordpiece_workspace(self, rows, text_bytes):
+        """``ops.hip.wordpiece_workspace`` without the device library."""
+        return int(self._lib.tcamd_host_wordpiece_workspace(int(rows), int(text_bytes)))
+
+    def wordpiece_fold(self, cp):
+        """What code point ``cp`` folds to: 0 to 3 words, each a code point with
+        bit 30 set when it is a word of its own (punctuation, CJK), or one word
+        with bit 31 for a space; ``[]`` for a dropped code point."""
+        out = (ctypes.c_uint32 * 3)()
+        n = self._lib.tcamd_host_wordpiece_fold(int(cp), out)
+        if n < 0:
+            raise ValueError("no code point %#x" % cp)
+        return [int(out[i]) for i in range(n)]
+
+    def wordpiece_tokenize(self, questions, contexts, vocab, max_query_length=64, S=384, emulate=False,
+                           workspace_bytes=None):
+        """K28 ``wordpiece_tokenize`` on the host, bit for bit: ``questions`` and
+        ``contexts`` are bytes objects (UTF-8, unchecked), ``vocab`` a
+        ``utils.wordpiece.Vocab``, ``max_query_length`` one int or one per row.
+        Returns ``(ids, mask, type_ids, offsets, overflow, status)``: int32
+        ``[rows, S]`` three times, int32 ``[rows, S, 2]`` (byte offsets into the
+        context, context pieces only), int32 ``[rows]`` (context pieces that did
+        not fit) and uint32 ``[rows]`` (0, or why the row is all zeros:
+        ``utils.wordpiece.status_error``).  ``emulate`` runs the kernel's phases
+        in the kernel's workspace layout instead of the front-to-back walk."""
+        from triton_client_amd.utils import wordpiece as wp
+
+        buf, table = wp.pack_texts(questions, contexts)
+        rows = table.shape[0]
+        mq = np.ascontiguousarray(np.broadcast_to(np.asarray(max_query_length, dtype=np.int32), (rows,)))
+        image = np.ascontiguousarray(vocab.image, dtype=np.uint32)
+        pad = max(rows, 1)
+        ids, mask, tt = (np.zeros((pad, S), dtype=np.int32) for _ in range(3))
+        offsets = np.zeros((pad, S, 2), dtype=np.int32)
+        overflow, status = np.zeros(pad, dtype=np.int32), np.zeros(pad, dtype=np.uint32)
+        text = buf if buf.size else np.zeros(4, dtype=np.uint8)
+        tab = table if rows else np.zeros((1, 4), dtype=np.uint32)
+        mqa = mq if rows else np.zeros(1, dtype=np.int32)
+        head = (text.ctypes.data, int(buf.size), tab.ctypes.data, mqa.ctypes.data, rows, int(S), image.ctypes.data,
+                int(image.size))
+        outs = tuple(a.ctypes.data for a in (ids, mask, tt, offsets, overflow, status))
+        if emulate:
+            nbytes = self.wordpiece_workspace(rows, buf.size) if workspace_bytes is None else int(workspace_bytes)
+            ws = np.zeros(max(nbytes // 4, 1), dtype=np.uint32)
+            rc = self._lib.tcamd_host_wordpiece_emulate(*head, ws.ctypes.data, nbytes, *outs)
+        else:
+            rc = self._lib.tcamd_host_wordpiece_tokenize(*head, *outs)
+        if rc:
+            raise ValueError("wordpiece_tokenize: a size or pointer the rule refuses")
+        return ids[:rows], mask[:rows], tt[:rows], offsets[:rows], overflow[:rows], status[:rows]
 
     # -- baseline JPEG (csrc/host/jpeg.cc) ---------------------------------------------
     @staticmethod

@@ -40,7 +40,12 @@ def main(argv=None):
                          "value such as the pool's 4; 0 = leave the environment alone).  Each model instance replays its graphs on its own stream; with 4 "
                          "instances plus copy streams on 4 queues, ready batches waited for a queue: 1.6 ms of "
                          "every request's server time was outside queue and compute (profiles/r3_hw_queues.md)")
+    ap.add_argument("--bert-vocab", default="",
+                    help="vocab.txt of the bert_tokenizer model (one piece per line; handed down as "
+                         "TCAMD_BERT_VOCAB); default: the demonstration vocabulary that ships with the package")
     args = ap.parse_args(argv)
+    if args.bert_vocab:
+        os.environ["TCAMD_BERT_VOCAB"] = os.path.abspath(args.bert_vocab)
     if args.hw_queues > 0:
         # before anything initialises HIP in this process.  The GPU boxes
         # export GPU_MAX_HW_QUEUES=4 (HIP's own default) into every job, so a

@@ -18,7 +18,9 @@ Behaviour is pinned by the reference's example/test expectations:
   tensor -> classifier ensemble (ensemble_image_client.py).
 
 Not from the reference: ``qa_spans``, the answer-span step behind ``bert_large``
-(examples/python/bert_qa_client.py), here on the host twin of K27.
+(examples/python/bert_qa_client.py), here on the host twin of K27, and
+``bert_tokenizer``, the step in front of it (examples/python/bert_qa_text_client.py),
+here on the host twin of K28.
 """
 
 import threading
@@ -27,7 +29,7 @@ import time
 import numpy as np
 
 from .model_base import Model, TensorSpec
-from .types import ServerError
+from .types import OutputTensor, ServerError
 
 
 class SimpleAddSub(Model):
@@ -537,7 +539,135 @@ class QaSpans(Model):
         return self.results(plan, *self.run_host(requests, plan, total))
 
 
+class BertTokenizer(Model):
+    """``bert_tokenizer`` — UTF-8 text to the three inputs of ``bert_large``, the
+    step in front of it: BYTES [1] ``question`` and ``context`` in; per row INT32
+    [384] ``input_ids`` / ``attention_mask`` / ``token_type_ids``, INT32 [384, 2]
+    ``offsets`` (the bytes of the context each context piece covers, (0, 0)
+    elsewhere; ``utils.qa.answer_text`` turns a span back into text) and INT32 [1]
+    ``overflow`` (context pieces that did not fit; there is no doc stride) out.
+    The rule is csrc/kernels/wordpiece_core.h: BERT's uncased WordPiece, a row
+    ``[CLS] question[:max_query_length] [SEP] context [SEP]``, ``token_type_ids``
+    1 on the context pieces only, so that ``qa_spans`` never answers with the
+    last ``[SEP]``.  This class runs the host twin of K28
+    (``HostCodec.wordpiece_tokenize``), one call per batch;
+    server/gpu_models.py BertTokenizer runs the kernel.
+
+    The vocabulary is ``TCAMD_BERT_VOCAB`` (the server's ``--bert-vocab``), else
+    the demonstration vocabulary that ships with the package; it is read at
+    load.  Custom request parameter: ``max_query_length`` (int64, 1..381,
+    default 64); requests of different values share a batch.  A text that is
+    not valid UTF-8 or longer than 65,536 bytes fails its own request."""
+
+    name = "bert_tokenizer"
+    max_batch_size = 128
+    SEQ = 384
+    MAX_QUERY = 64
+    inputs = (TensorSpec("question", "BYTES", [1]), TensorSpec("context", "BYTES", [1]))
+    outputs = (TensorSpec("input_ids", "INT32", [384]), TensorSpec("attention_mask", "INT32", [384]),
+               TensorSpec("token_type_ids", "INT32", [384]), TensorSpec("offsets", "INT32", [384, 2]),
+               TensorSpec("overflow", "INT32", [1]))
+    dynamic_batching = {"preferred": [], "max_queue_delay_us": 100}
+
+    @classmethod
+    def plan(cls, requests):
+        """Per request ``(first_row, questions, contexts, max_query_length)``, or
+        the ServerError of its parameters, shapes or lengths; and the rows of the
+        batch."""
+        from triton_client_amd.utils.wordpiece import MAX_TEXT_BYTES
+
+        out, total = [], 0
+        for r in requests:
+            try:
+                mq = QaSpans._int_param(r, "max_query_length", cls.MAX_QUERY, 1, cls.SEQ - 3)
+                texts = []
+                for nm in ("question", "context"):
+                    col = [bytes(x) if not isinstance(x, str) else x.encode("utf-8")
+                           for x in np.asarray(r.input(nm).numpy(), dtype=object).reshape(-1)]
+                    if any(len(x) > MAX_TEXT_BYTES for x in col):
+                        raise ServerError("bert_tokenizer: %s too long" % nm)
+                    texts.append(col)
+                if len(texts[0]) != len(texts[1]):
+                    raise ServerError("bert_tokenizer: question and context must have one element per row")
+            except ServerError as e:
+                out.append(e)
+                continue
+            out.append((total, texts[0], texts[1], mq))
+            total += len(texts[0])
+        return out, total
+
+    @staticmethod
+    def batch_texts(plan):
+        """(questions, contexts, max_query_length per row) of the plan's good requests."""
+        qs, cs, mq = [], [], []
+        for p in plan:
+            if not isinstance(p, Exception):
+                qs += p[1]
+                cs += p[2]
+                mq += [p[3]] * len(p[1])
+        return qs, cs, np.asarray(mq, dtype=np.int32)
+
+    def results(self, plan, ids, mask, tt, offsets, overflow, status, device=None):
+        """The per-request outputs from the batch's arrays; a request with a row
+        whose status is not 0 gets that row's error.  ``device`` = (tensor, device
+        id): ids / mask / type ids ``[3, rows, S]`` left on the device, handed out
+        as ``DeviceView`` with the tensor as ``owner``."""
+        from triton_client_amd.utils.wordpiece import status_error
+
+        from .types import DeviceView
+
+        res = []
+        for p in plan:
+            if isinstance(p, Exception):
+                res.append(p)
+                continue
+            first, n = p[0], len(p[1])
+            bad = [status_error(s) for s in status[first:first + n] if s]
+            if bad:
+                res.append(ServerError(bad[0]))
+                continue
+            outs = []
+            for k, (nm, a) in enumerate((("input_ids", ids), ("attention_mask", mask), ("token_type_ids", tt))):
+                if device is None:
+                    outs.append(self.out(nm, np.ascontiguousarray(a[first:first + n])))
+                else:
+                    t, dev_id = device
+                    row = self.SEQ * 4
+                    o = OutputTensor(nm, "INT32", [n, self.SEQ],
+                                     DeviceView(t[k].data_ptr() + first * row, n * row, dev_id))
+                    o.owner = t  # keeps the device memory alive while the ensemble holds the tensor
+                    outs.append(o)
+            outs.append(self.out("offsets", np.ascontiguousarray(offsets[first:first + n])))
+            outs.append(self.out("overflow", np.ascontiguousarray(overflow[first:first + n]).reshape(n, 1)))
+            res.append(outs)
+        return res
+
+    def load(self):
+        from triton_client_amd.ops import host_codec
+        from triton_client_amd.utils import wordpiece
+
+        self._codec = host_codec.load()
+        self.vocab_path = wordpiece.default_vocab_path()
+        try:
+            self.vocab = wordpiece.Vocab.load(self.vocab_path)
+        except (OSError, ValueError) as e:
+            raise ServerError("bert_tokenizer: cannot load the vocabulary %s: %s" % (self.vocab_path, e))
+
+    def run_host(self, plan):
+        qs, cs, mq = self.batch_texts(plan)
+        return self._codec.wordpiece_tokenize(qs, cs, self.vocab, mq, self.SEQ)
+
+    def execute(self, requests):
+        plan, total = self.plan(requests)
+        if total == 0:
+            return plan
+        if total > self.max_batch_size:
+            return [ServerError("batch of %d rows exceeds max_batch_size" % total)] * len(requests)
+        return self.results(plan, *self.run_host(plan))
+
+
 CPU_MODELS = [
+    BertTokenizer,
     QaSpans,
     FrontendSink,
     BertSink,

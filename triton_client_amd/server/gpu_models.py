@@ -1303,7 +1303,210 @@ class BertQaEnsemble(Model):
         raise ServerError("ensemble models are scheduled by the server")
 
 
-GPU_MODELS = [DensenetOnnx, PreprocessInception, PreprocessInceptionEnsemble, BertLarge, QaSpans, BertQaEnsemble]
+class BertTokenizer(Model):
+    """``bert_tokenizer`` on the GPU: the same I/O contract, request parameter,
+    vocabulary and rule as the CPU model of that name (server/cpu_models.py
+    BertTokenizer), which it replaces on a ``--gpu`` server and whose checks it
+    uses.
+
+    Per batch, the host copies each request's strings end to end into the
+    slot's pinned staging area behind the per-row table (``{question_off,
+    question_len, context_off, context_len}`` and ``max_query_length``), one
+    upload takes table and texts to the device, K28 ``wordpiece_tokenize``
+    (csrc/kernels/wordpiece.hip) decodes, folds, matches and assembles the rows
+    on the slot's stream against the vocabulary image uploaded at load, and one
+    download brings the outputs back.  A batch whose texts exceed the staging
+    budget (``TEXT_BUDGET``) runs in several launches, each over as many rows as
+    fit.  For a batch of ensemble steps (``accepts_device_outputs``) the three
+    id tensors are written into a tensor of the batch's own and handed on as
+    ``DeviceView`` with ``owner`` set, as ``BertLarge._execute_device_outputs``
+    does with its logits; ``offsets`` and ``overflow`` always go to the host.
+    ``TCAMD_DEVICE_TOKENIZER=0`` (read at load) runs the host twin instead."""
+
+    name = "bert_tokenizer"
+    max_batch_size = 128
+    SEQ = 384
+    TEXT_BUDGET = 1 << 20  # bytes of text per launch; one row needs at most 2 * 65,536
+    inputs = (TensorSpec("question", "BYTES", [1]), TensorSpec("context", "BYTES", [1]))
+    outputs = (TensorSpec("input_ids", "INT32", [384]), TensorSpec("attention_mask", "INT32", [384]),
+               TensorSpec("token_type_ids", "INT32", [384]), TensorSpec("offsets", "INT32", [384, 2]),
+               TensorSpec("overflow", "INT32", [1]))
+    dynamic_batching = {"preferred": [], "max_queue_delay_us": 100}
+    instance_kind = "KIND_GPU"
+    instance_count = 2
+    gpus = (0,)
+
+    def __init__(self, version=1, device_id=0, **kw):
+        super().__init__(version, **kw)
+        self.device_id = int(kw.get("device", device_id))
+        self._slots = []
+        self._free = []
+        self._cv = threading.Condition()
+        self._host = None
+
+    def load(self):
+        from .cpu_models import BertTokenizer as HostBertTokenizer
+
+        self._host = HostBertTokenizer(self.version)
+        self._host.load()
+        self.vocab = self._host.vocab
+        self.device_path = os.environ.get("TCAMD_DEVICE_TOKENIZER", "1") != "0"
+        if not self.device_path:
+            return
+        import torch
+
+        from triton_client_amd.ops import hip
+
+        if not torch.cuda.is_available():
+            raise ServerError("bert_tokenizer (GPU) requires a GPU")
+        hip.lib()  # fail loudly if the native kernels are missing
+        self.torch = torch
+        dev = torch.device("cuda", self.device_id)
+        n = self.max_batch_size
+        self.head_bytes = n * 16 + n * 4  # the row table, then max_query_length per row
+        self.in_bytes = self.head_bytes + self.TEXT_BUDGET
+        self.ws_bytes = hip.wordpiece_workspace(n, self.TEXT_BUDGET)
+        self.out_bytes = n * (self.SEQ * 5 + 2) * 4
+        self.vocab_dev = torch.from_numpy(self.vocab.image.view(np.int32).copy()).to(dev)
+        for _ in range(max(1, self.instance_count)):
+            self._slots.append({
+                "stream": torch.cuda.Stream(device=dev),
+                "in_host": hip.host_alloc(self.in_bytes),
+                "out_host": hip.host_alloc(self.out_bytes),
+                "in_dev": torch.zeros(self.in_bytes, device=dev, dtype=torch.uint8),
+                "out_dev": torch.zeros(self.out_bytes, device=dev, dtype=torch.uint8),
+                "ws": torch.zeros(self.ws_bytes, device=dev, dtype=torch.uint8),
+            })
+        self._free = list(range(len(self._slots)))
+
+    unload = QaSpans.unload
+    _acquire = QaSpans._acquire
+    _release = QaSpans._release
+
+    def execute(self, requests):
+        plan, total = self._host.plan(requests)
+        if total == 0:
+            return plan
+        if total > self.max_batch_size:
+            return [ServerError("batch of %d rows exceeds max_batch_size" % total)] * len(requests)
+        if not self.device_path:
+            return self._host.results(plan, *self._host.run_host(plan))
+        from triton_client_amd.ops import hip
+
+        on_device = all(getattr(r, "accepts_device_outputs", False) for r in requests)
+        i = self._acquire()
+        try:
+            return self._execute(self._slots[i], plan, total, on_device)
+        except (ServerError, hip.HipError) as e:
+            err = e if isinstance(e, ServerError) else ServerError("bert_tokenizer: %s" % e)
+            return [p if isinstance(p, Exception) else err for p in plan]
+        finally:
+            self._release(i)
+
+    @classmethod
+    def launches(cls, lens):
+        """The rows of a batch dealt into launches: ``[(first_row, rows)]``, each
+        launch's texts within ``TEXT_BUDGET``; ``lens[r]`` = the bytes of row r."""
+        out, first, used = [], 0, 0
+        for r, n in enumerate(lens):
+            if r > first and used + n > cls.TEXT_BUDGET:
+                out.append((first, r - first))
+                first, used = r, 0
+            used += n
+        out.append((first, len(lens) - first))
+        return out
+
+    def _execute(self, slot, plan, total, on_device):
+        import ctypes
+
+        from triton_client_amd.ops import hip
+
+        torch, S, n_max = self.torch, self.SEQ, self.max_batch_size
+        sh = slot["stream"].cuda_stream
+        qs, cs, mq = self._host.batch_texts(plan)
+        in_host, in_dev = slot["in_host"], slot["in_dev"].data_ptr()
+        out_dev = slot["out_dev"].data_ptr()
+        # the outputs of the batch, compact: offsets, overflow, status; then ids, mask, type ids
+        o_over, o_stat, o_ids = total * S * 8, total * S * 8 + total * 4, total * S * 8 + total * 8
+        res = None
+        if on_device:
+            with torch.cuda.stream(slot["stream"]):
+                res = torch.empty((3, total, S), device=slot["stream"].device, dtype=torch.int32)
+            id_ptrs = [res[k].data_ptr() for k in range(3)]
+        else:
+            id_ptrs = [out_dev + o_ids + k * total * S * 4 for k in range(3)]
+        table = np.ctypeslib.as_array((ctypes.c_uint32 * (n_max * 4)).from_address(in_host)).reshape(n_max, 4)
+        maxq = np.ctypeslib.as_array((ctypes.c_int32 * n_max).from_address(in_host + n_max * 16))
+        lens = [len(q) + len(c) for q, c in zip(qs, cs)]
+        groups = self.launches(lens)
+        for g, (first, rows) in enumerate(groups):
+            if g:
+                hip.stream_synchronize(sh)  # the staging area is about to be rewritten
+            at = 0
+            for r in range(rows):
+                for f, s in enumerate((qs[first + r], cs[first + r])):
+                    table[r, 2 * f], table[r, 2 * f + 1] = at, len(s)
+                    ctypes.memmove(in_host + self.head_bytes + at, s, len(s))
+                    at += len(s)
+            maxq[:rows] = mq[first:first + rows]
+            hip.memcpy_async(in_dev, in_host, self.head_bytes + at, sh)
+            hip.wordpiece_tokenize(in_dev + self.head_bytes, at, in_dev, in_dev + n_max * 16, rows, S,
+                                   self.vocab_dev.data_ptr(), self.vocab.image.size, slot["ws"].data_ptr(),
+                                   self.ws_bytes, id_ptrs[0] + first * S * 4, id_ptrs[1] + first * S * 4,
+                                   id_ptrs[2] + first * S * 4, out_dev + first * S * 8, out_dev + o_over + first * 4,
+                                   out_dev + o_stat + first * 4, stream=sh)
+        nbytes = o_ids if on_device else o_ids + 3 * total * S * 4
+        hip.memcpy_async(slot["out_host"], out_dev, nbytes, sh)
+        hip.stream_synchronize(sh)
+        raw = np.ctypeslib.as_array((ctypes.c_uint8 * nbytes).from_address(slot["out_host"])).copy()
+        offsets = raw[:o_over].view(np.int32).reshape(total, S, 2)
+        overflow, status = raw[o_over:o_stat].view(np.int32), raw[o_stat:o_ids].view(np.uint32)
+        if on_device:
+            return self._host.results(plan, None, None, None, offsets, overflow, status, device=(res, self.device_id))
+        ids, mask, tt = (raw[o_ids + k * total * S * 4:o_ids + (k + 1) * total * S * 4].view(np.int32).reshape(total, S)
+                         for k in range(3))
+        return self._host.results(plan, ids, mask, tt, offsets, overflow, status)
+
+
+class BertQaTextEnsemble(Model):
+    """Ensemble: UTF-8 text -> ``bert_tokenizer`` -> ``bert_large`` ->
+    ``qa_spans``.  The ids stay on the device between the first two steps and
+    the logits between the last two (each step hands its outputs on as
+    ``DeviceView``); ``offsets`` and ``overflow`` come from the first step, so
+    ``utils.qa.answer_text`` can turn a span back into the context's bytes.
+    ``max_query_length``, ``n_best`` and ``max_answer_length`` travel as the
+    ensemble's custom request parameters to the steps that read them.  The ids
+    and the logits are outputs too; a request that does not ask for them does
+    not pay for their copy.  A context longer than the row is cut
+    (``overflow``): there is no doc stride."""
+
+    name = "bert_qa_text_ensemble"
+    platform = "ensemble"
+    backend = ""
+    max_batch_size = 128
+    inputs = BertTokenizer.inputs
+    outputs = QaSpans.outputs + BertTokenizer.outputs[3:] + BertTokenizer.outputs[:3] + BertLarge.outputs
+    ensemble_steps = [
+        ("bert_tokenizer", {"question": "question", "context": "context"},
+         {"input_ids": "input_ids", "attention_mask": "attention_mask", "token_type_ids": "token_type_ids",
+          "offsets": "offsets", "overflow": "overflow"}),
+        ("bert_large", {"input_ids": "input_ids", "attention_mask": "attention_mask",
+                        "token_type_ids": "token_type_ids"},
+         {"start_logits": "start_logits", "end_logits": "end_logits"}),
+        ("qa_spans", {"start_logits": "start_logits", "end_logits": "end_logits", "attention_mask": "attention_mask",
+                      "token_type_ids": "token_type_ids"},
+         {"spans": "spans", "scores": "scores", "null_score": "null_score"}),
+    ]
+
+    def load(self):
+        pass
+
+    def execute(self, requests):  # pragma: no cover - the server runs ensembles step by step
+        raise ServerError("ensemble models are scheduled by the server")
+
+
+GPU_MODELS = [DensenetOnnx, PreprocessInception, PreprocessInceptionEnsemble, BertLarge, QaSpans, BertQaEnsemble,
+              BertTokenizer, BertQaTextEnsemble]
 # loaded only when --models names them: bert_large_fp32 adds ~2 GB of bf16x3
 # weights and 28 captured HIP graphs per instance (round-5 advisor finding)
 OPT_IN_GPU_MODELS = [BertLargeFP32]

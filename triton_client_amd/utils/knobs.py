@@ -104,6 +104,14 @@ KNOBS = [
     Knob("TCAMD_DEVICE_QA_SPANS", "python", 1, "server/gpu_models.py",
          "GPU qa_spans: K27 qa_spans picks the answer spans on the device; 0 = the host twin of the same rule",
          "tests/test_qa_spans_gpu.py::test_the_knob_changes_the_route_and_not_one_bit_of_the_spans"),
+    Knob("TCAMD_DEVICE_TOKENIZER", "python", 1, "server/gpu_models.py",
+         "GPU bert_tokenizer: K28 wordpiece_tokenize turns the texts into rows on the device; 0 = the host twin of "
+         "the same rule",
+         "tests/test_wordpiece_gpu.py::test_the_knob_changes_the_route_and_not_one_bit_of_the_rows"),
+    Knob("TCAMD_BERT_VOCAB", "python", "", "utils/wordpiece.py",
+         "bert_tokenizer: the vocab.txt to load (the server's --bert-vocab sets it); unset = the demonstration "
+         "vocabulary triton_client_amd/data/bert_demo_vocab.txt",
+         "tests/test_wordpiece_served.py::test_the_vocabulary_comes_from_the_environment"),
     Knob("TCAMD_BYTES_HOST_MAX", "python", 8192, "tritonclient/utils/hip_shared_memory",
          "BYTES set with bytes_path=auto: host codec up to this many elements, K2 above",
          "tests/test_knobs.py::test_bytes_auto_path_knobs"),

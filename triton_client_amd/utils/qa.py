@@ -11,6 +11,18 @@ import numpy as np
 FILLER_SCORE = np.float32(-3.4028234663852886e38)  # -FLT_MAX
 
 
+def answer_text(context_bytes, span, offsets):
+    """The bytes of the context a span ``(first token, last token)`` covers, by
+    the ``offsets`` ``[S, 2]`` that ``bert_tokenizer`` returned for the row:
+    ``context[offsets[s, 0]:offsets[e, 1]]``; ``b""`` for the filler span
+    ``(-1, -1)``."""
+    s, e = int(span[0]), int(span[1])
+    if s < 0 or e < 0:
+        return b""
+    offsets = np.asarray(offsets)
+    return bytes(context_bytes)[int(offsets[s, 0]):int(offsets[e, 1])]
+
+
 def n_best_spans(start, end, attention_mask, token_type_ids, n_best=20, max_answer_length=30):
     """One row: ``(spans int32 [n_best, 2], scores fp32 [n_best], null_score)``.
     Ranks past the candidates hold ``(-1, -1)`` and ``-FLT_MAX``."""

@@ -2,7 +2,7 @@
 # in-tree (the .so files travel to the GPU box with the repo snapshot).
 #   libcshm.so        POSIX shm C ABI (tritonclient.utils.shared_memory)
 #   libtcamd_hip.so   HIP runtime glue + CDNA4 kernels (gfx950) + native batch executor
-#   libtcamd_host.so  host codecs (BYTES pack/scan, baseline JPEG, PNG, the compare, QA span and WordPiece rules; links zlib)
+#   libtcamd_host.so  host codecs (BYTES pack/scan, baseline JPEG, PNG, the compare, QA span, QA merge and WordPiece rules; links zlib)
 HIPCC      ?= /opt/rocm/bin/hipcc
 CXX        ?= g++
 ARCH       ?= gfx950
@@ -33,10 +33,10 @@ $(HIPLIB): $(HIP_OBJS)
 
 $(HOSTLIB): csrc/host/host_codec.cc csrc/host/jpeg.cc csrc/host/jpeg.h csrc/kernels/jpeg_math.h csrc/kernels/jpeg_huff_core.h csrc/kernels/jpeg_huff_wide_core.h \
 		csrc/host/png.cc csrc/host/png.h csrc/kernels/png_math.h csrc/host/compare.cc csrc/kernels/compare_math.h \
-		csrc/host/qa_spans.cc csrc/kernels/qa_span_math.h \
+		csrc/host/qa_spans.cc csrc/host/qa_merge.cc csrc/kernels/qa_span_math.h \
 		csrc/host/wordpiece.cc csrc/kernels/wordpiece_core.h csrc/kernels/wordpiece_table.h
 	@mkdir -p $(dir $@)
-	$(CXX) $(CXXFLAGS) -shared -o $@ csrc/host/host_codec.cc csrc/host/jpeg.cc csrc/host/png.cc csrc/host/compare.cc csrc/host/qa_spans.cc csrc/host/wordpiece.cc -lz
+	$(CXX) $(CXXFLAGS) -shared -o $@ csrc/host/host_codec.cc csrc/host/jpeg.cc csrc/host/png.cc csrc/host/compare.cc csrc/host/qa_spans.cc csrc/host/qa_merge.cc csrc/host/wordpiece.cc -lz
 
 clean:
 	rm -rf build $(CSHM) $(HIPLIB) $(HOSTLIB)

@@ -8,17 +8,14 @@
 
 #include "../kernels/qa_span_math.h"
 
-extern "C" {
+namespace {
 
-// Returns 0, or 1 (the value of hipErrorInvalidValue) for what the device entry
-// refuses too; then nothing is written.
-int tcamd_host_qa_spans(const float* start, const float* end, uint64_t logit_stride_bytes, const int32_t* mask,
-                        const int32_t* ttype, uint64_t ids_stride_bytes, int32_t rows, int32_t S, const int32_t* k_row,
-                        const int32_t* len_row, int32_t kmax, int32_t* spans, float* scores, float* null_score) {
+// start_ok null: every eligible token may start a span
+int qa_spans_host(const float* start, const float* end, uint64_t logit_stride_bytes, const int32_t* mask,
+                  const int32_t* ttype, const int32_t* start_ok, uint64_t ids_stride_bytes, int32_t rows, int32_t S,
+                  const int32_t* k_row, const int32_t* len_row, int32_t kmax, int32_t* spans, float* scores,
+                  float* null_score) {
   using namespace tcamd_qa;
-  if (!args_valid(start, end, logit_stride_bytes, mask, ttype, ids_stride_bytes, rows, S, k_row, len_row, kmax, spans,
-                  scores, null_score))
-    return 1;
   const auto row = [](const void* base, int64_t r, uint64_t stride) {
     return static_cast<const uint8_t*>(base) + r * stride;
   };
@@ -31,11 +28,12 @@ int tcamd_host_qa_spans(const float* start, const float* end, uint64_t logit_str
     const float* en = reinterpret_cast<const float*>(row(end, r, logit_stride_bytes));
     const int32_t* mk = reinterpret_cast<const int32_t*>(row(mask, r, ids_stride_bytes));
     const int32_t* tt = reinterpret_cast<const int32_t*>(row(ttype, r, ids_stride_bytes));
+    const int32_t* so = start_ok ? reinterpret_cast<const int32_t*>(row(start_ok, r, ids_stride_bytes)) : nullptr;
     put(null_score + r, score_bits(f32_bits(st[0]), f32_bits(en[0])));
     const int L = clamp_len(len_row[r], S);
     int n = 0;  // keys in the heap, the smallest on top
     for (int s = 0; s < S && L > 0; ++s) {
-      if (!eligible(mk[s], tt[s])) continue;
+      if (!eligible(mk[s], tt[s]) || (so && so[s] < 1)) continue;
       const int hi = std::min(s + L, (int)S);
       for (int e = s; e < hi; ++e) {
         if (!eligible(mk[e], tt[e])) continue;
@@ -68,6 +66,35 @@ int tcamd_host_qa_spans(const float* start, const float* end, uint64_t logit_str
     }
   }
   return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+// Returns 0, or 1 (the value of hipErrorInvalidValue) for what the device entry
+// refuses too; then nothing is written.
+int tcamd_host_qa_spans(const float* start, const float* end, uint64_t logit_stride_bytes, const int32_t* mask,
+                        const int32_t* ttype, uint64_t ids_stride_bytes, int32_t rows, int32_t S, const int32_t* k_row,
+                        const int32_t* len_row, int32_t kmax, int32_t* spans, float* scores, float* null_score) {
+  if (!tcamd_qa::args_valid(start, end, logit_stride_bytes, mask, ttype, ids_stride_bytes, rows, S, k_row, len_row,
+                            kmax, spans, scores, null_score))
+    return 1;
+  return qa_spans_host(start, end, logit_stride_bytes, mask, ttype, nullptr, ids_stride_bytes, rows, S, k_row, len_row,
+                       kmax, spans, scores, null_score);
+}
+
+// The host twin of tcamd_qa_spans_masked: a span may start only where start_ok >= 1.
+int tcamd_host_qa_spans_masked(const float* start, const float* end, uint64_t logit_stride_bytes, const int32_t* mask,
+                               const int32_t* ttype, const int32_t* start_ok, uint64_t ids_stride_bytes, int32_t rows,
+                               int32_t S, const int32_t* k_row, const int32_t* len_row, int32_t kmax, int32_t* spans,
+                               float* scores, float* null_score) {
+  if (!tcamd_qa::args_valid(start, end, logit_stride_bytes, mask, ttype, ids_stride_bytes, rows, S, k_row, len_row,
+                            kmax, spans, scores, null_score) ||
+      !start_ok || ((uintptr_t)start_ok & 3))
+    return 1;
+  return qa_spans_host(start, end, logit_stride_bytes, mask, ttype, start_ok, ids_stride_bytes, rows, S, k_row, len_row,
+                       kmax, spans, scores, null_score);
 }
 
 }  // extern "C"

@@ -5,8 +5,10 @@
 // kernels/qa_span_math.h, which both compile.
 //
 // One 256-thread workgroup per row.  The row's start and end bits and one
-// eligibility byte per token go into LDS once (9 bytes per token, 9.3 KB at
-// S = 1024).  Thread t owns the starts t, t + 256, t + 512 and t + 768 and
+// byte per token (bit 0 eligible, bit 1 may start a span: every eligible token
+// without a start mask, those with start_ok >= 1 with one) go into LDS once
+// (9 bytes per token, 9.3 KB at S = 1024).  Thread t owns the starts t,
+// t + 256, t + 512 and t + 768 and
 // keeps the best key of each one's window [s, min(s + L, S)) in four 64-bit
 // registers: one pass of about S * L / 256 evaluations per thread.  Then k
 // rounds.  A round takes the workgroup maximum of the per-start keys (64-bit
@@ -27,7 +29,9 @@
 //   * the round loop runs j < k, and its only break tests `win`, which every
 //     thread computes from the same four LDS words after the same barrier;
 //   * the loops between the barriers (the load, the first pass, the rescan)
-//     have per-thread bounds and contain no barrier and no shuffle;
+//     have per-thread bounds and contain no barrier and no shuffle; the start
+//     mask is read in the load alone and decides only which starts of the
+//     first pass have candidates;
 //   * the two reduction arrays alternate: red[0] is written before the first
 //     barrier of a round and read after it, red[1] before and after the second,
 //     so a slot is never rewritten before every thread has passed the barrier
@@ -60,8 +64,9 @@ __device__ __forceinline__ uint64_t wave_max_u64(uint64_t v) {
 __global__ void __launch_bounds__(kBlock)
 qa_spans_rows(const uint8_t* __restrict__ start, const uint8_t* __restrict__ end, uint64_t logit_stride,
               const uint8_t* __restrict__ mask, const uint8_t* __restrict__ ttype, uint64_t ids_stride, int S,
-              const int32_t* __restrict__ k_row, const int32_t* __restrict__ len_row, int kmax,
-              int32_t* __restrict__ spans, uint32_t* __restrict__ scores, uint32_t* __restrict__ null_score) {
+              const uint8_t* __restrict__ start_ok, const int32_t* __restrict__ k_row,
+              const int32_t* __restrict__ len_row, int kmax, int32_t* __restrict__ spans,
+              uint32_t* __restrict__ scores, uint32_t* __restrict__ null_score) {
   __shared__ uint32_t s_start[kMaxSeq];
   __shared__ uint32_t s_end[kMaxSeq];
   __shared__ uint8_t s_ok[kMaxSeq];
@@ -77,6 +82,7 @@ qa_spans_rows(const uint8_t* __restrict__ start, const uint8_t* __restrict__ end
   const uint32_t* en = reinterpret_cast<const uint32_t*>(end + r * logit_stride);
   const int32_t* mk = reinterpret_cast<const int32_t*>(mask + r * ids_stride);
   const int32_t* tt = reinterpret_cast<const int32_t*>(ttype + r * ids_stride);
+  const int32_t* so = start_ok ? reinterpret_cast<const int32_t*>(start_ok + r * ids_stride) : nullptr;
   int32_t* out_spans = spans + r * (uint64_t)kmax * 2;
   uint32_t* out_scores = scores + r * (uint64_t)kmax;
   if (t == 0) null_score[r] = score_bits(st[0], en[0]);
@@ -92,7 +98,7 @@ qa_spans_rows(const uint8_t* __restrict__ start, const uint8_t* __restrict__ end
   for (int i = t; i < S; i += kBlock) {
     s_start[i] = st[i];
     s_end[i] = en[i];
-    s_ok[i] = eligible(mk[i], tt[i]) ? 1 : 0;
+    s_ok[i] = token_bits(mk[i], tt[i], so != nullptr, so ? so[i] : 0);
   }
   __syncthreads();
 
@@ -102,7 +108,7 @@ qa_spans_rows(const uint8_t* __restrict__ start, const uint8_t* __restrict__ end
   for (int i = 0; i < kStartsPerThread; ++i) {
     const int s = t + i * kBlock;
     uint64_t best = 0;
-    if (s < S && s_ok[s]) {
+    if (s < S && (s_ok[s] & kTokStart)) {
       const uint32_t sb = s_start[s];
       const int hi = s + L < S ? s + L : S;
       const uint32_t base = (uint32_t)s * (uint32_t)S;
@@ -182,7 +188,28 @@ extern "C" int tcamd_qa_spans(const float* start, const float* end, uint64_t log
   if (rows == 0) return hipSuccess;
   hipLaunchKernelGGL(qa_spans_rows, dim3((unsigned)rows), dim3(kBlock), 0, s, reinterpret_cast<const uint8_t*>(start),
                      reinterpret_cast<const uint8_t*>(end), logit_stride_bytes, reinterpret_cast<const uint8_t*>(mask),
-                     reinterpret_cast<const uint8_t*>(ttype), ids_stride_bytes, (int)S, k_row, len_row, (int)kmax,
-                     spans, reinterpret_cast<uint32_t*>(scores), reinterpret_cast<uint32_t*>(null_score));
+                     reinterpret_cast<const uint8_t*>(ttype), ids_stride_bytes, (int)S,
+                     static_cast<const uint8_t*>(nullptr), k_row, len_row, (int)kmax, spans,
+                     reinterpret_cast<uint32_t*>(scores), reinterpret_cast<uint32_t*>(null_score));
+  return hipGetLastError();
+}
+
+// tcamd_qa_spans with a start mask: start_ok, device int32 rows ids_stride_bytes
+// apart like mask / ttype; a span may start only where start_ok >= 1.
+extern "C" int tcamd_qa_spans_masked(const float* start, const float* end, uint64_t logit_stride_bytes,
+                                     const int32_t* mask, const int32_t* ttype, const int32_t* start_ok,
+                                     uint64_t ids_stride_bytes, int32_t rows, int32_t S, const int32_t* k_row,
+                                     const int32_t* len_row, int32_t kmax, int32_t* spans, float* scores,
+                                     float* null_score, hipStream_t s) {
+  if (!args_valid(start, end, logit_stride_bytes, mask, ttype, ids_stride_bytes, rows, S, k_row, len_row, kmax, spans,
+                  scores, null_score) ||
+      !start_ok || ((uintptr_t)start_ok & 3))
+    return hipErrorInvalidValue;
+  if (rows == 0) return hipSuccess;
+  hipLaunchKernelGGL(qa_spans_rows, dim3((unsigned)rows), dim3(kBlock), 0, s, reinterpret_cast<const uint8_t*>(start),
+                     reinterpret_cast<const uint8_t*>(end), logit_stride_bytes, reinterpret_cast<const uint8_t*>(mask),
+                     reinterpret_cast<const uint8_t*>(ttype), ids_stride_bytes, (int)S,
+                     reinterpret_cast<const uint8_t*>(start_ok), k_row, len_row, (int)kmax, spans,
+                     reinterpret_cast<uint32_t*>(scores), reinterpret_cast<uint32_t*>(null_score));
   return hipGetLastError();
 }

@@ -39,6 +39,25 @@
 //             special tokens, overflow and the status word
 // Nothing is computed on the host.
 //
+// K28w, tcamd_wordpiece_windows, is the same call for contexts longer than a
+// row (rule 8 of the header: doc-stride windows).  A row of the table is a
+// document; its launches are the ten above over a clear of the call's row
+// capacity, with two changes:
+//   windows   one workgroup, between the second scan and the assemble: thread d
+//             turns t_npiece into document d's W, a workgroup scan of the W that
+//             passed max_windows gives the row bases, a second one of the rows
+//             that fit gives n_rows; the thread writes doc_info and the
+//             window_info of its rows
+//   assemble  windowed: the position that starts or ends context piece k finds
+//             the windows w_lo .. w_hi that hold k, at most ceil(cap / stride),
+//             the best of them by the max-context score in one loop, and stores
+//             into each in a second (O(windows) per piece); a question piece
+//             goes into every row of its document; one thread per text stores
+//             the special tokens of the document's rows
+// doc_info is the hand-over between the two: the assemble reads first row, W, P
+// and status from the output the windows launch finished, so the workspace does
+// not grow (tcamd_wordpiece_windows_workspace is tcamd_wordpiece_workspace).
+//
 // LDS is four words per workgroup whatever the text length; everything else is
 // in the caller's workspace (tcamd_wordpiece_workspace: 16 bytes per text byte
 // plus 135 KB).  Every store is a vector store; the only atomic is count's
@@ -50,7 +69,14 @@
 // launch finished writing (t_stat, t_err, t_nfold) or the row table: the same
 // addresses for all 256 threads, never threadIdx.  count reads t_stat only, not
 // t_err, which that launch itself updates.  The per-thread bounds (i < len,
-// p < n) guard loads and stores, never a block_scan.  No workgroup waits on
+// p < n) guard loads and stores, never a block_scan.  K28w adds two kernels.
+// wp_windows is one workgroup that returns nowhere: threads past the documents
+// carry zeros through both block_scans, and the per-thread loop over a
+// document's windows between them holds no barrier.  wp_assemble_windows returns, ahead of its block_scan, on
+// blockIdx, on doc_info[d][3] (the status the windows launch finished, one
+// address for the workgroup) and on t_nfold; a document with status 0 is not
+// dead, so t_nfold and t_base are what the earlier launches left.  The loops
+// over windows are bounded by W <= 128.  No workgroup waits on
 // another inside a launch: what one needs from others (chunk bases, match
 // lengths of the next chunk, piece marks) it reads after a kernel boundary.
 // No loop is unbounded: probes stop after `slots` steps, words after 101.
@@ -249,6 +275,55 @@ __global__ void __launch_bounds__(kBlock) wp_assemble(Ctx c) {
     }
 }
 
+// ---- K28w -------------------------------------------------------------------------
+// One workgroup per row of the call's capacity: zero before anything else writes.
+__global__ void __launch_bounds__(kBlock) wp_clear_windows(Ctx c) {
+  const uint64_t row = (uint64_t)blockIdx.x * (uint64_t)c.S;
+  for (int i = threadIdx.x; i < c.S; i += kBlock) {
+    c.ids[row + i] = 0;
+    c.mask[row + i] = 0;
+    c.type_ids[row + i] = 0;
+    c.start_mask[row + i] = 0;
+    c.offsets[2 * (row + i)] = 0;
+    c.offsets[2 * (row + i) + 1] = 0;
+  }
+  if (threadIdx.x < 4) c.window_info[4 * blockIdx.x + threadIdx.x] = 0;
+}
+
+__global__ void __launch_bounds__(kBlock) wp_windows(Ctx c) {
+  __shared__ uint32_t s_w[kWaves];
+  const int d = threadIdx.x;
+  uint32_t st = kStOk, P = 0, W = 0, total;
+  const uint32_t want = d < c.rows ? windows_doc(c, d, &st, &P, &W) : 0u;
+  const uint32_t base = block_scan(want, s_w, &total);
+  const uint32_t got = d < c.rows ? windows_place(c, d, st, P, W, base) : 0u;
+  block_scan(got, s_w, &total);
+  if (d == 0) c.n_rows[0] = (int32_t)total;
+}
+
+__global__ void __launch_bounds__(kBlock) wp_assemble_windows(Ctx c) {
+  __shared__ uint32_t s_w[kWaves];
+  const int t = blockIdx.y;
+  const uint32_t ch = blockIdx.x;
+  if (c.doc_info[4 * (t >> 1) + 3] != kStOk) return;
+  if (ch == 0 && threadIdx.x == 0) windows_text(c, t);
+  const uint32_t n = c.t_nfold[t], base = c.t_base[t];
+  if (ch * kChunk >= n) return;
+  const uint32_t p0 = ch * kChunk + threadIdx.x * kPerThread;
+  uint32_t cnt = 0;
+#pragma unroll
+  for (int j = 0; j < kPerThread; ++j)
+    if (p0 + j < n) cnt += piece_at(c, base, p0 + j);
+  uint32_t total;
+  uint32_t incl = c.ch_piece[t * kMaxChunks + ch] + block_scan(cnt, s_w, &total);
+#pragma unroll
+  for (int j = 0; j < kPerThread; ++j)
+    if (p0 + j < n) {
+      incl += piece_at(c, base, p0 + j);
+      windows_item(c, t, base, n, p0 + j, incl);
+    }
+}
+
 }  // namespace
 
 extern "C" uint64_t tcamd_wordpiece_workspace(int32_t rows, uint64_t text_bytes) {
@@ -298,5 +373,52 @@ extern "C" int tcamd_wordpiece_tokenize(const uint8_t* text, uint64_t text_bytes
   hipLaunchKernelGGL(wp_pieces, grid, block, 0, s, c);
   hipLaunchKernelGGL(wp_scan, one, block, 0, s, c, 1);
   hipLaunchKernelGGL(wp_assemble, grid, block, 0, s, c);
+  return hipGetLastError();
+}
+
+extern "C" uint64_t tcamd_wordpiece_windows_workspace(int32_t docs, uint64_t text_bytes) {
+  return workspace_bytes(docs, text_bytes);
+}
+
+// K28w.  The inputs of tcamd_wordpiece_tokenize, a row of the table being a
+// document, and per document doc_stride (stride_row, 1 .. S - 3) and
+// max_windows (maxw_row, 1 .. 128), device int32 [docs]; out_rows <= 128 is the
+// row capacity of the outputs.  ids / mask / type_ids / start_mask
+// [out_rows][S], offsets [out_rows][S][2], window_info [out_rows][4], doc_info
+// [docs][4] and n_rows [1] are as rule 8 of kernels/wordpiece_core.h has them;
+// rows from n_rows on are zero.  Refusals as tcamd_wordpiece_tokenize, and
+// out_rows outside 1 .. 128; docs == 0 is success without a launch.
+extern "C" int tcamd_wordpiece_windows(const uint8_t* text, uint64_t text_bytes, const uint32_t* row_table,
+                                       const int32_t* maxq_row, const int32_t* stride_row, const int32_t* maxw_row,
+                                       int32_t docs, int32_t S, const uint32_t* vocab, uint64_t vocab_words, void* ws,
+                                       uint64_t ws_bytes, int32_t out_rows, int32_t* ids, int32_t* mask,
+                                       int32_t* type_ids, int32_t* start_mask, int32_t* offsets, int32_t* window_info,
+                                       uint32_t* doc_info, int32_t* n_rows, hipStream_t s) {
+  if (!args_valid(text, row_table, maxq_row, docs, S, vocab, vocab_words, ws, ids, mask, type_ids, offsets, n_rows,
+                  doc_info) ||
+      !window_args_valid(stride_row, maxw_row, out_rows, start_mask, window_info, doc_info, n_rows))
+    return hipErrorInvalidValue;
+  Ctx c{};
+  if (!ctx_place(&c, ws, ws_bytes)) return hipErrorInvalidValue;
+  if (docs == 0) return hipSuccess;
+  c.text = text, c.text_bytes = text_bytes, c.row_table = row_table, c.maxq_row = maxq_row, c.rows = docs, c.S = S;
+  c.vocab = vocab, c.vocab_words = vocab_words;
+  c.ids = ids, c.mask = mask, c.type_ids = type_ids, c.offsets = offsets;
+  c.stride_row = stride_row, c.maxw_row = maxw_row, c.out_rows = out_rows;
+  c.start_mask = start_mask, c.window_info = window_info, c.doc_info = doc_info, c.n_rows = n_rows;
+  const uint64_t longest = text_bytes < kMaxTextBytes ? text_bytes : kMaxTextBytes;
+  const unsigned chunks = longest ? (unsigned)chunks_of((uint32_t)longest) : 1u;
+  const dim3 grid(chunks, 2u * (unsigned)docs), one(2u * (unsigned)docs), block(kBlock);
+  hipLaunchKernelGGL(wp_clear_windows, dim3((unsigned)out_rows), block, 0, s, c);
+  hipLaunchKernelGGL(wp_plan, dim3(1), block, 0, s, c);
+  hipLaunchKernelGGL(wp_count, grid, block, 0, s, c);
+  hipLaunchKernelGGL(wp_scan, one, block, 0, s, c, 0);
+  hipLaunchKernelGGL(wp_emit, grid, block, 0, s, c);
+  hipLaunchKernelGGL(wp_match, grid, block, 0, s, c);
+  hipLaunchKernelGGL(wp_walk, grid, block, 0, s, c);
+  hipLaunchKernelGGL(wp_pieces, grid, block, 0, s, c);
+  hipLaunchKernelGGL(wp_scan, one, block, 0, s, c, 1);
+  hipLaunchKernelGGL(wp_windows, dim3(1), block, 0, s, c);
+  hipLaunchKernelGGL(wp_assemble_windows, grid, block, 0, s, c);
   return hipGetLastError();
 }

@@ -34,6 +34,26 @@ to hold K28 against the host twin behind the same ensemble.  ``--text --kernel``
 K28 ``wordpiece_tokenize`` alone (its ten launches between two events) at 1, 8
 and 128 rows of such texts and at 128 rows of 64 KB contexts, next to the host
 twin on one core and, where it is installed, ``tokenizers``' ``encode_batch``.
+
+``--doc-stride N``: the same two for contexts longer than a row.  Served: one
+server with the doc-stride models and ``bert_qa_ensemble``, one document of 40
+and ``--context-bytes`` bytes per request (default 3000: the client's route below
+is bound to the 1021 pieces a 1024-token row of the host twin holds), in two modes:
+
+  doc       ``bert_qa_doc_ensemble`` asking for ``spans``, ``windows``,
+            ``scores``, ``null_score``, ``offsets`` and ``doc_info``: ids and
+            logits never leave the device
+  client    what a user had to do before: the host twin of the tokenizer on a
+            row of 1024 tokens, the windows sliced out of it in numpy
+            (``utils.qa.doc_windows``), one ``bert_qa_ensemble`` request of W
+            rows for the logits, and ``utils.qa.merge_windows``, all inside the
+            measured latency
+
+``--doc-stride N --kernel``: K28w ``wordpiece_windows`` (its launches between two
+events) and K27 masked + K29 ``qa_merge`` at 1 and 16 documents of
+``--context-bytes`` (default 4096), and K28w
+against K28 on 1, 8 and 128 contexts of 1000 bytes, which fit one window (the cost
+of the extra launch).
 """
 
 import argparse
@@ -276,7 +296,231 @@ def text_served(args):
         srv.stop()
 
 
-def closed_loop(c, mod, model, ins, outputs, conc, warmup, seconds, post):
+def _event_times(torch, launch, iters, warm=5):
+    for _ in range(warm):
+        launch()
+    torch.cuda.synchronize()
+    times = []
+    for _ in range(iters):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        launch()
+        b.record()
+        b.synchronize()
+        times.append(a.elapsed_time(b) * 1e3)
+    return times
+
+
+def doc_kernel_time(iters, doc_stride, context_bytes):
+    import numpy as np
+    import torch
+
+    from triton_client_amd.ops import hip, host_codec
+    from triton_client_amd.utils import wordpiece
+
+    torch.cuda.set_device(0)
+    hc = host_codec.load()
+    vocab = wordpiece.Vocab.load(wordpiece.default_vocab_path())
+    vocab_dev = torch.from_numpy(vocab.image.view(np.int32).copy()).cuda()
+    s = torch.cuda.current_stream().cuda_stream
+    stat = lambda t: {"mean_us": round(float(np.mean(t)), 2), "min_us": round(float(np.min(t)), 2),  # noqa: E731
+                      "max_us": round(float(np.max(t)), 2)}
+
+    def windows_call(qs, cs, out_rows=128):
+        buf, table = wordpiece.pack_texts(qs, cs)
+        docs = len(qs)
+        text = torch.from_numpy(np.array(buf)).cuda()
+        tab = torch.from_numpy(table.view(np.int32).copy()).cuda()
+        par = torch.tensor([[64] * docs, [doc_stride] * docs, [128] * docs], dtype=torch.int32, device="cuda")
+        ws_bytes = hip.wordpiece_windows_workspace(docs, buf.size)
+        ws = torch.zeros(ws_bytes, dtype=torch.uint8, device="cuda")
+        o = {n: torch.zeros(out_rows, SEQ, dtype=torch.int32, device="cuda") for n in ("ids", "mask", "tt", "sm")}
+        o["offsets"] = torch.zeros(out_rows, SEQ, 2, dtype=torch.int32, device="cuda")
+        o["winfo"] = torch.zeros(out_rows, 4, dtype=torch.int32, device="cuda")
+        o["dinfo"] = torch.zeros(docs, 4, dtype=torch.int32, device="cuda")
+        o["n_rows"] = torch.zeros(1, dtype=torch.int32, device="cuda")
+
+        def launch():
+            hip.wordpiece_windows(text.data_ptr(), buf.size, tab.data_ptr(), par[0].data_ptr(), par[1].data_ptr(),
+                                  par[2].data_ptr(), docs, SEQ, vocab_dev.data_ptr(), vocab.image.size, ws.data_ptr(),
+                                  ws_bytes, out_rows, o["ids"].data_ptr(), o["mask"].data_ptr(), o["tt"].data_ptr(),
+                                  o["sm"].data_ptr(), o["offsets"].data_ptr(), o["winfo"].data_ptr(),
+                                  o["dinfo"].data_ptr(), o["n_rows"].data_ptr(), stream=s)
+
+        return launch, o, (buf, table, text, tab, ws_bytes, ws)
+
+    for docs in (1, 16):
+        qs, cs = make_texts(docs, context_bytes, docs)
+        launch, o, _ = windows_call(qs, cs)
+        times = _event_times(torch, launch, iters)
+        t0 = time.perf_counter()
+        want = hc.wordpiece_windows(qs, cs, vocab, 64, doc_stride, 128)
+        host_ms = (time.perf_counter() - t0) * 1e3
+        got = [o[n].cpu().numpy() for n in ("ids", "mask", "tt", "sm", "offsets", "winfo")]
+        n_rows = int(o["n_rows"].cpu()[0])
+        same = n_rows == want[7] and all(np.array_equal(g, w) for g, w in zip(got, want[:6])) and \
+            np.array_equal(o["dinfo"].cpu().numpy(), want[6].view(np.int32))
+        res = {"kernel": "K28w wordpiece_windows", "documents": docs, "context_bytes": context_bytes,
+               "doc_stride": doc_stride, "rows": n_rows, "launches": iters, "host_twin_ms": round(host_ms, 3),
+               "equals_host_twin": bool(same)}
+        res.update(stat(times))
+        print(json.dumps(res), flush=True)
+        # K27 with the start mask, then K29, on random logits over those windows
+        rng = np.random.default_rng(docs)
+        st, en = (torch.from_numpy(rng.standard_normal((128, SEQ)).astype(np.float32)).cuda() for _ in range(2))
+        k = 20
+        k_row = torch.full((128,), k, dtype=torch.int32, device="cuda")
+        len_row = torch.full((128,), 30, dtype=torch.int32, device="cuda")
+        l_spans = torch.zeros(128, k, 2, dtype=torch.int32, device="cuda")
+        l_scores, l_null = torch.zeros(128, k, device="cuda"), torch.zeros(128, device="cuda")
+        d_spans = torch.zeros(docs, k, 2, dtype=torch.int32, device="cuda")
+        d_win = torch.zeros(docs, k, dtype=torch.int32, device="cuda")
+        d_scores, d_null = torch.zeros(docs, k, device="cuda"), torch.zeros(docs, device="cuda")
+
+        def spans():
+            hip.qa_spans_masked(st.data_ptr(), en.data_ptr(), SEQ * 4, o["mask"].data_ptr(), o["tt"].data_ptr(),
+                                o["sm"].data_ptr(), SEQ * 4, n_rows, SEQ, k_row.data_ptr(), len_row.data_ptr(), k,
+                                l_spans.data_ptr(), l_scores.data_ptr(), l_null.data_ptr(), stream=s)
+
+        def merge():
+            hip.qa_merge(l_spans.data_ptr(), l_scores.data_ptr(), l_null.data_ptr(), n_rows, o["winfo"].data_ptr(),
+                         o["dinfo"].data_ptr(), docs, k_row.data_ptr(), k, d_spans.data_ptr(), d_win.data_ptr(),
+                         d_scores.data_ptr(), d_null.data_ptr(), stream=s)
+
+        t27 = _event_times(torch, spans, iters)
+        t29 = _event_times(torch, merge, iters)
+        lists = hc.qa_spans_masked(st.cpu().numpy()[:n_rows], en.cpu().numpy()[:n_rows], want[1][:n_rows],
+                                   want[2][:n_rows], want[3][:n_rows], [k] * n_rows, [30] * n_rows, k)
+        w29 = hc.qa_merge(*lists, want[5][:n_rows], want[6], [k] * docs, k)
+        same = all(g.cpu().numpy().tobytes() == w.tobytes() for g, w in zip((d_spans, d_win, d_scores, d_null), w29))
+        res = {"kernel": "K29 qa_merge", "documents": docs, "rows": n_rows, "n_best": k, "launches": iters,
+               "equals_host_twin": bool(same), "k27_masked_mean_us": round(float(np.mean(t27)), 2),
+               "k27_masked_min_us": round(float(np.min(t27)), 2)}
+        res.update(stat(t29))
+        print(json.dumps(res), flush=True)
+    # contexts that fit one window: K28w against K28 on the same texts
+    for rows in (1, 8, 128):
+        qs, cs = make_texts(rows, 1000, rows)
+        launch_w, o, (buf, table, text, tab, ws_bytes, ws) = windows_call(qs, cs)
+        mq = torch.full((rows,), 64, dtype=torch.int32, device="cuda")
+        ids, mask, tt = (torch.zeros(rows, SEQ, dtype=torch.int32, device="cuda") for _ in range(3))
+        offsets = torch.zeros(rows, SEQ, 2, dtype=torch.int32, device="cuda")
+        overflow, status = (torch.zeros(rows, dtype=torch.int32, device="cuda") for _ in range(2))
+
+        def launch_k28():
+            hip.wordpiece_tokenize(text.data_ptr(), buf.size, tab.data_ptr(), mq.data_ptr(), rows, SEQ,
+                                   vocab_dev.data_ptr(), vocab.image.size, ws.data_ptr(), ws_bytes, ids.data_ptr(),
+                                   mask.data_ptr(), tt.data_ptr(), offsets.data_ptr(), overflow.data_ptr(),
+                                   status.data_ptr(), stream=s)
+
+        tw, t28 = [], []
+        for _ in range(3):  # alternate, so that drift hits both alike
+            t28 += _event_times(torch, launch_k28, iters // 3 + 1)
+            tw += _event_times(torch, launch_w, iters // 3 + 1)
+        same = int(o["n_rows"].cpu()[0]) == rows and torch.equal(o["ids"][:rows], ids) and \
+            torch.equal(o["offsets"][:rows], offsets) and not bool(overflow.any())
+        print(json.dumps({"kernel": "K28w against K28, one window", "rows": rows, "context_bytes": 1000,
+                          "k28_mean_us": round(float(np.mean(t28)), 2), "k28_min_us": round(float(np.min(t28)), 2),
+                          "k28w_mean_us": round(float(np.mean(tw)), 2), "k28w_min_us": round(float(np.min(tw)), 2),
+                          "ratio_of_means": round(float(np.mean(tw) / np.mean(t28)), 3),
+                          "ratio_of_mins": round(float(np.min(tw) / np.min(t28)), 3), "same_rows": bool(same)}),
+              flush=True)
+
+
+def doc_served(args):
+    import numpy as np
+
+    import tritonclient.grpc as grpcclient
+    from triton_client_amd.ops import host_codec
+    from triton_client_amd.perf.harness import ServerProcess
+    from triton_client_amd.utils import qa, wordpiece
+
+    log = os.path.abspath(args.server_log) if args.server_log else None
+    if log:
+        os.makedirs(os.path.dirname(log), exist_ok=True)
+    srv = ServerProcess(device=0, models="bert_window_tokenizer,bert_large,qa_doc_spans,bert_qa_doc_ensemble,qa_spans,"
+                                         "bert_qa_ensemble", log_path=log,
+                        extra_args=["--native-grpc", args.native_grpc])
+    try:
+        srv.wait_ready(timeout=900, model="bert_qa_doc_ensemble")
+        qs, cs = make_texts(1, args.context_bytes, 0)
+        hc = host_codec.load()
+        vocab = wordpiece.Vocab.load(wordpiece.default_vocab_path())
+        c = grpcclient.InferenceServerClient(srv.grpc_url)
+        doc_ins = []
+        for name, col in (("question", qs), ("context", cs)):
+            x = grpcclient.InferInput(name, [1], "BYTES")
+            x.set_data_from_numpy(np.array(col, dtype=object))
+            doc_ins.append(x)
+        keep = {}
+
+        def client_windows():
+            """The rows a client cuts by hand: one row of 1024 tokens from the host twin, sliced."""
+            ids, mask, tt, offsets, overflow, status = hc.wordpiece_tokenize(qs, cs, vocab, 64, 1024)
+            if status[0] or overflow[0]:
+                raise SystemExit("the client-side route needs a context of at most 1021 pieces")
+            first = int(tt[0].argmax()) if tt[0].any() else 2
+            qn, P = first - 2, int(tt[0].sum())
+            starts, lens, best = qa.doc_windows(P, qn, args.doc_stride, SEQ)
+            W = len(starts)
+            w_ids, w_mask, w_tt, w_sm = (np.zeros((W, SEQ), np.int32) for _ in range(4))
+            w_off = np.zeros((W, SEQ, 2), np.int32)
+            for w in range(W):
+                a, n = int(starts[w]), int(lens[w])
+                w_ids[w, :first] = ids[0, :first]
+                w_ids[w, first:first + n] = ids[0, first + a:first + a + n]
+                w_ids[w, first + n] = vocab.sep
+                w_mask[w, :first + n + 1] = 1
+                w_tt[w, first:first + n] = 1
+                w_sm[w, first:first + n] = best[a:a + n] == w
+                w_off[w, first:first + n] = offsets[0, first + a:first + a + n]
+            winfo = np.stack([np.zeros(W, np.int64), starts, lens, np.full(W, first)], axis=1).astype(np.int32)
+            keep.update(ids=w_ids, mask=w_mask, tt=w_tt, sm=w_sm, winfo=winfo, dinfo=np.array([[0, W, P, 0]], np.int32),
+                        offsets=w_off)
+            ins = []
+            for name, a in (("input_ids", w_ids), ("attention_mask", w_mask), ("token_type_ids", w_tt)):
+                x = grpcclient.InferInput(name, list(a.shape), "INT32")
+                x.set_data_from_numpy(a)
+                ins.append(x)
+            return ins
+
+        def client_merge(result):
+            return qa.merge_windows(result.as_numpy("start_logits"), result.as_numpy("end_logits"), keep["mask"],
+                                    keep["tt"], keep["sm"], keep["winfo"], keep["dinfo"], 20, 30)
+
+        params = {"doc_stride": args.doc_stride}
+        r = c.infer("bert_qa_doc_ensemble", doc_ins, parameters=params)
+        mine = client_merge(c.infer("bert_qa_ensemble", client_windows()))
+        same_rows = all(np.array_equal(r.as_numpy(n), keep[k]) for n, k in (
+            ("input_ids", "ids"), ("attention_mask", "mask"), ("token_type_ids", "tt"), ("start_mask", "sm"),
+            ("offsets", "offsets"), ("window_info", "winfo"), ("doc_info", "dinfo")))
+        agree = all(np.array_equal(r.as_numpy(n).view(np.uint32), m.view(np.uint32))
+                    for n, m in zip(("spans", "windows", "scores", "null_score"), mine))
+        t0 = time.perf_counter()
+        for _ in range(3):
+            client_windows()
+        cut_ms = (time.perf_counter() - t0) / 3 * 1e3
+        doc_out = ["spans", "windows", "scores", "null_score", "offsets", "doc_info"]
+        for rep in range(args.reps):
+            for conc in args.concurrency:
+                res = closed_loop(c, grpcclient, "bert_qa_doc_ensemble", doc_ins, doc_out, conc, args.warmup,
+                                  args.seconds, lambda result: None, parameters=params)
+                res.update(mode="doc")
+                res2 = closed_loop(c, grpcclient, "bert_qa_ensemble", client_windows, ["start_logits", "end_logits"],
+                                   conc, args.warmup, args.seconds, client_merge)
+                res2.update(mode="client", client_tokenize_and_slice_ms=round(cut_ms, 3))
+                for x in (res, res2):
+                    x.update(rep=rep, documents_per_request=1, context_bytes=args.context_bytes,
+                             doc_stride=args.doc_stride, windows=int(keep["dinfo"][0, 1]),
+                             same_windows=bool(same_rows), doc_equals_client_route=bool(agree),
+                             native_grpc=args.native_grpc)
+                    print(json.dumps(x), flush=True)
+        c.close()
+    finally:
+        srv.stop()
+
+
+def closed_loop(c, mod, model, ins, outputs, conc, warmup, seconds, post, parameters=None):
     """``conc`` requests in flight; ``post(result)`` runs in the callback, inside the measured latency;
     ``ins`` may be a function that makes a request's inputs, called inside it too."""
     lock = threading.Lock()
@@ -304,7 +548,7 @@ def closed_loop(c, mod, model, ins, outputs, conc, warmup, seconds, post):
             if again:
                 send()
 
-        c.async_infer(model, ins() if callable(ins) else ins, callback=cb, outputs=outs)
+        c.async_infer(model, ins() if callable(ins) else ins, callback=cb, outputs=outs, parameters=parameters)
 
     for _ in range(conc):
         send()
@@ -380,6 +624,10 @@ def main():
     ap.add_argument("--text", action="store_true", help="the text route: K28 / bert_qa_text_ensemble (see above)")
     ap.add_argument("--device-tokenizer", type=int, default=None, choices=[0, 1],
                     help="--text: TCAMD_DEVICE_TOKENIZER of the server (default: the knob's default)")
+    ap.add_argument("--doc-stride", type=int, default=None, metavar="N",
+                    help="the doc-stride route: K28w, K29 / bert_qa_doc_ensemble at this stride (see above)")
+    ap.add_argument("--context-bytes", type=int, default=None,
+                    help="--doc-stride: bytes of the context (default 4096 with --kernel, else 3000)")
     ap.add_argument("--iters", type=int, default=200, help="--kernel: timed launches per point (after 10 warm-up)")
     ap.add_argument("--concurrency", type=int, nargs="+", default=[1, 8])
     ap.add_argument("--rows", type=int, default=1, help="rows per request")
@@ -391,7 +639,11 @@ def main():
                          "ensemble to the Python one; off = the Python front end answers both modes")
     ap.add_argument("--server-log", default="", metavar="PATH", help="keep the server's log in this file")
     args = ap.parse_args()
-    if args.text:
+    if args.doc_stride is not None:
+        if args.context_bytes is None:
+            args.context_bytes = 4096 if args.kernel else 3000
+        doc_kernel_time(args.iters, args.doc_stride, args.context_bytes) if args.kernel else doc_served(args)
+    elif args.text:
         text_kernel_time(args.iters) if args.kernel else text_served(args)
     elif args.kernel:
         kernel_time(args.iters)

@@ -18,6 +18,9 @@ events, peer access.  Kernels (csrc/kernels/*.hip, gfx950):
 * :func:`topk_rows`       K19 per-row top-K {score, index} pairs (classification)
 * :func:`qa_spans`        K27 per-row n best answer spans of question-answering logits
 * :func:`wordpiece_tokenize`  K28 UTF-8 text to BERT question-answering rows (WordPiece)
+* :func:`wordpiece_windows`   K28w the same over doc-stride windows of a long context
+* :func:`qa_spans_masked`     K27 with a start mask (the max-context rule of the windows)
+* :func:`qa_merge`            K29 the n best spans of a document from those of its windows
 
 Pointers are plain ints (device addresses).  ``stream`` is a hipStream_t as an
 int (``torch.cuda.current_stream().cuda_stream`` works) or None for the
@@ -210,6 +213,32 @@ _SIGS = {
         ctypes.c_int,
     ),
     "tcamd_wordpiece_workspace": ([ctypes.c_int32, ctypes.c_uint64], ctypes.c_uint64),
+    "tcamd_wordpiece_windows_workspace": ([ctypes.c_int32, ctypes.c_uint64], ctypes.c_uint64),
+    "tcamd_wordpiece_windows": (
+        [
+            ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+            ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64,
+            ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+        ],
+        ctypes.c_int,
+    ),
+    "tcamd_qa_spans_masked": (
+        [
+            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+            ctypes.c_uint64, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32,
+            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+        ],
+        ctypes.c_int,
+    ),
+    "tcamd_qa_merge": (
+        [
+            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
+            ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+            ctypes.c_void_p, ctypes.c_void_p,
+        ],
+        ctypes.c_int,
+    ),
     "tcamd_wordpiece_geometry": ([ctypes.POINTER(ctypes.c_int32)], None),
     # fused DenseNet kernels (csrc/kernels/densenet.hip)
     "tcamd_dn_conv1x1": (
@@ -997,6 +1026,39 @@ def qa_spans(start_ptr, end_ptr, logit_stride_bytes, mask_ptr, token_type_ptr, i
                                   _vp(stream)), "qa_spans")
 
 
+def qa_spans_masked(start_ptr, end_ptr, logit_stride_bytes, mask_ptr, token_type_ptr, start_ok_ptr, ids_stride_bytes,
+                    rows, S, k_row_ptr, len_row_ptr, kmax, spans_ptr, scores_ptr, null_score_ptr, stream=None):
+    """K27 with a start mask: :func:`qa_spans`, and a span may start only at a
+    token with ``start_ok >= 1`` (device int32 rows ``ids_stride_bytes`` apart,
+    the ``start_mask`` of :func:`wordpiece_windows`); its end needs eligibility
+    only."""
+    _check(_load().tcamd_qa_spans_masked(_vp(start_ptr), _vp(end_ptr), int(logit_stride_bytes), _vp(mask_ptr),
+                                         _vp(token_type_ptr), _vp(start_ok_ptr), int(ids_stride_bytes), int(rows),
+                                         int(S), _vp(k_row_ptr), _vp(len_row_ptr), int(kmax), _vp(spans_ptr),
+                                         _vp(scores_ptr), _vp(null_score_ptr), _vp(stream)), "qa_spans_masked")
+
+
+QA_MERGE_MAX_ROWS = 128  # tcamd_qa::kMergeMaxRows: the windows of one document
+
+
+def qa_merge(spans_ptr, scores_ptr, null_score_ptr, rows, window_info_ptr, doc_info_ptr, docs, k_doc_ptr, kmax,
+             out_spans_ptr, out_windows_ptr, out_scores_ptr, out_null_ptr, stream=None):
+    """K29: the n best spans of each document from the n best of its windows
+    (csrc/kernels/qa_span_math.h).  ``spans`` ``[rows, kmax, 2]``, ``scores``
+    ``[rows, kmax]`` and ``null_score`` ``[rows]`` are what
+    :func:`qa_spans_masked` left with ``k_row`` = the document's ``k``;
+    ``window_info`` ``[rows, 4]`` and ``doc_info`` ``[docs, 4]`` what
+    :func:`wordpiece_windows` left; ``k_doc`` device int32 ``[docs]``.  Document
+    ``d`` gets int32 ``out_spans[d][:kmax][2]`` (tokens of the window's row),
+    ``out_windows[d][:kmax]`` (the row), fp32 ``out_scores[d][:kmax]`` and
+    ``out_null[d]`` (the lowest null score of its rows); ranks past the
+    candidates hold ``(-1, -1)``, ``-1`` and ``-FLT_MAX``.  One launch."""
+    _check(_load().tcamd_qa_merge(_vp(spans_ptr), _vp(scores_ptr), _vp(null_score_ptr), int(rows),
+                                  _vp(window_info_ptr), _vp(doc_info_ptr), int(docs), _vp(k_doc_ptr), int(kmax),
+                                  _vp(out_spans_ptr), _vp(out_windows_ptr), _vp(out_scores_ptr), _vp(out_null_ptr),
+                                  _vp(stream)), "qa_merge")
+
+
 WORDPIECE_GEOMETRY = ("chunk", "block", "max_text_bytes", "max_word_chars", "max_rows", "max_chunks")
 
 
@@ -1040,6 +1102,38 @@ def wordpiece_tokenize(text_ptr, text_bytes, row_table_ptr, maxq_row_ptr, rows, 
                                             int(workspace_bytes), _vp(ids_ptr), _vp(mask_ptr), _vp(type_ids_ptr),
                                             _vp(offsets_ptr), _vp(overflow_ptr), _vp(status_ptr), _vp(stream)),
            "wordpiece_tokenize")
+
+
+WORDPIECE_MAX_WINDOWS = 128  # tcamd_wp::kMaxWindows: per document, and rows per windowed call
+
+
+def wordpiece_windows_workspace(docs, text_bytes):
+    """Bytes of device workspace :func:`wordpiece_windows` needs for ``docs``
+    documents whose texts have ``text_bytes`` bytes in all (what
+    :func:`wordpiece_workspace` says: the windows need none of their own)."""
+    return int(_load().tcamd_wordpiece_windows_workspace(int(docs), int(text_bytes)))
+
+
+def wordpiece_windows(text_ptr, text_bytes, row_table_ptr, maxq_row_ptr, stride_row_ptr, maxw_row_ptr, docs, S,
+                      vocab_ptr, vocab_words, workspace_ptr, workspace_bytes, out_rows, ids_ptr, mask_ptr, type_ids_ptr,
+                      start_mask_ptr, offsets_ptr, window_info_ptr, doc_info_ptr, n_rows_ptr, stream=None):
+    """K28w: :func:`wordpiece_tokenize` over doc-stride windows (rule 8 of
+    csrc/kernels/wordpiece_core.h).  A row of ``row_table`` is a document;
+    ``stride_row`` / ``maxw_row`` are device int32 ``[docs]`` (``doc_stride`` in
+    1..S-3, ``max_windows`` in 1..128), ``out_rows`` <= 128 the row capacity of
+    the outputs: int32 ``ids`` / ``mask`` / ``type_ids`` / ``start_mask``
+    ``[out_rows, S]``, ``offsets`` ``[out_rows, S, 2]``, ``window_info``
+    ``[out_rows, 4]`` = ``{document, first context piece, context pieces, token
+    of the first context piece}``, uint32 ``doc_info`` ``[docs, 4]`` = ``{first
+    row, windows, context pieces, status}`` and int32 ``n_rows`` ``[1]``; rows
+    from ``n_rows`` on are zero.  Eleven launches on ``stream`` (K28's ten, the
+    clear among them, and one more), nothing on the host."""
+    _check(_load().tcamd_wordpiece_windows(_vp(text_ptr), int(text_bytes), _vp(row_table_ptr), _vp(maxq_row_ptr),
+                                           _vp(stride_row_ptr), _vp(maxw_row_ptr), int(docs), int(S), _vp(vocab_ptr),
+                                           int(vocab_words), _vp(workspace_ptr), int(workspace_bytes), int(out_rows),
+                                           _vp(ids_ptr), _vp(mask_ptr), _vp(type_ids_ptr), _vp(start_mask_ptr),
+                                           _vp(offsets_ptr), _vp(window_info_ptr), _vp(doc_info_ptr), _vp(n_rows_ptr),
+                                           _vp(stream)), "wordpiece_windows")
 
 
 def dn_conv1x1(x, ldx, M, K, in_scale, in_bias, w, N, out_bias, relu_out, y, ldy, pool=0, H=0, W=0, stream=None,

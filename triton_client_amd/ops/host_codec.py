@@ -129,6 +129,25 @@ class HostCodec:
                                             ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p,
                                             ctypes.c_void_p, ctypes.c_void_p]
         lib.tcamd_host_qa_spans.restype = ctypes.c_int
+        lib.tcamd_host_qa_spans_masked.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
+                                                   ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int32,
+                                                   ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32,
+                                                   ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+        lib.tcamd_host_qa_spans_masked.restype = ctypes.c_int
+        lib.tcamd_host_qa_merge.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32,
+                                            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p,
+                                            ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                            ctypes.c_void_p]
+        lib.tcamd_host_qa_merge.restype = ctypes.c_int
+        wpw = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+               ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_uint64]
+        wouts = [ctypes.c_int32] + [ctypes.c_void_p] * 8
+        lib.tcamd_host_wordpiece_windows.argtypes = wpw + wouts
+        lib.tcamd_host_wordpiece_windows.restype = ctypes.c_int
+        lib.tcamd_host_wordpiece_windows_emulate.argtypes = wpw + [ctypes.c_void_p, ctypes.c_uint64] + wouts
+        lib.tcamd_host_wordpiece_windows_emulate.restype = ctypes.c_int
+        lib.tcamd_host_wordpiece_windows_workspace.argtypes = [ctypes.c_int32, ctypes.c_uint64]
+        lib.tcamd_host_wordpiece_windows_workspace.restype = ctypes.c_uint64
         wp = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32,
               ctypes.c_void_p, ctypes.c_uint64]
         outs = [ctypes.c_void_p] * 6
@@ -249,6 +268,71 @@ class HostCodec:
                           ptr(spans), ptr(scores), null.ctypes.data)
         return spans, scores, null[:rows]
 
+    def qa_spans_masked(self, start, end, attention_mask, token_type_ids, start_mask, k_row, len_row, kmax=None):
+        """K27 with a start mask on the host, bit for bit: :meth:`qa_spans`, and
+        a span may start only where ``start_mask`` (int32 ``[rows, S]``) is at
+        least 1."""
+        st = np.ascontiguousarray(start, dtype=np.float32)
+        en = np.ascontiguousarray(end, dtype=np.float32)
+        mk = np.ascontiguousarray(attention_mask, dtype=np.int32)
+        tt = np.ascontiguousarray(token_type_ids, dtype=np.int32)
+        so = np.ascontiguousarray(start_mask, dtype=np.int32)
+        if st.ndim != 2 or not (st.shape == en.shape == mk.shape == tt.shape == so.shape):
+            raise ValueError("qa_spans_masked: the five inputs must be [rows, S] arrays of one shape")
+        rows, S = st.shape
+        k = np.ascontiguousarray(k_row, dtype=np.int32).reshape(-1)
+        ln = np.ascontiguousarray(len_row, dtype=np.int32).reshape(-1)
+        if k.size != rows or ln.size != rows:
+            raise ValueError("qa_spans_masked: k_row and len_row must have one entry per row")
+        if kmax is None:
+            kmax = max(1, int(k.max())) if rows else 1
+        spans = np.zeros((rows, kmax, 2), dtype=np.int32)
+        scores = np.zeros((rows, kmax), dtype=np.float32)
+        null = np.zeros((max(rows, 1),), dtype=np.float32)
+        one = np.zeros(1, dtype=np.int32)
+        ptr = lambda a: a.ctypes.data if a.size else one.ctypes.data  # noqa: E731
+        if self._lib.tcamd_host_qa_spans_masked(ptr(st), ptr(en), S * 4, ptr(mk), ptr(tt), ptr(so), S * 4, rows, S,
+                                                ptr(k), ptr(ln), int(kmax), ptr(spans), ptr(scores), null.ctypes.data):
+            raise ValueError("qa_spans_masked: a size, pointer or stride the rule refuses")
+        return spans, scores, null[:rows]
+
+    def qa_merge(self, spans, scores, null_score, window_info, doc_info, k_doc, kmax=None):
+        """K29 ``qa_merge`` on the host, bit for bit: ``spans`` int32 ``[rows,
+        kmax, 2]``, ``scores`` fp32 ``[rows, kmax]`` and ``null_score`` fp32
+        ``[rows]`` as :meth:`qa_spans_masked` returns them, ``window_info`` int32
+        ``[rows, 4]`` and ``doc_info`` uint32 ``[docs, 4]`` as
+        :meth:`wordpiece_windows` returns them, ``k_doc`` int32 ``[docs]``.
+        Returns ``(spans [docs, kmax, 2], windows [docs, kmax], scores [docs,
+        kmax], null_score [docs])``; ranks past ``k_doc[d]`` hold zeros."""
+        sp = np.ascontiguousarray(spans, dtype=np.int32)
+        sc = np.ascontiguousarray(scores, dtype=np.float32)
+        nu = np.ascontiguousarray(null_score, dtype=np.float32).reshape(-1)
+        wi = np.ascontiguousarray(window_info, dtype=np.int32)
+        di = np.ascontiguousarray(doc_info, dtype=np.uint32)
+        if sp.ndim != 3 or sp.shape[2] != 2 or sc.shape != sp.shape[:2] or nu.size != sp.shape[0] \
+                or wi.shape != (sp.shape[0], 4) or di.ndim != 2 or di.shape[1] != 4:
+            raise ValueError("qa_merge: spans [rows, kmax, 2], scores [rows, kmax], null [rows], window_info "
+                             "[rows, 4] and doc_info [docs, 4]")
+        rows, kin = sc.shape
+        docs = di.shape[0]
+        k = np.ascontiguousarray(k_doc, dtype=np.int32).reshape(-1)
+        if k.size != docs:
+            raise ValueError("qa_merge: k_doc must have one entry per document")
+        if kmax is None:
+            kmax = kin
+        if kmax != kin:
+            raise ValueError("qa_merge: kmax is the ranks of the input lists")
+        o_sp = np.zeros((docs, kmax, 2), dtype=np.int32)
+        o_wn = np.zeros((docs, kmax), dtype=np.int32)
+        o_sc = np.zeros((docs, kmax), dtype=np.float32)
+        o_nu = np.zeros((max(docs, 1),), dtype=np.float32)
+        one = np.zeros(4, dtype=np.int32)
+        ptr = lambda a: a.ctypes.data if a.size else one.ctypes.data  # noqa: E731
+        if self._lib.tcamd_host_qa_merge(ptr(sp), ptr(sc), ptr(nu), rows, ptr(wi), ptr(di), docs, ptr(k), int(kmax),
+                                         ptr(o_sp), ptr(o_wn), ptr(o_sc), o_nu.ctypes.data):
+            raise ValueError("qa_merge: a size or pointer the rule refuses")
+        return o_sp, o_wn, o_sc, o_nu[:docs]
+
     # -- the BERT tokenizer (csrc/kernels/wordpiece_core.h) -------------------------------
     WORDPIECE_GEOMETRY = ("chunk", "block", "max_text_bytes", "max_word_chars", "max_rows", "max_chunks")
 
@@ -308,6 +392,51 @@ class HostCodec:
         if rc:
             raise ValueError("wordpiece_tokenize: a size or pointer the rule refuses")
         return ids[:rows], mask[:rows], tt[:rows], offsets[:rows], overflow[:rows], status[:rows]
+
+    def wordpiece_windows_workspace(self, docs, text_bytes):
+        """``ops.hip.wordpiece_windows_workspace`` without the device library."""
+        return int(self._lib.tcamd_host_wordpiece_windows_workspace(int(docs), int(text_bytes)))
+
+    def wordpiece_windows(self, questions, contexts, vocab, max_query_length=64, doc_stride=128, max_windows=128, S=384,
+                          out_rows=128, emulate=False, workspace_bytes=None):
+        """K28w ``wordpiece_windows`` on the host, bit for bit: one document per
+        question and context; ``max_query_length``, ``doc_stride`` and
+        ``max_windows`` one int or one per document; ``out_rows`` the row
+        capacity.  Returns ``(ids, mask, type_ids, start_mask, offsets,
+        window_info, doc_info, n_rows)``: int32 ``[out_rows, S]`` four times,
+        int32 ``[out_rows, S, 2]``, int32 ``[out_rows, 4]``, uint32 ``[docs, 4]``
+        and an int (rule 8 of csrc/kernels/wordpiece_core.h).  ``emulate`` runs
+        the kernel's phases in the kernel's workspace layout."""
+        from triton_client_amd.utils import wordpiece as wp
+
+        buf, table = wp.pack_texts(questions, contexts)
+        docs = table.shape[0]
+        per_doc = lambda v: np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=np.int32), (docs,)))  # noqa: E731
+        mq, ds, mw = per_doc(max_query_length), per_doc(doc_stride), per_doc(max_windows)
+        image = np.ascontiguousarray(vocab.image, dtype=np.uint32)
+        cap = max(int(out_rows), 1)
+        ids, mask, tt, sm = (np.zeros((cap, S), dtype=np.int32) for _ in range(4))
+        offsets = np.zeros((cap, S, 2), dtype=np.int32)
+        winfo = np.zeros((cap, 4), dtype=np.int32)
+        dinfo = np.zeros((max(docs, 1), 4), dtype=np.uint32)
+        n_rows = np.zeros(1, dtype=np.int32)
+        text = buf if buf.size else np.zeros(4, dtype=np.uint8)
+        tab = table if docs else np.zeros((1, 4), dtype=np.uint32)
+        one = np.zeros(1, dtype=np.int32)
+        head = (text.ctypes.data, int(buf.size), tab.ctypes.data) + tuple((a if docs else one).ctypes.data
+                                                                          for a in (mq, ds, mw)) + \
+            (docs, int(S), image.ctypes.data, int(image.size))
+        outs = (int(out_rows),) + tuple(a.ctypes.data for a in (ids, mask, tt, sm, offsets, winfo, dinfo, n_rows))
+        if emulate:
+            nbytes = self.wordpiece_windows_workspace(docs, buf.size) if workspace_bytes is None \
+                else int(workspace_bytes)
+            ws = np.zeros(max(nbytes // 4, 1), dtype=np.uint32)
+            rc = self._lib.tcamd_host_wordpiece_windows_emulate(*head, ws.ctypes.data, nbytes, *outs)
+        else:
+            rc = self._lib.tcamd_host_wordpiece_windows(*head, *outs)
+        if rc:
+            raise ValueError("wordpiece_windows: a size or pointer the rule refuses")
+        return ids, mask, tt, sm, offsets, winfo, dinfo[:docs], int(n_rows[0])
 
     # -- baseline JPEG (csrc/host/jpeg.cc) ---------------------------------------------
     @staticmethod

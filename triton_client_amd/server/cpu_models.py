@@ -20,7 +20,10 @@ Behaviour is pinned by the reference's example/test expectations:
 Not from the reference: ``qa_spans``, the answer-span step behind ``bert_large``
 (examples/python/bert_qa_client.py), here on the host twin of K27, and
 ``bert_tokenizer``, the step in front of it (examples/python/bert_qa_text_client.py),
-here on the host twin of K28.
+here on the host twin of K28; and their doc-stride forms for contexts longer
+than a row, ``bert_window_tokenizer`` and ``qa_doc_spans``
+(examples/python/bert_qa_doc_client.py), on the host twins of K28w, of K27 with
+a start mask and of K29.
 """
 
 import threading
@@ -545,7 +548,8 @@ class BertTokenizer(Model):
     [384] ``input_ids`` / ``attention_mask`` / ``token_type_ids``, INT32 [384, 2]
     ``offsets`` (the bytes of the context each context piece covers, (0, 0)
     elsewhere; ``utils.qa.answer_text`` turns a span back into text) and INT32 [1]
-    ``overflow`` (context pieces that did not fit; there is no doc stride) out.
+    ``overflow`` (context pieces that did not fit; ``bert_window_tokenizer`` is the
+    doc-stride form) out.
     The rule is csrc/kernels/wordpiece_core.h: BERT's uncased WordPiece, a row
     ``[CLS] question[:max_query_length] [SEP] context [SEP]``, ``token_type_ids``
     1 on the context pieces only, so that ``qa_spans`` never answers with the
@@ -666,9 +670,204 @@ class BertTokenizer(Model):
         return self.results(plan, *self.run_host(plan))
 
 
+class BertWindowTokenizer(BertTokenizer):
+    """``bert_window_tokenizer`` — ``bert_tokenizer`` for contexts longer than a
+    row: BYTES [D] ``question`` and ``context`` in (D documents, at most 128);
+    the doc-stride windows of all of them out, W rows in document order: INT32
+    [W, 384] ``input_ids`` / ``attention_mask`` / ``token_type_ids`` /
+    ``start_mask``, INT32 [W, 384, 2] ``offsets`` (bytes of the whole context),
+    INT32 [W, 4] ``window_info`` (document, first context piece, context pieces,
+    token of the first context piece) and INT32 [D, 4] ``doc_info`` (first row,
+    windows, context pieces, 0).  The rule is rule 8 of
+    csrc/kernels/wordpiece_core.h: window ``w`` starts at context piece ``w *
+    doc_stride``, the last one is the first that reaches the end, a context
+    without a piece still owns one row, and ``start_mask`` is 1 where the window
+    is the max-context window of the piece (run_squad's rule), which
+    ``qa_doc_spans`` needs to start each answer in one window only.  This class
+    runs the host twin of K28w (``HostCodec.wordpiece_windows``);
+    server/gpu_models.py BertWindowTokenizer runs the kernel.
+
+    Not batched (``max_batch_size`` 0): a request is a set of documents, and
+    its rows are a batch for ``bert_large``.  Custom request parameters:
+    ``max_query_length`` (int64, 1..381, default 64), ``doc_stride`` (int64,
+    1..381, default 128) and ``max_windows`` (int64, 1..128, default 128, per
+    document).  A document that is not valid UTF-8, longer than 65,536 bytes,
+    needs more than ``max_windows`` windows or does not fit the 128 rows of a
+    request fails the request, with a message that names the document."""
+
+    name = "bert_window_tokenizer"
+    max_batch_size = 0
+    MAX_DOCS = MAX_ROWS = 128
+    DOC_STRIDE, MAX_WINDOWS = 128, 128
+    inputs = (TensorSpec("question", "BYTES", [-1]), TensorSpec("context", "BYTES", [-1]))
+    outputs = (TensorSpec("input_ids", "INT32", [-1, 384]), TensorSpec("attention_mask", "INT32", [-1, 384]),
+               TensorSpec("token_type_ids", "INT32", [-1, 384]), TensorSpec("start_mask", "INT32", [-1, 384]),
+               TensorSpec("offsets", "INT32", [-1, 384, 2]), TensorSpec("window_info", "INT32", [-1, 4]),
+               TensorSpec("doc_info", "INT32", [-1, 4]))
+    dynamic_batching = None
+
+    @classmethod
+    def plan_one(cls, r):
+        """``(questions, contexts, max_query_length, doc_stride, max_windows)`` of
+        a request; ServerError for its parameters, shapes or lengths."""
+        from triton_client_amd.utils.wordpiece import MAX_TEXT_BYTES
+
+        mq = QaSpans._int_param(r, "max_query_length", cls.MAX_QUERY, 1, cls.SEQ - 3)
+        ds = QaSpans._int_param(r, "doc_stride", cls.DOC_STRIDE, 1, cls.SEQ - 3)
+        mw = QaSpans._int_param(r, "max_windows", cls.MAX_WINDOWS, 1, cls.MAX_ROWS)
+        texts = []
+        for nm in ("question", "context"):
+            col = [bytes(x) if not isinstance(x, str) else x.encode("utf-8")
+                   for x in np.asarray(r.input(nm).numpy(), dtype=object).reshape(-1)]
+            for d, x in enumerate(col):
+                if len(x) > MAX_TEXT_BYTES:
+                    raise ServerError("%s: document %d: %s too long" % (cls.name, d, nm))
+            texts.append(col)
+        if len(texts[0]) != len(texts[1]):
+            raise ServerError("%s: question and context must have one element per document" % cls.name)
+        if not 1 <= len(texts[0]) <= cls.MAX_DOCS:
+            raise ServerError("%s: a request holds 1 to %d documents, not %d" % (cls.name, cls.MAX_DOCS, len(texts[0])))
+        return texts[0], texts[1], mq, ds, mw
+
+    @classmethod
+    def doc_error(cls, doc_info, max_windows):
+        """The message of the first document whose status is not 0, or None."""
+        from triton_client_amd.utils.wordpiece import status_error
+
+        for d, (_, W, _, st) in enumerate(np.asarray(doc_info).tolist()):
+            if st == 0:
+                continue
+            if st & 0xFF == 6:
+                if W > max_windows:
+                    return "%s: document %d: context needs %d windows, max_windows %d" % (cls.name, d, W, max_windows)
+                return "%s: document %d: context needs %d windows, exceeds %d rows" % (cls.name, d, W, cls.MAX_ROWS)
+            return status_error(st, "%s: document %d" % (cls.name, d))
+        return None
+
+    def window_results(self, doc_info, n_rows, host, device=None):
+        """The outputs of a request: ``host`` = name -> array of the capacity's
+        rows; ``device`` = (tensor ``[4, rows, S]``, device id) hands the four id
+        tensors on as ``DeviceView`` with the tensor as ``owner``."""
+        from .types import DeviceView
+
+        outs = []
+        for k, nm in enumerate(("input_ids", "attention_mask", "token_type_ids", "start_mask")):
+            if device is None:
+                outs.append(self.out(nm, np.ascontiguousarray(host[nm][:n_rows])))
+            else:
+                t, dev_id = device
+                o = OutputTensor(nm, "INT32", [n_rows, self.SEQ],
+                                 DeviceView(t[k].data_ptr(), n_rows * self.SEQ * 4, dev_id))
+                o.owner = t
+                outs.append(o)
+        outs.append(self.out("offsets", np.ascontiguousarray(host["offsets"][:n_rows])))
+        outs.append(self.out("window_info", np.ascontiguousarray(host["window_info"][:n_rows])))
+        outs.append(self.out("doc_info", np.ascontiguousarray(doc_info).view(np.int32)))
+        return outs
+
+    def run_host_one(self, p):
+        qs, cs, mq, ds, mw = p
+        ids, mask, tt, sm, offsets, winfo, dinfo, n_rows = self._codec.wordpiece_windows(
+            qs, cs, self.vocab, mq, ds, mw, self.SEQ, self.MAX_ROWS)
+        err = self.doc_error(dinfo, mw)
+        if err:
+            return ServerError(err)
+        host = {"input_ids": ids, "attention_mask": mask, "token_type_ids": tt, "start_mask": sm, "offsets": offsets,
+                "window_info": winfo}
+        return self.window_results(dinfo, n_rows, host)
+
+    def execute(self, requests):
+        out = []
+        for r in requests:
+            try:
+                out.append(self.run_host_one(self.plan_one(r)))
+            except ServerError as e:
+                out.append(e)
+        return out
+
+
+class QaDocSpans(Model):
+    """``qa_doc_spans`` — the n best answers of each document from the logits of
+    its doc-stride windows, the step after ``bert_large`` behind
+    ``bert_window_tokenizer``: FP32 [W, 384] ``start_logits`` / ``end_logits``,
+    INT32 [W, 384] ``attention_mask`` / ``token_type_ids`` / ``start_mask``,
+    INT32 [W, 4] ``window_info`` and INT32 [D, 4] ``doc_info`` in; per document
+    INT32 ``spans`` [n_best, 2] (first and last token of row ``windows``), INT32
+    ``windows`` [n_best], FP32 ``scores`` [n_best] and FP32 ``null_score`` (the
+    lowest ``start[0] + end[0]`` of its windows) out.  The rule is
+    csrc/kernels/qa_span_math.h: per window the spans of ``qa_spans`` that start
+    where ``start_mask`` is 1, then per document the best of the union by score,
+    the lower document start piece, the shorter span; ranks past the candidates
+    hold ``(-1, -1)``, ``-1`` and ``-FLT_MAX``.  This class runs the host twins
+    of K27 with a start mask and of K29; server/gpu_models.py QaDocSpans runs
+    the kernels.
+
+    Not batched.  Custom request parameters: ``n_best`` (int64, 1..64, default
+    20) and ``max_answer_length`` (int64, 1..384, default 30)."""
+
+    name = "qa_doc_spans"
+    max_batch_size = 0
+    SEQ = 384
+    MAX_ROWS = MAX_DOCS = 128
+    inputs = (TensorSpec("start_logits", "FP32", [-1, 384]), TensorSpec("end_logits", "FP32", [-1, 384]),
+              TensorSpec("attention_mask", "INT32", [-1, 384]), TensorSpec("token_type_ids", "INT32", [-1, 384]),
+              TensorSpec("start_mask", "INT32", [-1, 384]), TensorSpec("window_info", "INT32", [-1, 4]),
+              TensorSpec("doc_info", "INT32", [-1, 4]))
+    outputs = (TensorSpec("spans", "INT32", [-1, -1, 2]), TensorSpec("windows", "INT32", [-1, -1]),
+               TensorSpec("scores", "FP32", [-1, -1]), TensorSpec("null_score", "FP32", [-1]))
+    ROW_INPUTS = (("start_logits", np.float32), ("end_logits", np.float32), ("attention_mask", np.int32),
+                  ("token_type_ids", np.int32), ("start_mask", np.int32))
+
+    @classmethod
+    def plan_one(cls, r):
+        """``(rows, documents, n_best, max_answer_length)`` of a request; ServerError
+        for its parameters or shapes."""
+        k = QaSpans._int_param(r, "n_best", QaSpans.N_BEST, 1, QaSpans.N_BEST_MAX)
+        ln = QaSpans._int_param(r, "max_answer_length", QaSpans.MAX_ANSWER, 1, QaSpans.MAX_ANSWER_MAX)
+        W = int(r.input("start_logits").shape[0])
+        D = int(r.input("doc_info").shape[0])
+        for nm, _ in cls.ROW_INPUTS:
+            if list(r.input(nm).shape) != [W, cls.SEQ]:
+                raise ServerError("%s: %s must be [%d, %d]" % (cls.name, nm, W, cls.SEQ))
+        if list(r.input("window_info").shape) != [W, 4] or list(r.input("doc_info").shape) != [D, 4]:
+            raise ServerError("%s: window_info must be [%d, 4] and doc_info [D, 4]" % (cls.name, W))
+        if not (1 <= W <= cls.MAX_ROWS and 1 <= D <= cls.MAX_DOCS):
+            raise ServerError("%s: a request holds 1 to %d rows and documents" % (cls.name, cls.MAX_ROWS))
+        return W, D, k, ln
+
+    def doc_results(self, k, spans, windows, scores, null):
+        return [self.out("spans", np.ascontiguousarray(spans[:, :k])),
+                self.out("windows", np.ascontiguousarray(windows[:, :k])),
+                self.out("scores", np.ascontiguousarray(scores[:, :k])), self.out("null_score", np.ascontiguousarray(null))]
+
+    def load(self):
+        from triton_client_amd.ops import host_codec
+
+        self._codec = host_codec.load()
+
+    def run_host_one(self, r, p):
+        W, D, k, ln = p
+        cols = [np.asarray(r.input(nm).numpy(), dtype=dt).reshape(W, self.SEQ) for nm, dt in self.ROW_INPUTS]
+        winfo = np.asarray(r.input("window_info").numpy(), dtype=np.int32).reshape(W, 4)
+        dinfo = np.asarray(r.input("doc_info").numpy(), dtype=np.int32).reshape(D, 4).view(np.uint32)
+        lists = self._codec.qa_spans_masked(*cols, np.full(W, k, np.int32), np.full(W, ln, np.int32), k)
+        return self.doc_results(k, *self._codec.qa_merge(*lists, winfo, dinfo, np.full(D, k, np.int32), k))
+
+    def execute(self, requests):
+        out = []
+        for r in requests:
+            try:
+                out.append(self.run_host_one(r, self.plan_one(r)))
+            except (ServerError, ValueError) as e:
+                out.append(e if isinstance(e, ServerError) else ServerError("%s: %s" % (self.name, e)))
+        return out
+
+
 CPU_MODELS = [
     BertTokenizer,
     QaSpans,
+    BertWindowTokenizer,
+    QaDocSpans,
     FrontendSink,
     BertSink,
     SimpleAddSub,

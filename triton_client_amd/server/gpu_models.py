@@ -31,6 +31,7 @@ import numpy as np
 
 from triton_client_amd.utils import jpeg_stage, roctx
 
+from . import cpu_models as _cpu
 from .model_base import Model, TensorSpec
 from .types import DeviceView, OutputTensor, ServerError
 
@@ -1478,7 +1479,8 @@ class BertQaTextEnsemble(Model):
     ensemble's custom request parameters to the steps that read them.  The ids
     and the logits are outputs too; a request that does not ask for them does
     not pay for their copy.  A context longer than the row is cut
-    (``overflow``): there is no doc stride."""
+    (``overflow``); ``bert_qa_doc_ensemble`` answers over the whole of it with
+    doc-stride windows."""
 
     name = "bert_qa_text_ensemble"
     platform = "ensemble"
@@ -1505,8 +1507,347 @@ class BertQaTextEnsemble(Model):
         raise ServerError("ensemble models are scheduled by the server")
 
 
+class BertWindowTokenizer(Model):
+    """``bert_window_tokenizer`` on the GPU: the same I/O contract, request
+    parameters, vocabulary and rule as the CPU model of that name
+    (server/cpu_models.py BertWindowTokenizer), which it replaces on a ``--gpu``
+    server and whose checks and messages it uses.
+
+    Per request, the host copies the documents' strings end to end into the
+    slot's pinned staging area behind the per-document table and parameters, one
+    upload takes them to the device, and K28w ``wordpiece_windows``
+    (csrc/kernels/wordpiece.hip) tokenizes and lays out the windows of all
+    documents on the slot's stream against the vocabulary image uploaded at
+    load.  ``doc_info``, the row count and ``window_info`` come back first (4
+    KB): they say whether a document was refused and how many rows there are;
+    then exactly those rows of ``offsets``.  For an ensemble step
+    (``accepts_device_outputs``) the four id tensors are written into a tensor
+    of the request's own and handed on as ``DeviceView`` with ``owner`` set;
+    otherwise their rows are downloaded too.  The texts of a request are limited
+    to ``TEXT_BUDGET`` bytes.  ``TCAMD_DEVICE_TOKENIZER=0`` (read at load) runs
+    the host twin instead."""
+
+    name = "bert_window_tokenizer"
+    max_batch_size = 0
+    SEQ = 384
+    MAX_ROWS = 128
+    TEXT_BUDGET = 1 << 20
+    inputs, outputs = _cpu.BertWindowTokenizer.inputs, _cpu.BertWindowTokenizer.outputs
+    instance_kind = "KIND_GPU"
+    instance_count = 2
+    gpus = (0,)
+
+    def __init__(self, version=1, device_id=0, **kw):
+        super().__init__(version, **kw)
+        self.device_id = int(kw.get("device", device_id))
+        self._slots = []
+        self._free = []
+        self._cv = threading.Condition()
+        self._host = None
+
+    def load(self):
+        from .cpu_models import BertWindowTokenizer as HostModel
+
+        self._host = HostModel(self.version)
+        self._host.load()
+        self.vocab = self._host.vocab
+        self.device_path = os.environ.get("TCAMD_DEVICE_TOKENIZER", "1") != "0"
+        if not self.device_path:
+            return
+        import torch
+
+        from triton_client_amd.ops import hip
+
+        if not torch.cuda.is_available():
+            raise ServerError("bert_window_tokenizer (GPU) requires a GPU")
+        hip.lib()  # fail loudly if the native kernels are missing
+        self.torch = torch
+        dev = torch.device("cuda", self.device_id)
+        n, S = self.MAX_ROWS, self.SEQ
+        self.head_bytes = n * 16 + 3 * n * 4  # the table, then max_query_length, doc_stride, max_windows per document
+        self.in_bytes = self.head_bytes + self.TEXT_BUDGET
+        self.ws_bytes = hip.wordpiece_windows_workspace(n, self.TEXT_BUDGET)
+        # doc_info, n_rows (16 bytes), window_info; offsets; ids, mask, type ids, start mask
+        self.o_nrows, self.o_winfo, self.o_offsets = n * 16, n * 16 + 16, 2 * n * 16 + 16
+        self.o_ids = self.o_offsets + n * S * 8
+        self.out_bytes = self.o_ids + 4 * n * S * 4
+        self.vocab_dev = torch.from_numpy(self.vocab.image.view(np.int32).copy()).to(dev)
+        for _ in range(max(1, self.instance_count)):
+            self._slots.append({
+                "stream": torch.cuda.Stream(device=dev),
+                "in_host": hip.host_alloc(self.in_bytes),
+                "out_host": hip.host_alloc(self.out_bytes),
+                "in_dev": torch.zeros(self.in_bytes, device=dev, dtype=torch.uint8),
+                "out_dev": torch.zeros(self.out_bytes, device=dev, dtype=torch.uint8),
+                "ws": torch.zeros(self.ws_bytes, device=dev, dtype=torch.uint8),
+            })
+        self._free = list(range(len(self._slots)))
+
+    unload = QaSpans.unload
+    _acquire = QaSpans._acquire
+    _release = QaSpans._release
+
+    def execute(self, requests):
+        from triton_client_amd.ops import hip
+
+        out = []
+        for r in requests:
+            try:
+                p = self._host.plan_one(r)
+                if not self.device_path:
+                    out.append(self._host.run_host_one(p))
+                    continue
+                i = self._acquire()
+                try:
+                    out.append(self._execute(self._slots[i], p, bool(getattr(r, "accepts_device_outputs", False))))
+                finally:
+                    self._release(i)
+            except ServerError as e:
+                out.append(e)
+            except hip.HipError as e:
+                out.append(ServerError("%s: %s" % (self.name, e)))
+        return out
+
+    def _execute(self, slot, p, on_device):
+        import ctypes
+
+        from triton_client_amd.ops import hip
+
+        qs, cs, mq, ds, mw = p
+        torch, S, n = self.torch, self.SEQ, self.MAX_ROWS
+        docs = len(qs)
+        total = sum(len(q) + len(c) for q, c in zip(qs, cs))
+        if total > self.TEXT_BUDGET:
+            raise ServerError("%s: the texts of a request have %d bytes, at most %d" % (self.name, total, self.TEXT_BUDGET))
+        sh = slot["stream"].cuda_stream
+        in_host, in_dev, out_host = slot["in_host"], slot["in_dev"].data_ptr(), slot["out_host"]
+        out_dev = slot["out_dev"].data_ptr()
+        table = np.ctypeslib.as_array((ctypes.c_uint32 * (n * 4)).from_address(in_host)).reshape(n, 4)
+        pars = np.ctypeslib.as_array((ctypes.c_int32 * (3 * n)).from_address(in_host + n * 16)).reshape(3, n)
+        at = 0
+        for d in range(docs):
+            for f, t in enumerate((qs[d], cs[d])):
+                table[d, 2 * f], table[d, 2 * f + 1] = at, len(t)
+                ctypes.memmove(in_host + self.head_bytes + at, t, len(t))
+                at += len(t)
+        pars[0, :docs], pars[1, :docs], pars[2, :docs] = mq, ds, mw
+        res = None
+        if on_device:
+            with torch.cuda.stream(slot["stream"]):
+                res = torch.empty((4, n, S), device=slot["stream"].device, dtype=torch.int32)
+            id_ptrs = [res[k].data_ptr() for k in range(4)]
+        else:
+            id_ptrs = [out_dev + self.o_ids + k * n * S * 4 for k in range(4)]
+        hip.memcpy_async(in_dev, in_host, self.head_bytes + at, sh)
+        hip.wordpiece_windows(in_dev + self.head_bytes, at, in_dev, in_dev + n * 16, in_dev + n * 20, in_dev + n * 24,
+                              docs, S, self.vocab_dev.data_ptr(), self.vocab.image.size, slot["ws"].data_ptr(),
+                              self.ws_bytes, n, id_ptrs[0], id_ptrs[1], id_ptrs[2], id_ptrs[3],
+                              out_dev + self.o_offsets, out_dev + self.o_winfo, out_dev, out_dev + self.o_nrows,
+                              stream=sh)
+        hip.memcpy_async(out_host, out_dev, self.o_offsets, sh)
+        hip.stream_synchronize(sh)
+        head = np.ctypeslib.as_array((ctypes.c_uint8 * self.o_offsets).from_address(out_host)).copy()
+        dinfo = head[:docs * 16].view(np.uint32).reshape(docs, 4)
+        n_rows = int(head[self.o_nrows:self.o_nrows + 4].view(np.int32)[0])
+        err = self._host.doc_error(dinfo, mw)
+        if err:
+            raise ServerError(err)
+        host = {"window_info": head[self.o_winfo:self.o_winfo + n_rows * 16].view(np.int32).reshape(n_rows, 4)}
+        hip.memcpy_async(out_host + self.o_offsets, out_dev + self.o_offsets, n_rows * S * 8, sh)
+        if not on_device:
+            for k in range(4):
+                o = self.o_ids + k * n * S * 4
+                hip.memcpy_async(out_host + o, out_dev + o, n_rows * S * 4, sh)
+        hip.stream_synchronize(sh)
+
+        def rows_at(o, width):
+            raw = np.ctypeslib.as_array((ctypes.c_uint8 * (n_rows * S * width)).from_address(out_host + o)).copy()
+            return raw.view(np.int32)
+
+        host["offsets"] = rows_at(self.o_offsets, 8).reshape(n_rows, S, 2)
+        if on_device:
+            return self._host.window_results(dinfo, n_rows, host, device=(res, self.device_id))
+        for k, nm in enumerate(("input_ids", "attention_mask", "token_type_ids", "start_mask")):
+            host[nm] = rows_at(self.o_ids + k * n * S * 4, 4).reshape(n_rows, S)
+        return self._host.window_results(dinfo, n_rows, host)
+
+
+class QaDocSpans(Model):
+    """``qa_doc_spans`` on the GPU: the same I/O contract, request parameters
+    and rule as the CPU model of that name (server/cpu_models.py QaDocSpans),
+    which it replaces on a ``--gpu`` server and whose checks it uses.
+
+    Per request, an input that arrives as ``DeviceView`` (the logits
+    ``bert_large`` and the id tensors ``bert_window_tokenizer`` left on the
+    device for the ensemble) is read in place, a host input goes up through the
+    slot's pinned staging buffer; K27 with the start mask
+    (``qa_spans_masked``) leaves every window's list in the slot's scratch and
+    K29 ``qa_merge`` (csrc/kernels/qa_merge.hip) merges them per document, back
+    to back on the slot's stream; the document-level result alone comes back, in
+    one copy of ``D * (n_best * 16 + 4)`` bytes.  ``TCAMD_DEVICE_QA_SPANS=0``
+    (read at load) runs the host twins instead."""
+
+    name = "qa_doc_spans"
+    max_batch_size = 0
+    SEQ = 384
+    MAX_ROWS = 128
+    inputs, outputs = _cpu.QaDocSpans.inputs, _cpu.QaDocSpans.outputs
+    instance_kind = "KIND_GPU"
+    instance_count = 2
+    gpus = (0,)
+
+    def __init__(self, version=1, device_id=0, **kw):
+        super().__init__(version, **kw)
+        self.device_id = int(kw.get("device", device_id))
+        self._slots = []
+        self._free = []
+        self._cv = threading.Condition()
+        self._host = None
+
+    def load(self):
+        from .cpu_models import QaDocSpans as HostModel
+
+        self._host = HostModel(self.version)
+        self._host.load()
+        self.device_path = os.environ.get("TCAMD_DEVICE_QA_SPANS", "1") != "0"
+        if not self.device_path:
+            return
+        import torch
+
+        from triton_client_amd.ops import hip
+
+        if not torch.cuda.is_available():
+            raise ServerError("qa_doc_spans (GPU) requires a GPU")
+        hip.lib()  # fail loudly if the native kernels are missing
+        self.torch = torch
+        dev = torch.device("cuda", self.device_id)
+        n, row, kmax = self.MAX_ROWS, self.SEQ * 4, hip.QA_SPANS_KMAX
+        # the five row tensors, window_info, doc_info, then k_row, len_row and k_doc
+        self.o_winfo = 5 * n * row
+        self.o_dinfo, self.o_par = self.o_winfo + n * 16, self.o_winfo + 2 * n * 16
+        self.in_bytes = self.o_par + 3 * n * 4
+        self.list_bytes = n * (kmax * 12 + 4)  # K27's lists: spans, scores, null
+        self.out_bytes = n * (kmax * 16 + 4)   # K29's: spans, windows, scores, null
+        for _ in range(max(1, self.instance_count)):
+            self._slots.append({
+                "stream": torch.cuda.Stream(device=dev),
+                "in_host": hip.host_alloc(self.in_bytes),
+                "out_host": hip.host_alloc(self.out_bytes),
+                "in_dev": torch.zeros(self.in_bytes, device=dev, dtype=torch.uint8),
+                "lists": torch.zeros(self.list_bytes, device=dev, dtype=torch.uint8),
+                "out_dev": torch.zeros(self.out_bytes, device=dev, dtype=torch.uint8),
+            })
+        self._free = list(range(len(self._slots)))
+
+    unload = QaSpans.unload
+    _acquire = QaSpans._acquire
+    _release = QaSpans._release
+
+    def execute(self, requests):
+        from triton_client_amd.ops import hip
+
+        out = []
+        for r in requests:
+            try:
+                p = self._host.plan_one(r)
+                if not self.device_path:
+                    out.append(self._host.run_host_one(r, p))
+                    continue
+                i = self._acquire()
+                try:
+                    out.append(self._host.doc_results(p[2], *self._execute(self._slots[i], r, p)))
+                finally:
+                    self._release(i)
+            except ServerError as e:
+                out.append(e)
+            except (ValueError, hip.HipError) as e:
+                out.append(ServerError("%s: %s" % (self.name, e)))
+        return out
+
+    def _execute(self, slot, r, p):
+        import ctypes
+
+        from triton_client_amd.ops import hip
+
+        W, D, k, ln = p
+        n, row = self.MAX_ROWS, self.SEQ * 4
+        sh = slot["stream"].cuda_stream
+        in_host, in_dev = slot["in_host"], slot["in_dev"].data_ptr()
+        pars = np.ctypeslib.as_array((ctypes.c_int32 * (3 * n)).from_address(in_host + self.o_par)).reshape(3, n)
+        pars[0, :W], pars[1, :W], pars[2, :D] = k, ln, k
+        hip.memcpy_async(in_dev + self.o_par, in_host + self.o_par, 3 * n * 4, sh)
+        at = []
+        specs = [(nm, dt, W * row, c * n * row) for c, (nm, dt) in enumerate(self._host.ROW_INPUTS)]
+        specs += [("window_info", np.int32, W * 16, self.o_winfo), ("doc_info", np.int32, D * 16, self.o_dinfo)]
+        for nm, dt, nbytes, base in specs:
+            t = r.input(nm)
+            if isinstance(t.data, DeviceView):
+                if t.data.nbytes < nbytes:
+                    raise ServerError("input region too small for %s" % nm)
+                at.append(t.data.ptr)
+                continue
+            stage = np.ctypeslib.as_array((ctypes.c_uint8 * nbytes).from_address(in_host + base)).view(dt)
+            stage[:] = np.asarray(t.data, dtype=dt).reshape(-1)
+            hip.memcpy_async(in_dev + base, in_host + base, nbytes, sh)
+            at.append(in_dev + base)
+        lists, out_dev = slot["lists"].data_ptr(), slot["out_dev"].data_ptr()
+        l_scores, l_null = W * k * 8, W * k * 12
+        hip.qa_spans_masked(at[0], at[1], row, at[2], at[3], at[4], row, W, self.SEQ, in_dev + self.o_par,
+                            in_dev + self.o_par + n * 4, k, lists, lists + l_scores, lists + l_null, stream=sh)
+        o_windows, o_scores, o_null = D * k * 8, D * k * 12, D * k * 16
+        hip.qa_merge(lists, lists + l_scores, lists + l_null, W, at[5], at[6], D, in_dev + self.o_par + 2 * n * 4, k,
+                     out_dev, out_dev + o_windows, out_dev + o_scores, out_dev + o_null, stream=sh)
+        nbytes = D * (k * 16 + 4)
+        hip.memcpy_async(slot["out_host"], out_dev, nbytes, sh)
+        hip.stream_synchronize(sh)
+        raw = np.ctypeslib.as_array((ctypes.c_uint8 * nbytes).from_address(slot["out_host"])).copy()
+        return (raw[:o_windows].view(np.int32).reshape(D, k, 2), raw[o_windows:o_scores].view(np.int32).reshape(D, k),
+                raw[o_scores:o_null].view(np.float32).reshape(D, k), raw[o_null:].view(np.float32))
+
+
+class BertQaDocEnsemble(Model):
+    """Ensemble: UTF-8 documents -> ``bert_window_tokenizer`` -> ``bert_large``
+    -> ``qa_doc_spans``: question answering over contexts longer than the
+    384-token row, by overlapping doc-stride windows, the max-context rule and a
+    merge of the windows' answers per document.  The W rows of a request's
+    documents are one ``bert_large`` batch; ids, masks and logits stay on the
+    device between the steps.  ``max_query_length``, ``doc_stride``,
+    ``max_windows``, ``n_best`` and ``max_answer_length`` travel as the
+    ensemble's custom request parameters to the steps that read them.
+    ``offsets`` (``utils.qa.answer_text_doc`` turns a span and its window back
+    into the context's bytes), ``window_info``, ``doc_info``, the ids and the
+    logits are outputs too; a request that does not ask for them does not pay
+    for their copy."""
+
+    name = "bert_qa_doc_ensemble"
+    platform = "ensemble"
+    backend = ""
+    max_batch_size = 0
+    inputs = BertWindowTokenizer.inputs
+    outputs = (QaDocSpans.outputs + BertWindowTokenizer.outputs[4:] + BertWindowTokenizer.outputs[:4] +
+               (TensorSpec("start_logits", "FP32", [-1, 384]), TensorSpec("end_logits", "FP32", [-1, 384])))
+    ensemble_steps = [
+        ("bert_window_tokenizer", {"question": "question", "context": "context"},
+         {"input_ids": "input_ids", "attention_mask": "attention_mask", "token_type_ids": "token_type_ids",
+          "start_mask": "start_mask", "offsets": "offsets", "window_info": "window_info", "doc_info": "doc_info"}),
+        ("bert_large", {"input_ids": "input_ids", "attention_mask": "attention_mask",
+                        "token_type_ids": "token_type_ids"},
+         {"start_logits": "start_logits", "end_logits": "end_logits"}),
+        ("qa_doc_spans", {"start_logits": "start_logits", "end_logits": "end_logits",
+                          "attention_mask": "attention_mask", "token_type_ids": "token_type_ids",
+                          "start_mask": "start_mask", "window_info": "window_info", "doc_info": "doc_info"},
+         {"spans": "spans", "windows": "windows", "scores": "scores", "null_score": "null_score"}),
+    ]
+
+    def load(self):
+        pass
+
+    def execute(self, requests):  # pragma: no cover - the server runs ensembles step by step
+        raise ServerError("ensemble models are scheduled by the server")
+
+
 GPU_MODELS = [DensenetOnnx, PreprocessInception, PreprocessInceptionEnsemble, BertLarge, QaSpans, BertQaEnsemble,
-              BertTokenizer, BertQaTextEnsemble]
+              BertTokenizer, BertQaTextEnsemble, BertWindowTokenizer, QaDocSpans, BertQaDocEnsemble]
 # loaded only when --models names them: bert_large_fp32 adds ~2 GB of bf16x3
 # weights and 28 captured HIP graphs per instance (round-5 advisor finding)
 OPT_IN_GPU_MODELS = [BertLargeFP32]

@@ -102,11 +102,12 @@ KNOBS = [
          "filters and converts the samples on the device; 0 = the host decodes it and the pixels go up",
          "tests/test_png_gpu.py::test_the_png_knob_changes_the_route_and_not_one_bit_of_the_rows"),
     Knob("TCAMD_DEVICE_QA_SPANS", "python", 1, "server/gpu_models.py",
-         "GPU qa_spans: K27 qa_spans picks the answer spans on the device; 0 = the host twin of the same rule",
+         "GPU qa_spans and qa_doc_spans: K27 qa_spans (and K29 qa_merge) pick the answer spans on the device; 0 = the "
+         "host twins of the same rules",
          "tests/test_qa_spans_gpu.py::test_the_knob_changes_the_route_and_not_one_bit_of_the_spans"),
     Knob("TCAMD_DEVICE_TOKENIZER", "python", 1, "server/gpu_models.py",
-         "GPU bert_tokenizer: K28 wordpiece_tokenize turns the texts into rows on the device; 0 = the host twin of "
-         "the same rule",
+         "GPU bert_tokenizer and bert_window_tokenizer: K28 wordpiece_tokenize / K28w wordpiece_windows turn the texts "
+         "into rows on the device; 0 = the host twin of the same rule",
          "tests/test_wordpiece_gpu.py::test_the_knob_changes_the_route_and_not_one_bit_of_the_rows"),
     Knob("TCAMD_BERT_VOCAB", "python", "", "utils/wordpiece.py",
          "bert_tokenizer: the vocab.txt to load (the server's --bert-vocab sets it); unset = the demonstration "

@@ -22,17 +22,22 @@ Host (non-shm) inputs are staged through pinned memory; host outputs come back
 with one D2H of the whole batch.  Each model instance owns a torch stream, its
 graphs (one per batch bucket) and static buffers, so ``instance_count``
 batches pipeline on separate HIP streams.
+
+The other models here follow the same pattern; the slot pool, the base classes
+and the staging helpers they share are in server/device_slots.py.
 """
 
+import ctypes
 import os
-import threading
 
 import numpy as np
 
 from triton_client_amd.utils import jpeg_stage, roctx
 
 from . import cpu_models as _cpu
-from .model_base import Model, TensorSpec
+from .device_slots import (DeviceModel, Ensemble, download, pinned_view, place_input, plan_errors, stage_input,
+                           stage_texts)
+from .model_base import TensorSpec
 from .types import DeviceView, OutputTensor, ServerError
 
 # HIP-graph batch buckets: powers of two up to 16, then every 8 rows to 128 and
@@ -43,7 +48,7 @@ from .types import DeviceView, OutputTensor, ServerError
 BUCKETS = (1, 2, 4, 8, 12, 16, 20) + tuple(range(24, 129, 8)) + tuple(range(144, 257, 16))
 
 
-class DensenetOnnx(Model):
+class DensenetOnnx(DeviceModel):
     name = "densenet_onnx"
     platform = "onnxruntime_onnx"
     backend = "onnxruntime"
@@ -65,14 +70,14 @@ class DensenetOnnx(Model):
 
     def __init__(self, version=1, device_id=0, buckets=BUCKETS, use_graphs=True, engine="fp32", max_batch_size=0,
                  **kw):
-        super().__init__(version, **kw)
+        super().__init__(version, device_id, **kw)
         if engine not in self.ENGINES:
             raise ServerError("unknown densenet engine %r" % engine)
         self.engine = engine
-        self.device_id = int(kw.get("device", device_id))
         if max_batch_size:
-            # option max_batch_size: the HIP-graph buckets up to it (BUCKETS).  The fused engine's device throughput keeps growing with the
-            # rows per forward: on MI355X (tools/engine_streams_bench.py) ~64k
+            # option max_batch_size: the HIP-graph buckets up to it (BUCKETS).
+            # The fused engine's device throughput keeps growing with the rows
+            # per forward: on MI355X (tools/engine_streams_bench.py) ~64k
             # img/s with 128-row forwards on 3-4 streams, ~70k with 256-row
             # forwards on 2 streams.
             if int(max_batch_size) not in buckets:
@@ -80,23 +85,13 @@ class DensenetOnnx(Model):
             self.max_batch_size = int(max_batch_size)
         self.buckets = tuple(b for b in buckets if b <= self.max_batch_size)
         self.use_graphs = use_graphs
-        self._slots = []
-        self._free = []
-        self._cv = threading.Condition()
 
     # -- load ----------------------------------------------------------------------
     def load(self):
-        import torch
-
         from triton_client_amd.models import densenet
-        from triton_client_amd.ops import hip
 
-        if not torch.cuda.is_available():
-            raise ServerError("densenet_onnx requires a GPU")
-        hip.lib()  # fail loudly if the native kernels are missing
+        torch, _, dev = self._gpu("densenet_onnx requires a GPU")
         torch.cuda.set_device(self.device_id)
-        self.torch = torch
-        dev = torch.device("cuda", self.device_id)
         if self.engine == "fp32":
             from triton_client_amd.models import densenet_fp32
 
@@ -111,8 +106,7 @@ class DensenetOnnx(Model):
         # the instances' streams run concurrently: engines route small batches for that
         self.model.concurrent_streams = max(1, self.instance_count)
         for _ in range(max(1, self.instance_count)):
-            self._slots.append(self._make_slot(dev))
-        self._free = list(range(len(self._slots)))
+            self._slots.add(self._make_slot(dev))
         self._pgx = None
         if self.engine != "torch" and self.use_graphs and os.environ.get("TCAMD_NATIVE_EXEC", "1") != "0":
             self._pgx = self._make_executor()
@@ -148,10 +142,8 @@ class DensenetOnnx(Model):
 
     def _make_slot(self, dev):
         torch = self.torch
-        from triton_client_amd.ops import hip
-
         net = self.model
-        if self.engine != "torch" and self._slots:
+        if self.engine != "torch" and len(self._slots):
             net = self.model.with_workspace()  # own activation buffers per concurrent stream
         slot = {"stream": torch.cuda.Stream(device=dev), "graphs": {}, "net": net,
                 "ev": [torch.cuda.Event(enable_timing=True) for _ in range(4)]}
@@ -159,16 +151,14 @@ class DensenetOnnx(Model):
         img_bytes = self.C * self.H * self.W * 4
         fused = self.engine != "torch"  # pointer-table engines (fp32 / bf16 fused kernels)
         slot["out"] = torch.zeros(maxb, self.OUT, device=dev, dtype=torch.float32)
-        slot["stage_host"] = hip.host_alloc(maxb * img_bytes)
+        self._pinned(slot, "stage_host", maxb * img_bytes)
         slot["stage_dev"] = torch.zeros(maxb * self.C * self.H * self.W, device=dev, dtype=torch.float32)
-        slot["out_host"] = hip.host_alloc(maxb * self.OUT * 4)
+        self._pinned(slot, "out_host", maxb * self.OUT * 4)
         if fused:
             # padded rows of a bucket read (finite) staging images, never a stale request region
             pad = np.arange(maxb, dtype=np.int64) * img_bytes + slot["stage_dev"].data_ptr()
             slot["pad_ptrs"] = pad
-            slot["ptrs_host"] = hip.host_alloc(maxb * 8)
-            slot["ptrs_tbl"] = np.ctypeslib.as_array((np.ctypeslib.ctypes.c_int64 * maxb).from_address(
-                slot["ptrs_host"]))
+            slot["ptrs_tbl"] = pinned_view(self._pinned(slot, "ptrs_host", maxb * 8), np.int64, maxb)
             net.ptrs.copy_(torch.from_numpy(pad))
 
             def run(b):
@@ -192,33 +182,12 @@ class DensenetOnnx(Model):
         return slot
 
     def unload(self):
-        from triton_client_amd.ops import hip
-
         if getattr(self, "_pgx", None) is not None:
             self._pgx.close()
             self._pgx = None
-        for s in self._slots:
-            try:
-                hip.host_free(s["stage_host"])
-                hip.host_free(s["out_host"])
-                if "ptrs_host" in s:
-                    hip.host_free(s["ptrs_host"])
-            except Exception:
-                pass
-        self._slots = []
+        super().unload()
 
     # -- execute ----------------------------------------------------------------------
-    def _acquire(self):
-        with self._cv:
-            while not self._free:
-                self._cv.wait()
-            return self._free.pop()
-
-    def _release(self, i):
-        with self._cv:
-            self._free.append(i)
-            self._cv.notify()
-
     def forward_device(self, slot, srcs, rows):
         """Assemble ``rows`` images from device pointers and run the model."""
         with roctx.range("densenet_onnx.forward rows=%d" % rows):
@@ -256,9 +225,6 @@ class DensenetOnnx(Model):
         return bucket
 
     def execute(self, requests):
-        torch = self.torch
-        from triton_client_amd.ops import hip
-
         img_bytes = self.C * self.H * self.W * 4
         out_row = self.OUT * 4
         rows = 0
@@ -272,85 +238,81 @@ class DensenetOnnx(Model):
             return [ServerError("batch of %d rows exceeds the largest bucket" % rows)] * len(requests)
         if getattr(self, "_pgx", None) is not None:
             return self._execute_pgx(plan, rows, img_bytes, out_row)
-        i = self._acquire()
-        slot = self._slots[i]
         try:
-            stream = slot["stream"]
-            sh = stream.cuda_stream
-            srcs = []
-            host_rows = 0
-            for r, first, n in plan:
-                t = r.input("data_0")
-                if isinstance(t.data, DeviceView):
-                    if t.data.nbytes < n * img_bytes:
-                        raise ServerError("input region too small for data_0")
-                    srcs += [t.data.ptr + k * img_bytes for k in range(n)]
-                else:
-                    a = np.ascontiguousarray(t.data, dtype=np.float32)
-                    dst = slot["stage_host"] + host_rows * img_bytes
-                    np.copyto(np.ctypeslib.as_array((np.ctypeslib.ctypes.c_float * a.size).from_address(dst)),
-                              a.reshape(-1))
-                    srcs += [slot["stage_dev"].data_ptr() + (host_rows + k) * img_bytes for k in range(n)]
-                    host_rows += n
-            if host_rows:
-                hip.memcpy_async(slot["stage_dev"].data_ptr(), slot["stage_host"], host_rows * img_bytes, sh)
-            self.forward_device(slot, srcs, rows)
-            # outputs: device-shm targets get a K7 scatter, the rest one D2H
-            out_base = slot["out"].data_ptr()
-            c_src, c_dst, c_n = [], [], []
-            need_host = False
-            results = []
-            for r, first, n in plan:
-                ro = next((o for o in r.outputs if o.name == "fc6_1"), None)
-                target = None
-                if ro is not None and ro.shm is not None and ro.class_count == 0:
-                    target = self._server_target(r, ro)
-                if isinstance(target, DeviceView):
-                    if target.nbytes < n * out_row:
-                        raise ServerError(
-                            "shared memory size specified with the request for output 'fc6_1' "
-                            "(%d bytes) should be at least %d bytes" % (target.nbytes, n * out_row)
-                        )
-                    c_src.append(out_base + first * out_row)
-                    c_dst.append(target.ptr)
-                    c_n.append(n * out_row)
-                    results.append(("shm", ro))
-                else:
-                    need_host = True
-                    results.append(("host", None))
-            if c_src:
-                hip.batched_copy(c_src, c_dst, c_n, sh)
-            if need_host:
-                hip.memcpy_async(slot["out_host"], out_base, rows * out_row, sh)
-            slot["ev"][3].record(stream)
-            stream.synchronize()
-            if self._batch_stats is not None:
-                ev = slot["ev"]
-                ms_in, ms_inf, ms_out = (ev[0].elapsed_time(ev[1]), ev[1].elapsed_time(ev[2]),
-                                         ev[2].elapsed_time(ev[3]))
-                self._batch_stats(rows, len(requests), int(ms_in * 1e6), int(ms_inf * 1e6), int(ms_out * 1e6))
-            host_all = None
-            if need_host:
-                host_all = np.ctypeslib.as_array(
-                    (np.ctypeslib.ctypes.c_float * (rows * self.OUT)).from_address(slot["out_host"])
-                ).reshape(rows, self.OUT).copy()
-            out = []
-            for (r, first, n), (kind, ro) in zip(plan, results):
-                if kind == "shm":
-                    o = OutputTensor("fc6_1", "FP32", [n, self.OUT], None, shm=ro.shm)
-                else:
-                    o = OutputTensor("fc6_1", "FP32", [n, self.OUT], host_all[first : first + n])
-                out.append([o])
-            return out
+            with self._slots.slot() as (_, slot):
+                return self._execute(slot, requests, plan, rows, img_bytes, out_row)
         except ServerError as e:
             return [e] * len(requests)
-        finally:
-            self._release(i)
+
+    def _execute(self, slot, requests, plan, rows, img_bytes, out_row):
+        from triton_client_amd.ops import hip
+
+        stream = slot["stream"]
+        sh = stream.cuda_stream
+        srcs = []
+        host_rows = 0
+        for r, first, n in plan:
+            t = r.input("data_0")
+            if isinstance(t.data, DeviceView):
+                if t.data.nbytes < n * img_bytes:
+                    raise ServerError("input region too small for data_0")
+                srcs += [t.data.ptr + k * img_bytes for k in range(n)]
+            else:
+                a = np.ascontiguousarray(t.data, dtype=np.float32)
+                np.copyto(pinned_view(slot["stage_host"] + host_rows * img_bytes, np.float32, a.size), a.reshape(-1))
+                srcs += [slot["stage_dev"].data_ptr() + (host_rows + k) * img_bytes for k in range(n)]
+                host_rows += n
+        if host_rows:
+            hip.memcpy_async(slot["stage_dev"].data_ptr(), slot["stage_host"], host_rows * img_bytes, sh)
+        self.forward_device(slot, srcs, rows)
+        # outputs: device-shm targets get a K7 scatter, the rest one D2H
+        out_base = slot["out"].data_ptr()
+        c_src, c_dst, c_n = [], [], []
+        need_host = False
+        results = []
+        for r, first, n in plan:
+            ro = next((o for o in r.outputs if o.name == "fc6_1"), None)
+            target = None
+            if ro is not None and ro.shm is not None and ro.class_count == 0:
+                target = self._server_target(r, ro)
+            if isinstance(target, DeviceView):
+                if target.nbytes < n * out_row:
+                    raise ServerError(
+                        "shared memory size specified with the request for output 'fc6_1' "
+                        "(%d bytes) should be at least %d bytes" % (target.nbytes, n * out_row)
+                    )
+                c_src.append(out_base + first * out_row)
+                c_dst.append(target.ptr)
+                c_n.append(n * out_row)
+                results.append(("shm", ro))
+            else:
+                need_host = True
+                results.append(("host", None))
+        if c_src:
+            hip.batched_copy(c_src, c_dst, c_n, sh)
+        if need_host:
+            hip.memcpy_async(slot["out_host"], out_base, rows * out_row, sh)
+        slot["ev"][3].record(stream)
+        stream.synchronize()
+        if self._batch_stats is not None:
+            ev = slot["ev"]
+            ms_in, ms_inf, ms_out = (ev[0].elapsed_time(ev[1]), ev[1].elapsed_time(ev[2]),
+                                     ev[2].elapsed_time(ev[3]))
+            self._batch_stats(rows, len(requests), int(ms_in * 1e6), int(ms_inf * 1e6), int(ms_out * 1e6))
+        host_all = None
+        if need_host:
+            host_all = pinned_view(slot["out_host"], np.float32, rows * self.OUT).reshape(rows, self.OUT).copy()
+        out = []
+        for (r, first, n), (kind, ro) in zip(plan, results):
+            if kind == "shm":
+                o = OutputTensor("fc6_1", "FP32", [n, self.OUT], None, shm=ro.shm)
+            else:
+                o = OutputTensor("fc6_1", "FP32", [n, self.OUT], host_all[first : first + n])
+            out.append([o])
+        return out
 
     def _execute_pgx(self, plan, rows, img_bytes, out_row):
         """Python-scheduled batch through the same C++ executor tcserve uses."""
-        import ctypes
-
         from .native_frontend import TcBatch, TcRef
 
         n = len(plan)
@@ -387,13 +349,11 @@ class DensenetOnnx(Model):
             nrows = (ctypes.c_int32 * n)(*[k for _, _, k in plan])
             timing = (ctypes.c_uint64 * 3)()
             b = TcBatch(n, rows, nrows, 1, ins, 1, outs, timing)
-            i = self._acquire()
-            try:
-                self._pgx.execute(i, ctypes.addressof(b))
-            except RuntimeError as e:
-                raise ServerError(str(e)) from e
-            finally:
-                self._release(i)
+            with self._slots.slot() as (i, _):
+                try:
+                    self._pgx.execute(i, ctypes.addressof(b))
+                except RuntimeError as e:
+                    raise ServerError(str(e)) from e
         except ServerError as e:
             return [e] * n
         if self._batch_stats is not None:
@@ -412,8 +372,6 @@ class DensenetOnnx(Model):
     def execute_native(self, instance, b):
         """One dynamic batch assembled by the C++ front end: raw device / host
         pointers in, outputs written straight to their targets."""
-        import ctypes
-
         from triton_client_amd.ops import hip
 
         img_bytes = self.C * self.H * self.W * 4
@@ -421,7 +379,7 @@ class DensenetOnnx(Model):
         total = int(b.total_rows)
         if total > max(self.buckets):
             raise ServerError("batch of %d rows exceeds the largest bucket" % total)
-        i = self._acquire()
+        i = self._slots.acquire()
         slot = self._slots[i]
         try:
             stream = slot["stream"]
@@ -468,7 +426,7 @@ class DensenetOnnx(Model):
             b.timing_ns[1] = int(ev[1].elapsed_time(ev[2]) * 1e6)
             b.timing_ns[2] = int(ev[2].elapsed_time(ev[3]) * 1e6)
         finally:
-            self._release(i)
+            self._slots.release(i)
 
     _server = None
     # set by the scheduler: (rows, n_requests, compute_input_ns, compute_infer_ns, compute_output_ns)
@@ -480,7 +438,7 @@ class DensenetOnnx(Model):
         return self._server.shm_target(region, nbytes, offset)
 
 
-class PreprocessInception(Model):
+class PreprocessInception(DeviceModel):
     """``preprocess_inception`` on the GPU: the same I/O contract as the CPU
     model of that name (BYTES PPM / PGM / TCIMG / JPEG / PNG blobs in, INCEPTION-scaled
     FP32 NCHW [3,224,224] out), which it replaces on a ``--gpu`` server.
@@ -552,67 +510,27 @@ class PreprocessInception(Model):
     C, H, W = 3, 224, 224
     STAGE_BYTES = 32 << 20  # pinned + device uint8 staging per instance (8 images of 1280x1024x3)
 
-    def __init__(self, version=1, device_id=0, **kw):
-        super().__init__(version, **kw)
-        self.device_id = int(kw.get("device", device_id))
-        self._slots = []
-        self._free = []
-        self._cv = threading.Condition()
-        self._host = None
-
     def load(self):
-        from .cpu_models import PreprocessInception as HostPreprocess
-
-        self._host = HostPreprocess(self.version)
-        self.device_path = os.environ.get("TCAMD_DEVICE_PREPROCESS", "1") != "0"
         self.device_huffman = jpeg_stage.device_huffman_knob()
         self.device_huffman_wide = jpeg_stage.device_huffman_wide_knob()
         self.device_png = jpeg_stage.device_png_knob()
-        if not self.device_path:
+        if not self._load_twin(_cpu.PreprocessInception, os.environ.get("TCAMD_DEVICE_PREPROCESS", "1") != "0"):
             return
-        import torch
-
-        from triton_client_amd.ops import hip, host_codec
+        from triton_client_amd.ops import host_codec
 
         self._codec = host_codec.load()  # the JPEG entropy decoder and the PNG inflate
-
-        if not torch.cuda.is_available():
-            raise ServerError("preprocess_inception (GPU) requires a GPU")
-        hip.lib()  # fail loudly if the native kernels are missing
-        self.torch = torch
-        dev = torch.device("cuda", self.device_id)
+        torch, _, dev = self._gpu()
         for _ in range(max(1, self.instance_count)):
-            host = hip.host_alloc(self.STAGE_BYTES)
-            self._slots.append({
-                "stream": torch.cuda.Stream(device=dev),
-                "stage_host": host,
-                "stage_np": np.ctypeslib.as_array((np.ctypeslib.ctypes.c_uint8 * self.STAGE_BYTES).from_address(host)),
-                "stage_dev": torch.empty(self.STAGE_BYTES, device=dev, dtype=torch.uint8),
-            })
-        self._free = list(range(len(self._slots)))
+            slot = {"stream": torch.cuda.Stream(device=dev),
+                    "stage_dev": torch.empty(self.STAGE_BYTES, device=dev, dtype=torch.uint8)}
+            slot["stage_np"] = pinned_view(self._pinned(slot, "stage_host", self.STAGE_BYTES), np.uint8,
+                                           self.STAGE_BYTES)
+            self._slots.add(slot)
 
     def unload(self):
-        from triton_client_amd.ops import hip
-
         for s in self._slots:
-            s.pop("stage_np", None)
-            try:
-                hip.host_free(s["stage_host"])
-            except Exception:
-                pass
-        self._slots = []
-        self._free = []
-
-    def _acquire(self):
-        with self._cv:
-            while not self._free:
-                self._cv.wait()
-            return self._free.pop()
-
-    def _release(self, i):
-        with self._cv:
-            self._free.append(i)
-            self._cv.notify()
+            s.pop("stage_np", None)  # the view goes before the memory under it
+        super().unload()
 
     def _host_one(self, r):
         try:
@@ -641,11 +559,9 @@ class PreprocessInception(Model):
     def execute(self, requests):
         if not self.device_path:
             return [self._host_one(r) for r in requests]
-        i = self._acquire()  # before the plan: JPEG coefficients are decoded straight into the slot's staging area
-        try:
-            return self._execute(self._slots[i], requests)
-        finally:
-            self._release(i)
+        # before the plan: JPEG coefficients are decoded straight into the slot's staging area
+        with self._slots.slot() as (_, slot):
+            return self._execute(slot, requests)
 
     def _execute(self, slot, requests):
         from triton_client_amd.ops import hip, host_codec
@@ -742,14 +658,12 @@ class PreprocessInception(Model):
         return res
 
 
-class PreprocessInceptionEnsemble(Model):
+class PreprocessInceptionEnsemble(Ensemble):
     """Ensemble: raw image bytes -> preprocess_inception -> densenet_onnx
     (the model the reference's ensemble_image_client drives,
     src/python/examples/ensemble_image_client.py)."""
 
     name = "preprocess_inception_ensemble"
-    platform = "ensemble"
-    backend = ""
     max_batch_size = 8
     inputs = (TensorSpec("INPUT", "BYTES", [1]),)
     outputs = (TensorSpec("OUTPUT", "FP32", [1000], label_filename="densenet_labels.txt"),)
@@ -759,14 +673,8 @@ class PreprocessInceptionEnsemble(Model):
     ]
     labels = DensenetOnnx.labels
 
-    def load(self):
-        pass
 
-    def execute(self, requests):  # pragma: no cover - the server runs ensembles step by step
-        raise ServerError("ensemble models are scheduled by the server")
-
-
-class BertLarge(Model):
+class BertLarge(DeviceModel):
     """``bert_large`` — BERT-large SQuAD-style QA (models/bert.py), the model of
     BASELINE.json's concurrency-sweep config.  INT32 [384] input_ids /
     attention_mask / token_type_ids in, FP32 [384] start/end logits out;
@@ -806,48 +714,34 @@ class BertLarge(Model):
     DENSE_FROM = 32
 
     def __init__(self, version=1, device_id=0, use_graphs=True, layers=24, **kw):
-        super().__init__(version, **kw)
-        self.device_id = int(kw.get("device", device_id))
+        super().__init__(version, device_id, **kw)
         self.use_graphs = use_graphs
         self.layers = int(layers)
-        self._slots = []
-        self._free = []
-        self._cv = threading.Condition()
 
     def load(self):
-        import torch
-
         from triton_client_amd.models import bert
-        from triton_client_amd.ops import hip
 
-        if not torch.cuda.is_available():
-            raise ServerError("bert_large requires a GPU")
-        hip.lib()
+        torch, _, dev = self._gpu("bert_large requires a GPU")
         torch.cuda.set_device(self.device_id)
-        self.torch = torch
-        dev = torch.device("cuda", self.device_id)
         self.model = self._build_model(bert, dev)
         # before the warm-up runs and graph captures below pick their GEMM solutions
         self.tuned_gemms = bert.use_tuned_gemms()
         for _ in range(max(1, self.instance_count)):
-            self._slots.append(self._make_slot(dev))
-        self._free = list(range(len(self._slots)))
+            self._slots.add(self._make_slot(dev))
 
     def _build_model(self, bert, dev):
         return bert.build(device=dev, layers=self.layers)
 
     def _make_slot(self, dev):
         torch = self.torch
-        from triton_client_amd.ops import hip
-
         n, s = self.max_batch_size, self.SEQ
         slot = {"stream": torch.cuda.Stream(device=dev), "graphs": {},
                 "ins": [torch.zeros(n, s, device=dev, dtype=torch.int32) for _ in range(3)],
                 "outs": [torch.zeros(n, s, device=dev, dtype=torch.float32) for _ in range(2)],
                 "ev": [torch.cuda.Event(enable_timing=True) for _ in range(4)]}
         slot["ins"][1].fill_(1)
-        slot["stage_host"] = hip.host_alloc(3 * n * s * 4)
-        slot["out_host"] = hip.host_alloc(2 * n * s * 4)
+        self._pinned(slot, "stage_host", 3 * n * s * 4)
+        self._pinned(slot, "out_host", 2 * n * s * 4)
 
         def run(b, dense=False):
             ids, mask, tt = (t[:b] for t in slot["ins"])
@@ -872,42 +766,17 @@ class BertLarge(Model):
         slot["stream"].synchronize()
         return slot
 
-    def unload(self):
-        from triton_client_amd.ops import hip
-
-        for sl in self._slots:
-            for k in ("stage_host", "out_host"):
-                try:
-                    hip.host_free(sl[k])
-                except Exception:
-                    pass
-        self._slots = []
-
-    def _acquire(self):
-        with self._cv:
-            while not self._free:
-                self._cv.wait()
-            return self._free.pop()
-
-    def _release(self, i):
-        with self._cv:
-            self._free.append(i)
-            self._cv.notify()
-
     def _mask_all_ones(self, slot, parts, total):
         """True when every real row's attention_mask is >= 1 everywhere (the
         model clamps it to [0, 1]).  Host-staged parts are scanned in place;
         if any part came from device memory (HIP shm) the staged device rows
         are checked on the slot stream (one small reduction + sync)."""
-        import ctypes
-
         on_device = False
         for kind, ptr, rows in parts:
             if kind == 1:
                 on_device = True
                 continue
-            a = np.ctypeslib.as_array((ctypes.c_int32 * (rows * self.SEQ)).from_address(ptr))
-            if a.min() < 1:
+            if pinned_view(ptr, np.int32, rows * self.SEQ).min() < 1:
                 return False
         if not on_device:
             return True
@@ -918,8 +787,6 @@ class BertLarge(Model):
     def _run_batch(self, slot, srcs, outs, total):
         """srcs: per input a list of (kind, ptr, rows) in row order; outs: per
         output a list of (kind, ptr, first_row, rows).  Returns timings (ns)."""
-        import ctypes
-
         from triton_client_amd.ops import hip
 
         row = self.SEQ * 4
@@ -998,17 +865,12 @@ class BertLarge(Model):
                 ref = b.outputs[r * b.n_outputs + k]
                 outs[k].append((ref.kind, ref.ptr, first, rows))
             first += rows
-        i = self._acquire()
-        try:
-            t = self._run_batch(self._slots[i], srcs, outs, total)
-        finally:
-            self._release(i)
+        with self._slots.slot() as (_, slot):
+            t = self._run_batch(slot, srcs, outs, total)
         for k in range(3):
             b.timing_ns[k] = t[k]
 
     def execute(self, requests):
-        import ctypes
-
         total = 0
         plan = []
         for r in requests:
@@ -1034,14 +896,10 @@ class BertLarge(Model):
         # outputs come back to host; shm targets are filled by the server (deliver_to_shm)
         res = np.empty((2, total, self.SEQ), dtype=np.float32)
         outs = [[(0, res[k].ctypes.data, 0, total)] for k in range(2)]
-        i = self._acquire()
-        try:
-            t = self._run_batch(self._slots[i], srcs, outs, total)
-        finally:
-            self._release(i)
+        with self._slots.slot() as (_, slot):
+            t = self._run_batch(slot, srcs, outs, total)
         if self._batch_stats is not None:
             self._batch_stats(total, len(requests), *t)
-        del ctypes
         return [[OutputTensor("start_logits", "FP32", [n, self.SEQ], res[0, f:f + n]),
                  OutputTensor("end_logits", "FP32", [n, self.SEQ], res[1, f:f + n])] for _, f, n in plan]
 
@@ -1054,15 +912,11 @@ class BertLarge(Model):
         the tensor as ``owner``."""
         torch = self.torch
         row = self.SEQ * 4
-        i = self._acquire()
-        try:
-            slot = self._slots[i]
+        with self._slots.slot() as (_, slot):
             with torch.cuda.stream(slot["stream"]):
                 res = torch.empty((2, total, self.SEQ), device=slot["stream"].device, dtype=torch.float32)
             outs = [[(1, res[k].data_ptr(), 0, total)] for k in range(2)]
             t = self._run_batch(slot, srcs, outs, total)  # ends with a stream synchronise
-        finally:
-            self._release(i)
         if self._batch_stats is not None:
             self._batch_stats(total, len(requests), *t)
         out = []
@@ -1104,7 +958,7 @@ class BertLargeFP32(BertLarge):
         return bert.prepare_x3(bert.build(device=dev, dtype=torch.float32, layers=self.layers))
 
 
-class QaSpans(Model):
+class QaSpans(DeviceModel):
     """``qa_spans`` on the GPU: the same I/O contract, request parameters and
     rule as the CPU model of that name (server/cpu_models.py QaSpans), which it
     replaces on a ``--gpu`` server and whose parameter checks it uses.
@@ -1134,66 +988,14 @@ class QaSpans(Model):
     instance_count = 2
     gpus = (0,)
 
-    def __init__(self, version=1, device_id=0, **kw):
-        super().__init__(version, **kw)
-        self.device_id = int(kw.get("device", device_id))
-        self._slots = []
-        self._free = []
-        self._cv = threading.Condition()
-        self._host = None
-
     def load(self):
-        from .cpu_models import QaSpans as HostQaSpans
-
-        self._host = HostQaSpans(self.version)
-        self._host.load()
-        self.device_path = os.environ.get("TCAMD_DEVICE_QA_SPANS", "1") != "0"
-        if not self.device_path:
+        if not self._load_twin(_cpu.QaSpans, os.environ.get("TCAMD_DEVICE_QA_SPANS", "1") != "0"):
             return
-        import torch
-
-        from triton_client_amd.ops import hip
-
-        if not torch.cuda.is_available():
-            raise ServerError("qa_spans (GPU) requires a GPU")
-        hip.lib()  # fail loudly if the native kernels are missing
-        self.torch = torch
-        dev = torch.device("cuda", self.device_id)
+        _, hip, dev = self._gpu()
         n, row = self.max_batch_size, self.SEQ * 4
         self.in_bytes = 4 * n * row + 2 * n * 4  # the four tensors, then k_row and len_row
         self.out_bytes = n * (hip.QA_SPANS_KMAX * 12 + 4)
-        for _ in range(max(1, self.instance_count)):
-            self._slots.append({
-                "stream": torch.cuda.Stream(device=dev),
-                "in_host": hip.host_alloc(self.in_bytes),
-                "out_host": hip.host_alloc(self.out_bytes),
-                "in_dev": torch.zeros(self.in_bytes, device=dev, dtype=torch.uint8),
-                "out_dev": torch.zeros(self.out_bytes, device=dev, dtype=torch.uint8),
-            })
-        self._free = list(range(len(self._slots)))
-
-    def unload(self):
-        from triton_client_amd.ops import hip
-
-        for s in self._slots:
-            for k in ("in_host", "out_host"):
-                try:
-                    hip.host_free(s[k])
-                except Exception:
-                    pass
-        self._slots = []
-        self._free = []
-
-    def _acquire(self):
-        with self._cv:
-            while not self._free:
-                self._cv.wait()
-            return self._free.pop()
-
-    def _release(self, i):
-        with self._cv:
-            self._free.append(i)
-            self._cv.notify()
+        self._add_stage_slots(dev, self.in_bytes, self.out_bytes)
 
     def execute(self, requests):
         plan, total = self._host.plan(requests)
@@ -1205,18 +1007,13 @@ class QaSpans(Model):
             return self._host.results(plan, *self._host.run_host(requests, plan, total))
         from triton_client_amd.ops import hip
 
-        i = self._acquire()
         try:
-            return self._host.results(plan, *self._execute(self._slots[i], requests, plan, total))
+            with self._slots.slot() as (_, slot):
+                return self._host.results(plan, *self._execute(slot, requests, plan, total))
         except (ServerError, hip.HipError) as e:
-            err = e if isinstance(e, ServerError) else ServerError("qa_spans: %s" % e)
-            return [p if isinstance(p, Exception) else err for p in plan]
-        finally:
-            self._release(i)
+            return plan_errors(plan, "qa_spans", e)
 
     def _execute(self, slot, requests, plan, total):
-        import ctypes
-
         from triton_client_amd.ops import hip
 
         n_max, row = self.max_batch_size, self.SEQ * 4
@@ -1224,7 +1021,7 @@ class QaSpans(Model):
         in_host, in_dev = slot["in_host"], slot["in_dev"].data_ptr()
         k_row, len_row, kmax = self._host.row_params(plan, total)
         par = 4 * n_max * row  # k_row and len_row: one copy
-        pars = np.ctypeslib.as_array((ctypes.c_int32 * (2 * n_max)).from_address(in_host + par))
+        pars = pinned_view(in_host + par, np.int32, 2 * n_max)
         pars[:total] = k_row
         pars[n_max:n_max + total] = len_row
         hip.memcpy_async(in_dev + par, in_host + par, 2 * n_max * 4, sh)
@@ -1233,18 +1030,12 @@ class QaSpans(Model):
         for c, spec in enumerate(self.inputs):
             base = c * n_max * row
             dt = np.float32 if spec.datatype == "FP32" else np.int32
-            stage = np.ctypeslib.as_array((ctypes.c_uint8 * (n_max * row)).from_address(in_host + base)).view(dt)
             lo, hi, where = None, 0, []
             for r, (first, n, _, _) in good:
-                t = r.input(spec.name)
-                if isinstance(t.data, DeviceView):
-                    if t.data.nbytes < n * row:
-                        raise ServerError("input region too small for %s" % spec.name)
-                    where.append(t.data.ptr)
-                    continue
-                stage[first * self.SEQ:(first + n) * self.SEQ] = np.asarray(t.data, dtype=dt).reshape(-1)
-                lo, hi = first if lo is None else lo, first + n
-                where.append(in_dev + base + first * row)
+                ptr, staged = place_input(slot, r.input(spec.name), spec.name, dt, n * row, base + first * row)
+                if staged:  # the staged rows of a tensor go up in one copy
+                    lo, hi = first if lo is None else lo, first + n
+                where.append(ptr)
             if lo is not None:
                 hip.memcpy_async(in_dev + base + lo * row, in_host + base + lo * row, (hi - lo) * row, sh)
             at.append(where)
@@ -1263,16 +1054,13 @@ class QaSpans(Model):
                          out_dev + first * kmax * 8, out_dev + o_scores + first * kmax * 4,
                          out_dev + o_null + first * 4, stream=sh)
             g = h
-        nbytes = total * (kmax * 12 + 4)
-        hip.memcpy_async(slot["out_host"], out_dev, nbytes, sh)
-        hip.stream_synchronize(sh)
-        raw = np.ctypeslib.as_array((ctypes.c_uint8 * nbytes).from_address(slot["out_host"])).copy()
+        raw = download(hip, slot, total * (kmax * 12 + 4), sh)
         return (raw[:o_scores].view(np.int32).reshape(total, kmax, 2),
                 raw[o_scores:o_null].view(np.float32).reshape(total, kmax),
                 raw[o_null:].view(np.float32))
 
 
-class BertQaEnsemble(Model):
+class BertQaEnsemble(Ensemble):
     """Ensemble: token ids -> ``bert_large`` -> ``qa_spans``.  The logits stay
     on the device between the steps (``bert_large`` hands them over as
     ``DeviceView``, K27 reads them in place); the second step takes the
@@ -1283,8 +1071,6 @@ class BertQaEnsemble(Model):
     for them does not pay for their copy."""
 
     name = "bert_qa_ensemble"
-    platform = "ensemble"
-    backend = ""
     max_batch_size = 128
     inputs = BertLarge.inputs
     outputs = QaSpans.outputs + BertLarge.outputs
@@ -1297,14 +1083,8 @@ class BertQaEnsemble(Model):
          {"spans": "spans", "scores": "scores", "null_score": "null_score"}),
     ]
 
-    def load(self):
-        pass
 
-    def execute(self, requests):  # pragma: no cover - the server runs ensembles step by step
-        raise ServerError("ensemble models are scheduled by the server")
-
-
-class BertTokenizer(Model):
+class BertTokenizer(DeviceModel):
     """``bert_tokenizer`` on the GPU: the same I/O contract, request parameter,
     vocabulary and rule as the CPU model of that name (server/cpu_models.py
     BertTokenizer), which it replaces on a ``--gpu`` server and whose checks it
@@ -1337,52 +1117,19 @@ class BertTokenizer(Model):
     instance_count = 2
     gpus = (0,)
 
-    def __init__(self, version=1, device_id=0, **kw):
-        super().__init__(version, **kw)
-        self.device_id = int(kw.get("device", device_id))
-        self._slots = []
-        self._free = []
-        self._cv = threading.Condition()
-        self._host = None
-
     def load(self):
-        from .cpu_models import BertTokenizer as HostBertTokenizer
-
-        self._host = HostBertTokenizer(self.version)
-        self._host.load()
+        device_path = self._load_twin(_cpu.BertTokenizer, os.environ.get("TCAMD_DEVICE_TOKENIZER", "1") != "0")
         self.vocab = self._host.vocab
-        self.device_path = os.environ.get("TCAMD_DEVICE_TOKENIZER", "1") != "0"
-        if not self.device_path:
+        if not device_path:
             return
-        import torch
-
-        from triton_client_amd.ops import hip
-
-        if not torch.cuda.is_available():
-            raise ServerError("bert_tokenizer (GPU) requires a GPU")
-        hip.lib()  # fail loudly if the native kernels are missing
-        self.torch = torch
-        dev = torch.device("cuda", self.device_id)
+        torch, hip, dev = self._gpu()
         n = self.max_batch_size
         self.head_bytes = n * 16 + n * 4  # the row table, then max_query_length per row
         self.in_bytes = self.head_bytes + self.TEXT_BUDGET
         self.ws_bytes = hip.wordpiece_workspace(n, self.TEXT_BUDGET)
         self.out_bytes = n * (self.SEQ * 5 + 2) * 4
         self.vocab_dev = torch.from_numpy(self.vocab.image.view(np.int32).copy()).to(dev)
-        for _ in range(max(1, self.instance_count)):
-            self._slots.append({
-                "stream": torch.cuda.Stream(device=dev),
-                "in_host": hip.host_alloc(self.in_bytes),
-                "out_host": hip.host_alloc(self.out_bytes),
-                "in_dev": torch.zeros(self.in_bytes, device=dev, dtype=torch.uint8),
-                "out_dev": torch.zeros(self.out_bytes, device=dev, dtype=torch.uint8),
-                "ws": torch.zeros(self.ws_bytes, device=dev, dtype=torch.uint8),
-            })
-        self._free = list(range(len(self._slots)))
-
-    unload = QaSpans.unload
-    _acquire = QaSpans._acquire
-    _release = QaSpans._release
+        self._add_stage_slots(dev, self.in_bytes, self.out_bytes, ws=self.ws_bytes)
 
     def execute(self, requests):
         plan, total = self._host.plan(requests)
@@ -1395,14 +1142,11 @@ class BertTokenizer(Model):
         from triton_client_amd.ops import hip
 
         on_device = all(getattr(r, "accepts_device_outputs", False) for r in requests)
-        i = self._acquire()
         try:
-            return self._execute(self._slots[i], plan, total, on_device)
+            with self._slots.slot() as (_, slot):
+                return self._execute(slot, plan, total, on_device)
         except (ServerError, hip.HipError) as e:
-            err = e if isinstance(e, ServerError) else ServerError("bert_tokenizer: %s" % e)
-            return [p if isinstance(p, Exception) else err for p in plan]
-        finally:
-            self._release(i)
+            return plan_errors(plan, "bert_tokenizer", e)
 
     @classmethod
     def launches(cls, lens):
@@ -1418,8 +1162,6 @@ class BertTokenizer(Model):
         return out
 
     def _execute(self, slot, plan, total, on_device):
-        import ctypes
-
         from triton_client_amd.ops import hip
 
         torch, S, n_max = self.torch, self.SEQ, self.max_batch_size
@@ -1436,19 +1178,14 @@ class BertTokenizer(Model):
             id_ptrs = [res[k].data_ptr() for k in range(3)]
         else:
             id_ptrs = [out_dev + o_ids + k * total * S * 4 for k in range(3)]
-        table = np.ctypeslib.as_array((ctypes.c_uint32 * (n_max * 4)).from_address(in_host)).reshape(n_max, 4)
-        maxq = np.ctypeslib.as_array((ctypes.c_int32 * n_max).from_address(in_host + n_max * 16))
+        table = pinned_view(in_host, np.uint32, n_max * 4).reshape(n_max, 4)
+        maxq = pinned_view(in_host + n_max * 16, np.int32, n_max)
         lens = [len(q) + len(c) for q, c in zip(qs, cs)]
         groups = self.launches(lens)
         for g, (first, rows) in enumerate(groups):
             if g:
                 hip.stream_synchronize(sh)  # the staging area is about to be rewritten
-            at = 0
-            for r in range(rows):
-                for f, s in enumerate((qs[first + r], cs[first + r])):
-                    table[r, 2 * f], table[r, 2 * f + 1] = at, len(s)
-                    ctypes.memmove(in_host + self.head_bytes + at, s, len(s))
-                    at += len(s)
+            at = stage_texts(slot, table, zip(qs[first:first + rows], cs[first:first + rows]), self.head_bytes)
             maxq[:rows] = mq[first:first + rows]
             hip.memcpy_async(in_dev, in_host, self.head_bytes + at, sh)
             hip.wordpiece_tokenize(in_dev + self.head_bytes, at, in_dev, in_dev + n_max * 16, rows, S,
@@ -1456,10 +1193,7 @@ class BertTokenizer(Model):
                                    self.ws_bytes, id_ptrs[0] + first * S * 4, id_ptrs[1] + first * S * 4,
                                    id_ptrs[2] + first * S * 4, out_dev + first * S * 8, out_dev + o_over + first * 4,
                                    out_dev + o_stat + first * 4, stream=sh)
-        nbytes = o_ids if on_device else o_ids + 3 * total * S * 4
-        hip.memcpy_async(slot["out_host"], out_dev, nbytes, sh)
-        hip.stream_synchronize(sh)
-        raw = np.ctypeslib.as_array((ctypes.c_uint8 * nbytes).from_address(slot["out_host"])).copy()
+        raw = download(hip, slot, o_ids if on_device else o_ids + 3 * total * S * 4, sh)
         offsets = raw[:o_over].view(np.int32).reshape(total, S, 2)
         overflow, status = raw[o_over:o_stat].view(np.int32), raw[o_stat:o_ids].view(np.uint32)
         if on_device:
@@ -1469,7 +1203,7 @@ class BertTokenizer(Model):
         return self._host.results(plan, ids, mask, tt, offsets, overflow, status)
 
 
-class BertQaTextEnsemble(Model):
+class BertQaTextEnsemble(Ensemble):
     """Ensemble: UTF-8 text -> ``bert_tokenizer`` -> ``bert_large`` ->
     ``qa_spans``.  The ids stay on the device between the first two steps and
     the logits between the last two (each step hands its outputs on as
@@ -1483,8 +1217,6 @@ class BertQaTextEnsemble(Model):
     doc-stride windows."""
 
     name = "bert_qa_text_ensemble"
-    platform = "ensemble"
-    backend = ""
     max_batch_size = 128
     inputs = BertTokenizer.inputs
     outputs = QaSpans.outputs + BertTokenizer.outputs[3:] + BertTokenizer.outputs[:3] + BertLarge.outputs
@@ -1500,14 +1232,8 @@ class BertQaTextEnsemble(Model):
          {"spans": "spans", "scores": "scores", "null_score": "null_score"}),
     ]
 
-    def load(self):
-        pass
 
-    def execute(self, requests):  # pragma: no cover - the server runs ensembles step by step
-        raise ServerError("ensemble models are scheduled by the server")
-
-
-class BertWindowTokenizer(Model):
+class BertWindowTokenizer(DeviceModel):
     """``bert_window_tokenizer`` on the GPU: the same I/O contract, request
     parameters, vocabulary and rule as the CPU model of that name
     (server/cpu_models.py BertWindowTokenizer), which it replaces on a ``--gpu``
@@ -1537,32 +1263,12 @@ class BertWindowTokenizer(Model):
     instance_count = 2
     gpus = (0,)
 
-    def __init__(self, version=1, device_id=0, **kw):
-        super().__init__(version, **kw)
-        self.device_id = int(kw.get("device", device_id))
-        self._slots = []
-        self._free = []
-        self._cv = threading.Condition()
-        self._host = None
-
     def load(self):
-        from .cpu_models import BertWindowTokenizer as HostModel
-
-        self._host = HostModel(self.version)
-        self._host.load()
+        device_path = self._load_twin(_cpu.BertWindowTokenizer, os.environ.get("TCAMD_DEVICE_TOKENIZER", "1") != "0")
         self.vocab = self._host.vocab
-        self.device_path = os.environ.get("TCAMD_DEVICE_TOKENIZER", "1") != "0"
-        if not self.device_path:
+        if not device_path:
             return
-        import torch
-
-        from triton_client_amd.ops import hip
-
-        if not torch.cuda.is_available():
-            raise ServerError("bert_window_tokenizer (GPU) requires a GPU")
-        hip.lib()  # fail loudly if the native kernels are missing
-        self.torch = torch
-        dev = torch.device("cuda", self.device_id)
+        torch, hip, dev = self._gpu()
         n, S = self.MAX_ROWS, self.SEQ
         self.head_bytes = n * 16 + 3 * n * 4  # the table, then max_query_length, doc_stride, max_windows per document
         self.in_bytes = self.head_bytes + self.TEXT_BUDGET
@@ -1572,45 +1278,19 @@ class BertWindowTokenizer(Model):
         self.o_ids = self.o_offsets + n * S * 8
         self.out_bytes = self.o_ids + 4 * n * S * 4
         self.vocab_dev = torch.from_numpy(self.vocab.image.view(np.int32).copy()).to(dev)
-        for _ in range(max(1, self.instance_count)):
-            self._slots.append({
-                "stream": torch.cuda.Stream(device=dev),
-                "in_host": hip.host_alloc(self.in_bytes),
-                "out_host": hip.host_alloc(self.out_bytes),
-                "in_dev": torch.zeros(self.in_bytes, device=dev, dtype=torch.uint8),
-                "out_dev": torch.zeros(self.out_bytes, device=dev, dtype=torch.uint8),
-                "ws": torch.zeros(self.ws_bytes, device=dev, dtype=torch.uint8),
-            })
-        self._free = list(range(len(self._slots)))
-
-    unload = QaSpans.unload
-    _acquire = QaSpans._acquire
-    _release = QaSpans._release
+        self._add_stage_slots(dev, self.in_bytes, self.out_bytes, ws=self.ws_bytes)
 
     def execute(self, requests):
-        from triton_client_amd.ops import hip
+        return self._per_request(requests, self._one)
 
-        out = []
-        for r in requests:
-            try:
-                p = self._host.plan_one(r)
-                if not self.device_path:
-                    out.append(self._host.run_host_one(p))
-                    continue
-                i = self._acquire()
-                try:
-                    out.append(self._execute(self._slots[i], p, bool(getattr(r, "accepts_device_outputs", False))))
-                finally:
-                    self._release(i)
-            except ServerError as e:
-                out.append(e)
-            except hip.HipError as e:
-                out.append(ServerError("%s: %s" % (self.name, e)))
-        return out
+    def _one(self, r):
+        p = self._host.plan_one(r)
+        if not self.device_path:
+            return self._host.run_host_one(p)
+        with self._slots.slot() as (_, slot):
+            return self._execute(slot, p, bool(getattr(r, "accepts_device_outputs", False)))
 
     def _execute(self, slot, p, on_device):
-        import ctypes
-
         from triton_client_amd.ops import hip
 
         qs, cs, mq, ds, mw = p
@@ -1622,14 +1302,9 @@ class BertWindowTokenizer(Model):
         sh = slot["stream"].cuda_stream
         in_host, in_dev, out_host = slot["in_host"], slot["in_dev"].data_ptr(), slot["out_host"]
         out_dev = slot["out_dev"].data_ptr()
-        table = np.ctypeslib.as_array((ctypes.c_uint32 * (n * 4)).from_address(in_host)).reshape(n, 4)
-        pars = np.ctypeslib.as_array((ctypes.c_int32 * (3 * n)).from_address(in_host + n * 16)).reshape(3, n)
-        at = 0
-        for d in range(docs):
-            for f, t in enumerate((qs[d], cs[d])):
-                table[d, 2 * f], table[d, 2 * f + 1] = at, len(t)
-                ctypes.memmove(in_host + self.head_bytes + at, t, len(t))
-                at += len(t)
+        table = pinned_view(in_host, np.uint32, n * 4).reshape(n, 4)
+        pars = pinned_view(in_host + n * 16, np.int32, 3 * n).reshape(3, n)
+        at = stage_texts(slot, table, zip(qs, cs), self.head_bytes)
         pars[0, :docs], pars[1, :docs], pars[2, :docs] = mq, ds, mw
         res = None
         if on_device:
@@ -1644,9 +1319,7 @@ class BertWindowTokenizer(Model):
                               self.ws_bytes, n, id_ptrs[0], id_ptrs[1], id_ptrs[2], id_ptrs[3],
                               out_dev + self.o_offsets, out_dev + self.o_winfo, out_dev, out_dev + self.o_nrows,
                               stream=sh)
-        hip.memcpy_async(out_host, out_dev, self.o_offsets, sh)
-        hip.stream_synchronize(sh)
-        head = np.ctypeslib.as_array((ctypes.c_uint8 * self.o_offsets).from_address(out_host)).copy()
+        head = download(hip, slot, self.o_offsets, sh)
         dinfo = head[:docs * 16].view(np.uint32).reshape(docs, 4)
         n_rows = int(head[self.o_nrows:self.o_nrows + 4].view(np.int32)[0])
         err = self._host.doc_error(dinfo, mw)
@@ -1661,18 +1334,17 @@ class BertWindowTokenizer(Model):
         hip.stream_synchronize(sh)
 
         def rows_at(o, width):
-            raw = np.ctypeslib.as_array((ctypes.c_uint8 * (n_rows * S * width)).from_address(out_host + o)).copy()
-            return raw.view(np.int32)
+            return pinned_view(out_host + o, np.int32, n_rows * S * width).copy()
 
-        host["offsets"] = rows_at(self.o_offsets, 8).reshape(n_rows, S, 2)
+        host["offsets"] = rows_at(self.o_offsets, 2).reshape(n_rows, S, 2)
         if on_device:
             return self._host.window_results(dinfo, n_rows, host, device=(res, self.device_id))
         for k, nm in enumerate(("input_ids", "attention_mask", "token_type_ids", "start_mask")):
-            host[nm] = rows_at(self.o_ids + k * n * S * 4, 4).reshape(n_rows, S)
+            host[nm] = rows_at(self.o_ids + k * n * S * 4, 1).reshape(n_rows, S)
         return self._host.window_results(dinfo, n_rows, host)
 
 
-class QaDocSpans(Model):
+class QaDocSpans(DeviceModel):
     """``qa_doc_spans`` on the GPU: the same I/O contract, request parameters
     and rule as the CPU model of that name (server/cpu_models.py QaDocSpans),
     which it replaces on a ``--gpu`` server and whose checks it uses.
@@ -1696,31 +1368,10 @@ class QaDocSpans(Model):
     instance_count = 2
     gpus = (0,)
 
-    def __init__(self, version=1, device_id=0, **kw):
-        super().__init__(version, **kw)
-        self.device_id = int(kw.get("device", device_id))
-        self._slots = []
-        self._free = []
-        self._cv = threading.Condition()
-        self._host = None
-
     def load(self):
-        from .cpu_models import QaDocSpans as HostModel
-
-        self._host = HostModel(self.version)
-        self._host.load()
-        self.device_path = os.environ.get("TCAMD_DEVICE_QA_SPANS", "1") != "0"
-        if not self.device_path:
+        if not self._load_twin(_cpu.QaDocSpans, os.environ.get("TCAMD_DEVICE_QA_SPANS", "1") != "0"):
             return
-        import torch
-
-        from triton_client_amd.ops import hip
-
-        if not torch.cuda.is_available():
-            raise ServerError("qa_doc_spans (GPU) requires a GPU")
-        hip.lib()  # fail loudly if the native kernels are missing
-        self.torch = torch
-        dev = torch.device("cuda", self.device_id)
+        _, hip, dev = self._gpu()
         n, row, kmax = self.MAX_ROWS, self.SEQ * 4, hip.QA_SPANS_KMAX
         # the five row tensors, window_info, doc_info, then k_row, len_row and k_doc
         self.o_winfo = 5 * n * row
@@ -1728,68 +1379,31 @@ class QaDocSpans(Model):
         self.in_bytes = self.o_par + 3 * n * 4
         self.list_bytes = n * (kmax * 12 + 4)  # K27's lists: spans, scores, null
         self.out_bytes = n * (kmax * 16 + 4)   # K29's: spans, windows, scores, null
-        for _ in range(max(1, self.instance_count)):
-            self._slots.append({
-                "stream": torch.cuda.Stream(device=dev),
-                "in_host": hip.host_alloc(self.in_bytes),
-                "out_host": hip.host_alloc(self.out_bytes),
-                "in_dev": torch.zeros(self.in_bytes, device=dev, dtype=torch.uint8),
-                "lists": torch.zeros(self.list_bytes, device=dev, dtype=torch.uint8),
-                "out_dev": torch.zeros(self.out_bytes, device=dev, dtype=torch.uint8),
-            })
-        self._free = list(range(len(self._slots)))
-
-    unload = QaSpans.unload
-    _acquire = QaSpans._acquire
-    _release = QaSpans._release
+        self._add_stage_slots(dev, self.in_bytes, self.out_bytes, lists=self.list_bytes)
 
     def execute(self, requests):
-        from triton_client_amd.ops import hip
+        return self._per_request(requests, self._one, wrapped=(ValueError,))
 
-        out = []
-        for r in requests:
-            try:
-                p = self._host.plan_one(r)
-                if not self.device_path:
-                    out.append(self._host.run_host_one(r, p))
-                    continue
-                i = self._acquire()
-                try:
-                    out.append(self._host.doc_results(p[2], *self._execute(self._slots[i], r, p)))
-                finally:
-                    self._release(i)
-            except ServerError as e:
-                out.append(e)
-            except (ValueError, hip.HipError) as e:
-                out.append(ServerError("%s: %s" % (self.name, e)))
-        return out
+    def _one(self, r):
+        p = self._host.plan_one(r)
+        if not self.device_path:
+            return self._host.run_host_one(r, p)
+        with self._slots.slot() as (_, slot):
+            return self._host.doc_results(p[2], *self._execute(slot, r, p))
 
     def _execute(self, slot, r, p):
-        import ctypes
-
         from triton_client_amd.ops import hip
 
         W, D, k, ln = p
         n, row = self.MAX_ROWS, self.SEQ * 4
         sh = slot["stream"].cuda_stream
         in_host, in_dev = slot["in_host"], slot["in_dev"].data_ptr()
-        pars = np.ctypeslib.as_array((ctypes.c_int32 * (3 * n)).from_address(in_host + self.o_par)).reshape(3, n)
+        pars = pinned_view(in_host + self.o_par, np.int32, 3 * n).reshape(3, n)
         pars[0, :W], pars[1, :W], pars[2, :D] = k, ln, k
         hip.memcpy_async(in_dev + self.o_par, in_host + self.o_par, 3 * n * 4, sh)
-        at = []
         specs = [(nm, dt, W * row, c * n * row) for c, (nm, dt) in enumerate(self._host.ROW_INPUTS)]
         specs += [("window_info", np.int32, W * 16, self.o_winfo), ("doc_info", np.int32, D * 16, self.o_dinfo)]
-        for nm, dt, nbytes, base in specs:
-            t = r.input(nm)
-            if isinstance(t.data, DeviceView):
-                if t.data.nbytes < nbytes:
-                    raise ServerError("input region too small for %s" % nm)
-                at.append(t.data.ptr)
-                continue
-            stage = np.ctypeslib.as_array((ctypes.c_uint8 * nbytes).from_address(in_host + base)).view(dt)
-            stage[:] = np.asarray(t.data, dtype=dt).reshape(-1)
-            hip.memcpy_async(in_dev + base, in_host + base, nbytes, sh)
-            at.append(in_dev + base)
+        at = [stage_input(hip, slot, r.input(nm), nm, dt, nbytes, base, sh) for nm, dt, nbytes, base in specs]
         lists, out_dev = slot["lists"].data_ptr(), slot["out_dev"].data_ptr()
         l_scores, l_null = W * k * 8, W * k * 12
         hip.qa_spans_masked(at[0], at[1], row, at[2], at[3], at[4], row, W, self.SEQ, in_dev + self.o_par,
@@ -1797,15 +1411,12 @@ class QaDocSpans(Model):
         o_windows, o_scores, o_null = D * k * 8, D * k * 12, D * k * 16
         hip.qa_merge(lists, lists + l_scores, lists + l_null, W, at[5], at[6], D, in_dev + self.o_par + 2 * n * 4, k,
                      out_dev, out_dev + o_windows, out_dev + o_scores, out_dev + o_null, stream=sh)
-        nbytes = D * (k * 16 + 4)
-        hip.memcpy_async(slot["out_host"], out_dev, nbytes, sh)
-        hip.stream_synchronize(sh)
-        raw = np.ctypeslib.as_array((ctypes.c_uint8 * nbytes).from_address(slot["out_host"])).copy()
+        raw = download(hip, slot, D * (k * 16 + 4), sh)
         return (raw[:o_windows].view(np.int32).reshape(D, k, 2), raw[o_windows:o_scores].view(np.int32).reshape(D, k),
                 raw[o_scores:o_null].view(np.float32).reshape(D, k), raw[o_null:].view(np.float32))
 
 
-class BertQaDocEnsemble(Model):
+class BertQaDocEnsemble(Ensemble):
     """Ensemble: UTF-8 documents -> ``bert_window_tokenizer`` -> ``bert_large``
     -> ``qa_doc_spans``: question answering over contexts longer than the
     384-token row, by overlapping doc-stride windows, the max-context rule and a
@@ -1820,8 +1431,6 @@ class BertQaDocEnsemble(Model):
     for their copy."""
 
     name = "bert_qa_doc_ensemble"
-    platform = "ensemble"
-    backend = ""
     max_batch_size = 0
     inputs = BertWindowTokenizer.inputs
     outputs = (QaDocSpans.outputs + BertWindowTokenizer.outputs[4:] + BertWindowTokenizer.outputs[:4] +
@@ -1838,12 +1447,6 @@ class BertQaDocEnsemble(Model):
                           "start_mask": "start_mask", "window_info": "window_info", "doc_info": "doc_info"},
          {"spans": "spans", "windows": "windows", "scores": "scores", "null_score": "null_score"}),
     ]
-
-    def load(self):
-        pass
-
-    def execute(self, requests):  # pragma: no cover - the server runs ensembles step by step
-        raise ServerError("ensemble models are scheduled by the server")
 
 
 GPU_MODELS = [DensenetOnnx, PreprocessInception, PreprocessInceptionEnsemble, BertLarge, QaSpans, BertQaEnsemble,

@@ -16,57 +16,15 @@
 #include <atomic>
 #include <type_traits>
 
+#include "kernels/bert_ln.h"
 #include "kernels/common.h"
 
 namespace {
 
-typedef uint32_t v4u __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ uint32_t pack2(float a, float b) {
-  const bf16x2 v = {(__bf16)a, (__bf16)b};
-  return __builtin_bit_cast(uint32_t, v);
-}
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-// LayerNorm of one row held as v[E] per lane (lane l owns the 16-B chunks
-// l, l + 64, ...) -> bf16 out row: exact two-pass mean / variance over the
-// register copy, wave butterflies through DPP-backed shuffles
-template <int E>
-__device__ __forceinline__ void ln_store_row(const float (&v)[E], const uint16_t* __restrict__ gamma,
-                                             const uint16_t* __restrict__ beta, uint16_t* orow, int lane, float eps) {
-  constexpr int H = 64 * E, C = E / 8;
-  float s = 0.f;
-#pragma unroll
-  for (int e = 0; e < E; ++e) s += v[e];
-  const float mean = wave_sum(s) * (1.0f / H);
-  float ss = 0.f;
-#pragma unroll
-  for (int e = 0; e < E; ++e) {
-    const float d = v[e] - mean;
-    ss += d * d;
-  }
-  const float rstd = rsqrtf(wave_sum(ss) * (1.0f / H) + eps);
-#pragma unroll
-  for (int c = 0; c < C; ++c) {
-    const int off = (c * 64 + lane) * 8;
-    const v4u g = *reinterpret_cast<const v4u*>(gamma + off);
-    const v4u bt = *reinterpret_cast<const v4u*>(beta + off);
-    v4u o;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const float g0 = __uint_as_float(g[q] << 16), g1 = __uint_as_float(g[q] & 0xffff0000u);
-      const float b0 = __uint_as_float(bt[q] << 16), b1 = __uint_as_float(bt[q] & 0xffff0000u);
-      o[q] = pack2((v[c * 8 + 2 * q] - mean) * rstd * g0 + b0, (v[c * 8 + 2 * q + 1] - mean) * rstd * g1 + b1);
-    }
-    *reinterpret_cast<v4u*>(orow + off) = o;
-  }
-}
+using tcamd_bert::v4u;
+using tcamd_bert::pack2;
+using tcamd_bert::wave_sum;
+using tcamd_bert::ln_store_row;
 
 // E = elements per lane (H = 64 * E), a multiple of 8.  Lane l owns the 16-B
 // chunks l, l + 64, ... of the row (coalesced: a wave instruction covers 1 KB).
@@ -304,221 +262,56 @@ __device__ __forceinline__ bf16x8 as_bf8(v4u v) { return __builtin_bit_cast(bf16
 // adds (q + b_q) . b_k to every score of a query, a constant that softmax
 // removes, so it is dropped; the value bias passes through the normalised
 // weights unchanged and is added to the output.
+//
+// The device code is a function of a row geometry, shared by K12 and K12v
+// (packed rows, below): the row's first token, the number of keys it stages
+// ``S`` (a multiple of 64: LDS rows and chunk count) and its length ``len``.
+// It lives in kernels/bert_attention_row.h, which says why it is a text and
+// not a function, and why its one barrier is workgroup-uniform.  K12 gives it
+// (seq * S, S, S) and PACKED = false, which folds every use of ``len`` away;
+// K12v (cu[r], 64 * ceil(len / 64), len).
 template <bool MASKED>
 __global__ void __launch_bounds__(768, 1) attention_kernel(const uint16_t* __restrict__ qkv, const int* __restrict__ mask,
                                                            uint16_t* __restrict__ out, int S, int heads, float scale,
                                                            const uint16_t* __restrict__ qkv_bias) {
-  extern __shared__ __attribute__((aligned(16))) uint8_t lds_a[];
-  uint16_t* Ks = reinterpret_cast<uint16_t*>(lds_a);
-  uint16_t* Vs = Ks + S * kAD;
-  float* kb = reinterpret_cast<float*>(Vs + S * kAD);  // per-key log2-domain bias
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int nthr = blockDim.x;
-  const int seq = blockIdx.x / heads, head = blockIdx.x % heads;
-  const int HD = heads * kAD, ld = 3 * HD;
-  const uint16_t* base = qkv + (size_t)seq * S * ld + head * kAD;
-  constexpr float kLog2e = 1.4426950408889634f;
+  constexpr bool PACKED = false;
+#define TC_ATTN_ROW_GEOMETRY const int seq = blockIdx.x / heads, head = blockIdx.x % heads, len = S;
+#define TC_ATTN_ROW_TOK0 ((size_t)seq * S)
+#include "kernels/bert_attention_row.h"
+#undef TC_ATTN_ROW_GEOMETRY
+#undef TC_ATTN_ROW_TOK0
+}
 
-  // ---- stage K and V rows (128 B each) by LDS-DMA (round 6) ----
-  // Both row-major, 16-B chunks XOR-swizzled on the SOURCE address (the DMA
-  // writes lane-linear: one wave instruction = 8 rows), every instruction of
-  // the block in flight at once and one wait.  K chunk c of key k sits at
-  // c ^ ((k >> 1) & 7) (conflict-free b128 reads by 16 consecutive keys);
-  // V chunk c at c ^ (((k >> 1) & 1) << 2), which makes the transposing
-  // ds_read_b64_tr_b16 reads of the PV operand conflict-free.  (Round 5
-  // staged with per-thread 16-B loads and transposed V by 4-byte LDS writes:
-  // ~25 of 83 us at bs64 and half of bs1's 11 us went to that staging,
-  // profiles/r6_k12/.)
+// ---- K12v: K12 over packed rows -------------------------------------------
+// qkv [t_cap][3 * heads * 64] holds the tokens of rows of different lengths
+// back to back (K30 bert_pack_plan, csrc/kernels/bert_pack.hip): block (row r,
+// head) attends the queries and keys cu[r] .. cu[r] + row_len[r] - 1 and
+// touches no other token, so rows [T, t_cap) of qkv are never read and those
+// of out never written.  It stages 64 * ceil(len / 64) keys, the ones at or
+// past len as copies of the row's last token under the -10000 bias.  The grid
+// is fixed per (rows, heads) -- K12's plan at S = 384 -- so a HIP graph can
+// capture it; an empty row's blocks, a block whose query split starts past
+// the row's end, and a row that does not fit t_cap (a caller's error) return
+// at once, on conditions uniform over the block.
+__global__ void __launch_bounds__(768, 1) attention_packed_kernel(const uint16_t* __restrict__ qkv,
+                                                                  const int* __restrict__ row_len,
+                                                                  const int* __restrict__ cu,
+                                                                  uint16_t* __restrict__ out, int t_cap, int heads,
+                                                                  float scale, const uint16_t* __restrict__ qkv_bias) {
+  constexpr bool MASKED = true, PACKED = true;
+  const int row = blockIdx.x / heads, first = cu[row];
   {
-    const int nw = nthr >> 6, nrb = S >> 3;  // waves, 8-row blocks per operand
-    const int r8 = lane >> 3, cs = lane & 7;
-    for (int j = wave; j < 2 * nrb; j += nw) {
-      const bool isv = j >= nrb;
-      const int row = 8 * (isv ? j - nrb : j) + r8;
-      const int c = isv ? cs ^ (((row >> 1) & 1) << 2) : cs ^ ((row >> 1) & 7);
-      const uint16_t* src = base + (size_t)row * ld + (isv ? 2 * HD : HD) + 8 * c;
-      uint8_t* dst = lds_a + (isv ? S * 128 : 0) + (j - (isv ? nrb : 0)) * 1024;
-      __builtin_amdgcn_global_load_lds((const void*)src, (void*)dst, 16, 0, 0);
-    }
+    const int len = row_len[row];
+    if (len <= 0 || len > kAMaxS || first < 0 || first > t_cap - len) return;
+    if (32 * (int)(blockIdx.y * (blockDim.x >> 6)) >= len) return;
   }
-  if (MASKED)
-    for (int k = tid; k < S; k += nthr) kb[k] = mask[(size_t)seq * S + k] == 0 ? -10000.0f * kLog2e : 0.0f;
-
-  // ---- this wave's queries: Q^T fragments (B operand: lane col = query) ----
-  const int col = lane & 31, h = lane >> 5;
-  const int q = 32 * (blockIdx.y * (nthr >> 6) + wave) + col;
-  v4u qf[4];
-#pragma unroll
-  for (int kk = 0; kk < 4; ++kk) qf[kk] = *reinterpret_cast<const v4u*>(base + (size_t)q * ld + 16 * kk + 8 * h);
-  if (qkv_bias) {
-#pragma unroll
-    for (int kk = 0; kk < 4; ++kk) {
-      const v4u bq = *reinterpret_cast<const v4u*>(qkv_bias + head * kAD + 16 * kk + 8 * h);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const float a0 = __uint_as_float(qf[kk][j] << 16) + __uint_as_float(bq[j] << 16);
-        const float a1 = __uint_as_float(qf[kk][j] & 0xffff0000u) + __uint_as_float(bq[j] & 0xffff0000u);
-        qf[kk][j] = pack2(a0, a1);
-      }
-    }
-  }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's K / V DMAs landed
-  __syncthreads();                                   // ... and every other wave's
-
-  const float sl2 = scale * kLog2e;
-  float m_run = -1.0e30f, l_part = 0.f;
-  f32x16 o[2];
-#pragma unroll
-  for (int r = 0; r < 2; ++r)
-#pragma unroll
-    for (int e = 0; e < 16; ++e) o[r][e] = 0.f;
-
-  // Chunk classes (round 6).  A key-padding mask is a run of valid keys, so
-  // most 64-key chunks are all valid or all padded: an all-valid chunk takes
-  // the unmasked math (no bias add, one FMA per score into the exponent), an
-  // all-padded chunk is skipped -- exactly: behind any valid key its scores
-  // are exp2(<= -14000) = 0 in fp32, and if it comes first the first valid
-  // chunk's rescale zeroes it.  Only a sequence with no valid key at all runs
-  // every chunk masked (softmax over the padded scores, as torch does).
-  const int nch = S / 64;
-  uint32_t todo = (1u << nch) - 1u, full = todo;
-  if constexpr (MASKED) {
-    full = 0u;
-    uint32_t empty = 0u;
-    for (int c = 0; c < nch; ++c) {
-      const uint64_t v = __ballot(kb[64 * c + lane] == 0.0f);
-      if (v == ~0ull) full |= 1u << c;
-      if (v == 0ull) empty |= 1u << c;
-    }
-    if (empty != todo) todo &= ~empty;
-  }
-
-  // transposed V reads: lane 4 q4 + p4 of 16-lane group g supplies row (key)
-  // 4 h + q4 of the 16-key step, dims 32 rd + 16 (g & 1) + 4 p4 .. + 3 (8 B of
-  // chunk 4 rd + 2 (g & 1) + p4 / 2, swizzled by its key -- bit 1 of the key
-  // is bit 1 of q4, the other terms are multiples of 4)
-  const int q4 = (lane >> 2) & 3, p4 = lane & 3, g1 = (lane >> 4) & 1;
-  const int vch = 2 * g1 + (p4 >> 1);
-  const uint8_t* vbase = lds_a + S * 128 + (4 * h + q4) * 128 + ((vch ^ (((q4 >> 1) & 1) << 2)) << 4) + 8 * (p4 & 1);
-  const int vrd = ((4 ^ (((q4 >> 1) & 1) << 2)) - (((q4 >> 1) & 1) << 2)) << 4;  // rd = 1: chunk + 4, swizzled
-  // S^T for keys [c0, c0 + 64): two 32-key row blocks; lane (query, h) holds
-  // keys 32 rb + 8 g + 4 h + e
-  auto qk = [&](f32x16 (&st)[2], int c0) {
-#pragma unroll
-    for (int rb = 0; rb < 2; ++rb) {
-#pragma unroll
-      for (int e = 0; e < 16; ++e) st[rb][e] = 0.f;
-      const int key = c0 + 32 * rb + col;
-#pragma unroll
-      for (int kk = 0; kk < 4; ++kk) {
-        const v4u kf = *reinterpret_cast<const v4u*>(Ks + key * kAD + 8 * ((2 * kk + h) ^ ((key >> 1) & 7)));
-        st[rb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf8(kf), as_bf8(qf[kk]), st[rb], 0, 0, 0);
-      }
-    }
-  };
-  // online softmax of one chunk's scores and O^T += V^T P^T.  masked: x = s
-  // scale log2e + bias, max and exp2(x - m) on x; unmasked (or an all-valid
-  // chunk): max on the raw scores (scale > 0 commutes with max) and p =
-  // exp2(s c - m c) as one FMA per score
-  auto soft_pv = [&](f32x16 (&st)[2], int c0, auto bias_tag) {
-    constexpr bool bias_chunk = decltype(bias_tag)::value;
-    float mx = -1.0e30f;
-    if constexpr (bias_chunk) {
-#pragma unroll
-      for (int rb = 0; rb < 2; ++rb)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          const f32x4 bb = *reinterpret_cast<const f32x4*>(kb + c0 + 32 * rb + 8 * g + 4 * h);
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            const float x = st[rb][4 * g + e] * sl2 + bb[e];
-            st[rb][4 * g + e] = x;
-            mx = fmaxf(mx, x);
-          }
-        }
-    } else {
-#pragma unroll
-      for (int rb = 0; rb < 2; ++rb)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) mx = fmaxf(mx, st[rb][e]);
-      mx *= sl2;
-    }
-    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-    const float m_new = fmaxf(m_run, mx);
-    const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
-    m_run = m_new;
-    f32x2 ls2 = f32x2{0.f, 0.f};
-    v4u pf[4];  // P^T fragments per 16-key step: keys 16 kk2 + {4h..4h+3, 8+4h..8+4h+3}
-#pragma unroll
-    for (int rb = 0; rb < 2; ++rb)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        float pv[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-          pv[e] = bias_chunk ? __builtin_amdgcn_exp2f(st[rb][4 * g + e] - m_new)
-                             : __builtin_amdgcn_exp2f(__builtin_fmaf(st[rb][4 * g + e], sl2, -m_new));
-        ls2 += f32x2{pv[0], pv[1]} + f32x2{pv[2], pv[3]};
-        const int kk2 = 2 * rb + (g >> 1), half = g & 1;
-        pf[kk2][2 * half] = pack2(pv[0], pv[1]);
-        pf[kk2][2 * half + 1] = pack2(pv[2], pv[3]);
-      }
-    const float ls = ls2[0] + ls2[1];
-    l_part = l_part * alpha + ls;
-#pragma unroll
-    for (int r = 0; r < 2; ++r)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) o[r][e] *= alpha;
-    // O^T += V^T P^T: A = V^T rows (dims 32 rd + col), keys in the permuted
-    // order, read TRANSPOSED from the row-major V image: ds_read_b64_tr_b16
-    // gives lane i of a 16-lane group column i (= its dim) of 4 key rows
-#pragma unroll
-    for (int kk2 = 0; kk2 < 4; ++kk2)
-#pragma unroll
-      for (int rd = 0; rd < 2; ++rd) {
-        const uint8_t* vr = vbase + (c0 + 16 * kk2) * 128 + rd * vrd;
-        const v2u a0 = __builtin_bit_cast(v2u, __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-                                                   (__attribute__((address_space(3))) v4s*)(vr)));
-        const v2u a1 = __builtin_bit_cast(v2u, __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-                                                   (__attribute__((address_space(3))) v4s*)(vr + 8 * 128)));
-        const v4u af = v4u{a0[0], a0[1], a1[0], a1[1]};
-        o[rd] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf8(af), as_bf8(pf[kk2]), o[rd], 0, 0, 0);
-      }
-  };
-  // all-valid chunks first (unmasked math), then the partial ones (masked
-  // math): the online softmax does not depend on the chunk order, and each
-  // loop keeps one compile-time path (a per-chunk branch inside the softmax
-  // cost registers and 10 % on the masked kernel, profiles/r6_k12.md)
-  f32x16 st[2];
-  for (uint32_t f = todo & full; f; f &= f - 1u) {
-    const int c0 = 64 * __builtin_ctz(f);
-    qk(st, c0);
-    soft_pv(st, c0, std::false_type{});
-  }
-  if constexpr (MASKED)
-    for (uint32_t m = todo & ~full; m; m &= m - 1u) {
-      const int c0 = 64 * __builtin_ctz(m);
-      qk(st, c0);
-      soft_pv(st, c0, std::true_type{});
-    }
-  const float inv = 1.0f / (l_part + __shfl_xor(l_part, 32, 64));
-  uint16_t* orow = out + ((size_t)seq * S + q) * HD + head * kAD;
-#pragma unroll
-  for (int rd = 0; rd < 2; ++rd)
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      const int d = 32 * rd + 8 * g + 4 * h;
-      float bv[4] = {0.f, 0.f, 0.f, 0.f};
-      if (qkv_bias) {
-        const v2u b2 = *reinterpret_cast<const v2u*>(qkv_bias + 2 * HD + head * kAD + d);
-        bv[0] = __uint_as_float(b2[0] << 16);
-        bv[1] = __uint_as_float(b2[0] & 0xffff0000u);
-        bv[2] = __uint_as_float(b2[1] << 16);
-        bv[3] = __uint_as_float(b2[1] & 0xffff0000u);
-      }
-      *reinterpret_cast<v2u*>(orow + d) = v2u{pack2(o[rd][4 * g] * inv + bv[0], o[rd][4 * g + 1] * inv + bv[1]),
-                                             pack2(o[rd][4 * g + 2] * inv + bv[2], o[rd][4 * g + 3] * inv + bv[3])};
-    }
+  const int* const mask = nullptr;                     // a key's validity is k < len
+  const int S = 64 * ((row_len[row] + 63) >> 6);       // keys staged
+#define TC_ATTN_ROW_GEOMETRY const int head = blockIdx.x % heads, len = row_len[row];
+#define TC_ATTN_ROW_TOK0 ((size_t)first)
+#include "kernels/bert_attention_row.h"
+#undef TC_ATTN_ROW_GEOMETRY
+#undef TC_ATTN_ROW_TOK0
 }
 
 // bf16x3 operand of the fp32-parity bert mode: x fp32 [rows][K] -> out bf16
@@ -890,6 +683,12 @@ int tcamd_attention_plan(int seqs, int S, int heads, int* splits, int* waves) {
   return hipSuccess;
 }
 
+// K12v's launch plan, fixed per (rows, heads) so a graph can capture it: K12's
+// at S = 384 (a row may be that long).  Host only.
+int tcamd_attention_packed_plan(int rows, int heads, int* splits, int* waves) {
+  return tcamd_attention_plan(rows, kAMaxS, heads, splits, waves);
+}
+
 // K12x's launch plan: *waves = 8 (128 queries per block: half the K / V
 // staging per query; bs64 x 384: 331 -> 248 us) once that still gives every
 // CU a block, else 4 (bs1 keeps 64 queries: 20.5 vs 21.2 us;
@@ -933,6 +732,33 @@ int tcamd_attention_bias(const void* qkv, const void* qkv_bias, const int* mask,
   else
     hipLaunchKernelGGL(attention_kernel<false>, grid, block, lds, (hipStream_t)stream, (const uint16_t*)qkv, mask,
                        (uint16_t*)out, S, heads, scale, (const uint16_t*)qkv_bias);
+  return hipGetLastError();
+}
+
+// K12v: K12 over packed rows.  qkv [t_cap][3 * heads * 64] bf16, row r's tokens
+// at cu[r] .. cu[r] + row_len[r] - 1 (row_len / cu int32 on the device, from
+// tcamd_bert_pack_plan; row_len <= 384) -> out [t_cap][heads * 64] bf16, of
+// which only the rows' own tokens are written.  qkv_bias as K12's, or null.
+// rows <= 128; pointers 16-B aligned.
+int tcamd_attention_packed(const void* qkv, const void* qkv_bias, const int* row_len, const int* cu, void* out, int rows,
+                           int t_cap, int heads, float scale, void* stream) {
+  if (rows <= 0 || t_cap <= 0) return hipSuccess;
+  if (!qkv || !out || !row_len || !cu || rows > 128 || heads <= 0 ||
+      ((uintptr_t)qkv | (uintptr_t)out | (uintptr_t)qkv_bias) % 16 || ((uintptr_t)row_len | (uintptr_t)cu) % 4)
+    return hipErrorInvalidValue;
+  const size_t lds = (size_t)kAMaxS * kAD * 2 * 2 + (size_t)kAMaxS * 4;  // as K12 at S = 384
+  static std::atomic<bool> attr{false};
+  if (!attr.load(std::memory_order_acquire)) {
+    const hipError_t e = hipFuncSetAttribute((const void*)attention_packed_kernel,
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    if (e != hipSuccess) return e;
+    attr.store(true, std::memory_order_release);
+  }
+  int splits = 1, qw = kAMaxS / 32;
+  if (const int e = tcamd_attention_packed_plan(rows, heads, &splits, &qw)) return e;
+  hipLaunchKernelGGL(attention_packed_kernel, dim3(rows * heads, splits), dim3(64 * qw), lds, (hipStream_t)stream,
+                     (const uint16_t*)qkv, row_len, cu, (uint16_t*)out, t_cap, heads, scale,
+                     (const uint16_t*)qkv_bias);
   return hipGetLastError();
 }
 

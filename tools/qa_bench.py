@@ -35,6 +35,10 @@ K28 ``wordpiece_tokenize`` alone (its ten launches between two events) at 1, 8
 and 128 rows of such texts and at 128 rows of 64 KB contexts, next to the host
 twin on one core and, where it is installed, ``tokenizers``' ``encode_batch``.
 
+``--text --bert-packed``: ``bert_qa_text_ensemble`` against a server started
+with ``TCAMD_BERT_PACKED=0`` and one with ``=1`` (the padding-free bert_large
+route), loaded in turn ``--reps`` times, contexts of each of ``--packed-contexts`` bytes.
+
 ``--doc-stride N``: the same two for contexts longer than a row.  Served: one
 server with the doc-stride models and ``bert_qa_ensemble``, one document of 40
 and ``--context-bytes`` bytes per request (default 3000: the client's route below
@@ -294,6 +298,77 @@ def text_served(args):
         c.close()
     finally:
         srv.stop()
+
+
+def text_packed_served(args):
+    """``--text --bert-packed``: ``bert_qa_text_ensemble`` against a server with
+    ``TCAMD_BERT_PACKED=0`` and one with ``=1``, loaded in turn ``--reps`` times;
+    the same closed loops against each.  Every request carries the same rows, so
+    the route of a batch follows from the rule alone (``BertLarge.packed_bucket``
+    on the twin tokenizer's mask) and is printed with each line; bert_large's
+    own statistics give its batches, rows and the mean compute_input (where the
+    token count and its sync land) and compute_infer per batch."""
+    import numpy as np
+
+    import tritonclient.grpc as grpcclient
+    from tests import wordpiece_cases as wc
+    from triton_client_amd.perf.harness import ServerProcess
+    from triton_client_amd.server.gpu_models import BertLarge
+    from triton_client_amd.utils import wordpiece
+
+    twin_vocab = wc.TwinVocab(wordpiece.default_vocab_path())
+    text_out = ["spans", "scores", "null_score", "offsets", "overflow"]
+    points = []  # per context size: (bytes, tokens per request, route per requests in a batch, inputs)
+    for ctx in args.packed_contexts:
+        qs, cs = make_texts(args.rows, ctx, 0)
+        _, mask, _, _, _, _ = wc.tokenize_rows(qs, cs, twin_vocab, 64)
+        tokens = int((np.asarray(mask) >= 1).sum())
+        # a batch of n such requests: the route its token count picks
+        routes = {n: BertLarge.packed_bucket(n * args.rows, n * tokens) for n in (1, 2, 4, 8)
+                  if n * args.rows <= BertLarge.max_batch_size}
+        ins = []
+        for name, col in (("question", qs), ("context", cs)):
+            x = grpcclient.InferInput(name, [args.rows, 1], "BYTES")
+            x.set_data_from_numpy(np.array(col, dtype=object).reshape(-1, 1))
+            ins.append(x)
+        points.append((ctx, tokens, {k: ("padded" if v is None else "packed-%d" % v[1]) for k, v in routes.items()},
+                       ins))
+
+    def bert_stats(c):
+        st = c.get_inference_statistics("bert_large", as_json=True)["model_stats"][0]
+        inf = {k: st.get("inference_stats", {}).get(k, {}) for k in ("compute_input", "compute_infer")}
+        return {"executions": int(st.get("execution_count", 0)), "rows": int(st.get("inference_count", 0)),
+                "compute_input_ns": int(inf["compute_input"].get("ns", 0)),
+                "compute_infer_ns": int(inf["compute_infer"].get("ns", 0))}
+
+    for rep in range(args.reps):
+        for knob in (0, 1):
+            log = os.path.abspath(args.server_log) + ".packed%d" % knob if args.server_log else None
+            if log:
+                os.makedirs(os.path.dirname(log), exist_ok=True)
+            srv = ServerProcess(device=0, log_path=log, extra_args=["--native-grpc", args.native_grpc],
+                                models="bert_tokenizer,bert_large,qa_spans,bert_qa_ensemble,bert_qa_text_ensemble",
+                                env={"TCAMD_BERT_PACKED": str(knob)})
+            try:
+                srv.wait_ready(timeout=900, model="bert_qa_text_ensemble")
+                c = grpcclient.InferenceServerClient(srv.grpc_url)
+                for (ctx, tokens, routes, text_ins), conc in ((p, k) for p in points for k in args.concurrency):
+                    s0 = bert_stats(c)
+                    res = closed_loop(c, grpcclient, "bert_qa_text_ensemble", text_ins, text_out, conc, args.warmup,
+                                      args.seconds, lambda result: None)
+                    s1 = bert_stats(c)
+                    ex = max(1, s1["executions"] - s0["executions"])  # the ns sums grow once per batch
+                    res.update(mode="text", bert_packed=knob, rep=rep, rows_per_request=args.rows, context_bytes=ctx,
+                               tokens_per_request=tokens, route_by_requests_per_batch=routes,
+                               bert_batches=s1["executions"] - s0["executions"],
+                               bert_rows_per_batch=round((s1["rows"] - s0["rows"]) / ex, 2),
+                               bert_compute_input_us=round((s1["compute_input_ns"] - s0["compute_input_ns"]) / ex / 1e3, 1),
+                               bert_compute_infer_us=round((s1["compute_infer_ns"] - s0["compute_infer_ns"]) / ex / 1e3, 1),
+                               native_grpc=args.native_grpc)
+                    print(json.dumps(res), flush=True)
+                c.close()
+            finally:
+                srv.stop()
 
 
 def _event_times(torch, launch, iters, warm=5):
@@ -628,6 +703,11 @@ def main():
                     help="the doc-stride route: K28w, K29 / bert_qa_doc_ensemble at this stride (see above)")
     ap.add_argument("--context-bytes", type=int, default=None,
                     help="--doc-stride: bytes of the context (default 4096 with --kernel, else 3000)")
+    ap.add_argument("--packed-contexts", type=int, nargs="+", default=[300, 600, 1500], metavar="BYTES",
+                    help="--text --bert-packed: the context sizes, each looped at every concurrency on every server "
+                         "(with the demonstration vocabulary 105, 205 and 384 tokens a row: fill 128, fill 256, padded)")
+    ap.add_argument("--bert-packed", action="store_true",
+                    help="--text: the text ensemble against a TCAMD_BERT_PACKED=0 and a =1 server, loaded in turn")
     ap.add_argument("--iters", type=int, default=200, help="--kernel: timed launches per point (after 10 warm-up)")
     ap.add_argument("--concurrency", type=int, nargs="+", default=[1, 8])
     ap.add_argument("--rows", type=int, default=1, help="rows per request")
@@ -643,6 +723,8 @@ def main():
         if args.context_bytes is None:
             args.context_bytes = 4096 if args.kernel else 3000
         doc_kernel_time(args.iters, args.doc_stride, args.context_bytes) if args.kernel else doc_served(args)
+    elif args.text and args.bert_packed:
+        text_packed_served(args)
     elif args.text:
         text_kernel_time(args.iters) if args.kernel else text_served(args)
     elif args.kernel:

@@ -20,6 +20,16 @@ in the FFN-up GEMM's epilogue and every
 residual add + LayerNorm as ONE hand-written HIP kernel (K11,
 csrc/kernels/bert.hip), as is the embedding sum + LayerNorm.  The serving wrapper captures one HIP graph per
 batch bucket.
+
+Padding-free form (``BertLargeQA.forward_packed``, bf16 model): K30
+(csrc/kernels/bert_pack.hip) plans where each token with attention_mask >= 1
+goes, the packed embedding LayerNorm gathers those tokens into one dense
+[t_cap, hidden] list, the 24 layers run over it -- the projections,
+LayerNorms, GELU and the QA head are per-token operators, so they only see
+fewer tokens; attention is K12v, K12 over rows of different lengths -- and
+the unpack scatters the logits back to [b, s], PAD_LOGIT where the mask is
+below 1.  The work falls with the fill of the rows instead of staying at
+b x 384.
 """
 
 import math
@@ -36,6 +46,7 @@ HEADS = 16
 FFN = 4096
 MAX_POS = 512
 TYPES = 2
+PAD_LOGIT = -10000.0  # a packed forward's logit where attention_mask < 1: the additive mask constant
 
 
 # fused paths on the GPU (bf16 CUDA tensors); TC_BERT_FUSED=0 runs plain torch ops
@@ -418,6 +429,86 @@ def _attention(qkv, b, s, mask_i32, bias, qkv_bias=None, x3_out=False):
     return a.transpose(1, 2).reshape(b, s, HIDDEN)
 
 
+class PackPlan:
+    """Where the tokens of a [b, s] batch go in a packed forward: int32
+    ``row_len`` [b], ``cu`` [b + 1] (exclusive scan; cu[b] = T, the token
+    count), ``tok_src`` [t_cap] (b * s index of packed token t, -1 for a pad
+    token) and ``tok_of`` [b * s] (packed token of a position, or -1)."""
+
+    def __init__(self, b, s, t_cap, row_len, cu, tok_src, tok_of):
+        self.b, self.s, self.t_cap = b, s, t_cap
+        self.row_len, self.cu, self.tok_src, self.tok_of = row_len, cu, tok_src, tok_of
+
+
+def _packed_ok(w, s):
+    """The HIP form of the packed forward takes this model: bf16 on the GPU, s <= 384."""
+    if not (FUSED and w.is_cuda and w.dtype == torch.bfloat16):
+        return False
+    from triton_client_amd.ops import hip
+
+    return s <= hip.ATTENTION_MAX_SEQ
+
+
+def pack_plan(attention_mask, t_cap, fused):
+    """The PackPlan of ``attention_mask`` [b, s] (valid = mask >= 1; any mask,
+    not only a prefix): K30 on the GPU (no host sync: the caller guarantees
+    T <= t_cap, tokens past t_cap would be dropped and answer PAD_LOGIT),
+    torch ops elsewhere (which raise when T > t_cap)."""
+    b, s = attention_mask.shape
+    dev = attention_mask.device
+    if fused:
+        from triton_client_amd.ops import hip
+
+        if b > hip.BERT_PACK_MAX_ROWS:
+            raise ValueError("a packed forward takes at most %d rows" % hip.BERT_PACK_MAX_ROWS)
+        mask = attention_mask if attention_mask.dtype == torch.int32 else attention_mask.to(torch.int32)
+        if mask.stride(1) != 1:
+            mask = mask.contiguous()
+        row_len = torch.empty(b, device=dev, dtype=torch.int32)
+        cu = torch.empty(b + 1, device=dev, dtype=torch.int32)
+        tok_src = torch.empty(t_cap, device=dev, dtype=torch.int32)
+        tok_of = torch.empty(b * s, device=dev, dtype=torch.int32)
+        hip.bert_pack_plan(mask.data_ptr(), mask.stride(0), b, s, t_cap, row_len.data_ptr(), cu.data_ptr(),
+                           tok_src.data_ptr(), tok_of.data_ptr(), stream=torch.cuda.current_stream(dev).cuda_stream)
+        return PackPlan(b, s, t_cap, row_len, cu, tok_src, tok_of)
+    valid = attention_mask >= 1
+    row_len = valid.sum(1)
+    cu = torch.cat([row_len.new_zeros(1), row_len.cumsum(0)])
+    src = valid.reshape(-1).nonzero().flatten()  # ascending: rows in order, positions ascending
+    T = int(src.numel())
+    if T > t_cap:
+        raise ValueError("%d tokens do not fit t_cap = %d" % (T, t_cap))
+    tok_src = torch.full((t_cap,), -1, device=dev, dtype=torch.int64)
+    tok_src[:T] = src
+    tok_of = torch.full((b * s,), -1, device=dev, dtype=torch.int64)
+    tok_of[src] = torch.arange(T, device=dev)
+    return PackPlan(b, s, t_cap, row_len, cu, tok_src, tok_of)
+
+
+def _attention_packed(qkv, plan, qkv_bias=None):
+    """Attention over the packed QKV projection [1, t_cap, 3H], every row
+    within its own tokens: K12v on the GPU (``qkv`` computed without its bias,
+    which the kernel applies; the pad tokens of the result are never written),
+    SDPA row by row elsewhere (``qkv`` with its bias; pad tokens zero)."""
+    t_cap = qkv.shape[1]
+    if qkv_bias is not None:
+        from triton_client_amd.ops import hip
+
+        out = torch.empty(1, t_cap, HIDDEN, device=qkv.device, dtype=qkv.dtype)
+        hip.attention_packed(qkv.data_ptr(), plan.row_len.data_ptr(), plan.cu.data_ptr(), out.data_ptr(), plan.b, t_cap,
+                             HEADS, 1.0 / math.sqrt(HIDDEN // HEADS), bias=qkv_bias.data_ptr(),
+                             stream=torch.cuda.current_stream(qkv.device).cuda_stream)
+        return out
+    out = qkv.new_zeros(1, t_cap, HIDDEN)
+    cu = plan.cu.tolist()
+    for r in range(plan.b):
+        t0, t1 = cu[r], cu[r + 1]
+        if t1 > t0:
+            q, k, v = qkv[0, t0:t1].view(t1 - t0, 3, HEADS, HIDDEN // HEADS).permute(1, 2, 0, 3)
+            out[0, t0:t1] = F.scaled_dot_product_attention(q, k, v).transpose(0, 1).reshape(t1 - t0, HIDDEN)
+    return out
+
+
 def _qa_head(x, qa):
     """(start, end) fp32 logits [b, s]: the QA head kernel (csrc/kernels/bert.hip qa_head) on the GPU
     (one launch instead of an N = 2 library GEMM, a cast and two strided
@@ -448,9 +539,16 @@ class _Layer(nn.Module):
         self.ffn2 = nn.Linear(FFN, HIDDEN)
         self.ln2 = nn.LayerNorm(HIDDEN, eps=1e-12)
 
-    def forward(self, x, bias, mask_i32=None):
+    def forward(self, x, bias, mask_i32=None, packed=None):
+        """packed (a PackPlan): x is the packed token list [1, t_cap, H] and
+        attention stays within each row's own tokens."""
         b, s, _ = x.shape
-        if _k12_ok(x, s):
+        if packed is not None:
+            if _packed_ok(x, packed.s) and x.is_contiguous():
+                a = _attention_packed(_proj(x, self.qkv, "none", name="qkv"), packed, qkv_bias=self.qkv.bias)
+            else:
+                a = _attention_packed(_proj(x, self.qkv, name="qkv"), packed)
+        elif _k12_ok(x, s):
             # plain GEMM (no bias epilogue: 152 vs 171 us at bs64 x 384,
             # profiles/r3_bert_gemm_layout.log); K12 applies the bias
             qkv = _proj(x, self.qkv, "none", name="qkv")
@@ -491,6 +589,65 @@ class BertLargeQA(nn.Module):
             return out
         pos = torch.arange(s, device=input_ids.device)
         return self.ln(self.word(input_ids) + self.pos(pos)[None] + self.tok_type(token_type_ids))
+
+    def _embed_packed(self, input_ids, token_type_ids, plan, fused):
+        """The embedding LayerNorm of the plan's tokens -> [1, t_cap, H]: one HIP
+        launch straight from the int32 inputs (ids wrapped by remainder(VOCAB),
+        types clamped to [0, 1], as the served model applies them; a pad token
+        is id 0, position 0, type 0), a torch gather elsewhere."""
+        w = self.word.weight
+        if fused:
+            from triton_client_amd.ops import hip
+
+            ids = input_ids.to(torch.int32).contiguous()
+            tt = token_type_ids.to(torch.int32).contiguous()
+            out = torch.empty(1, plan.t_cap, HIDDEN, device=w.device, dtype=w.dtype)
+            hip.embed_layernorm_packed(ids.data_ptr(), tt.data_ptr(), plan.tok_src.data_ptr(), w.data_ptr(),
+                                       self.pos.weight.data_ptr(), self.tok_type.weight.data_ptr(),
+                                       self.ln.weight.data_ptr(), self.ln.bias.data_ptr(), out.data_ptr(), plan.t_cap,
+                                       plan.b * plan.s, plan.s, HIDDEN, VOCAB, TYPES, self.ln.eps,
+                                       stream=torch.cuda.current_stream(w.device).cuda_stream)
+            return out
+        src = plan.tok_src.clamp(min=0)
+        real = plan.tok_src >= 0
+        zero = torch.zeros_like(src)
+        ids = torch.where(real, input_ids.reshape(-1).long().remainder(VOCAB)[src], zero)
+        tt = torch.where(real, token_type_ids.reshape(-1).long().clamp(0, TYPES - 1)[src], zero)
+        pos = torch.where(real, src % plan.s, zero)
+        return self.ln(self.word(ids) + self.pos(pos) + self.tok_type(tt))[None]
+
+    def forward_packed(self, input_ids, attention_mask, token_type_ids, t_cap):
+        """The padding-free forward: (start, end) fp32 [b, s], equal to
+        ``forward`` at every position with attention_mask >= 1 (a padded key's
+        exp(-10000) is exactly 0 in fp32) and PAD_LOGIT everywhere else.  Only
+        the valid tokens are computed, packed into ``t_cap`` token slots: plan
+        (K30) -> packed embedding LayerNorm -> the layers over [1, t_cap, H]
+        with K12v attention -> QA head over t_cap tokens -> unpack.  ``t_cap``
+        must hold every valid token; the HIP form does not check it (no host
+        sync, so a graph can capture it).  ids wrap by remainder(VOCAB) and
+        types clamp to [0, 1], as the served model applies them.  HIP kernels
+        on the GPU in bf16, plain torch ops (gather, SDPA per row, scatter)
+        off the GPU, in another dtype or with TC_BERT_FUSED=0."""
+        b, s = input_ids.shape
+        t_cap = int(t_cap)
+        fused = _packed_ok(self.word.weight, s) and input_ids.is_cuda
+        plan = pack_plan(attention_mask, t_cap, fused)
+        x = self._embed_packed(input_ids, token_type_ids, plan, fused)
+        for layer in self.layers:
+            x = layer(x, None, packed=plan)
+        st, en = _qa_head(x, self.qa)  # [1, t_cap]
+        if fused:
+            from triton_client_amd.ops import hip
+
+            out = torch.empty(2, b, s, device=x.device, dtype=torch.float32)
+            hip.unpack_logits(st.data_ptr(), en.data_ptr(), plan.tok_of.data_ptr(), out[0].data_ptr(), out[1].data_ptr(),
+                              b * s, t_cap, stream=torch.cuda.current_stream(x.device).cuda_stream)
+            return out[0], out[1]
+        real = plan.tok_of >= 0
+        at = plan.tok_of.clamp(min=0)
+        pad = st.new_full((), PAD_LOGIT)
+        return (torch.where(real, st.reshape(-1)[at], pad).view(b, s),
+                torch.where(real, en.reshape(-1)[at], pad).view(b, s))
 
     def forward(self, input_ids, attention_mask, token_type_ids, dense=False):
         """dense=True: the caller guarantees attention_mask is all ones, so

@@ -457,6 +457,32 @@ _SIGS = {
     "tcamd_attention_f32_plan": (
         [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int)], ctypes.c_int,
     ),
+    # padding-free bert_large: K30 pack plan / packed embed / unpack (csrc/kernels/bert_pack.hip), K12v
+    "tcamd_bert_pad_logit": ([], ctypes.c_float),
+    "tcamd_bert_pack_plan": (
+        [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
+         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p],
+        ctypes.c_int,
+    ),
+    "tcamd_embed_layernorm_packed": (
+        [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+         ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_void_p],
+        ctypes.c_int,
+    ),
+    "tcamd_unpack_logits": (
+        [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
+         ctypes.c_int, ctypes.c_void_p],
+        ctypes.c_int,
+    ),
+    "tcamd_attention_packed": (
+        [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
+         ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_void_p],
+        ctypes.c_int,
+    ),
+    "tcamd_attention_packed_plan": (
+        [ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)], ctypes.c_int,
+    ),
     # native batch executor for pointer-table graph models (csrc/runtime/graph_exec.hip)
     "tcamd_pgx_create": (
         [ctypes.c_int32, ctypes.c_int32, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int32,
@@ -1216,6 +1242,61 @@ def attention_f32_plan(seqs, S, heads):
     w = ctypes.c_int(0)
     _check(_load().tcamd_attention_f32_plan(int(seqs), int(S), int(heads), ctypes.byref(w)), "attention_f32_plan")
     return w.value
+
+
+# The logit a packed bert_large forward leaves where attention_mask < 1: the
+# model's own additive mask constant (tcamd_bert_pad_logit, csrc/kernels/bert_pack.hip).
+BERT_PAD_LOGIT = -10000.0
+BERT_PACK_MAX_ROWS = 128
+
+
+def bert_pack_plan(mask, mask_stride, rows, S, t_cap, row_len, cu, tok_src, tok_of, stream=None):
+    """K30: the pack plan of a padding-free BERT forward.  ``mask`` int32
+    [rows][S] at a row stride of ``mask_stride`` elements (any mask; valid =
+    mask >= 1), rows <= 128, S <= 384 -> int32 device arrays ``row_len`` [rows],
+    ``cu`` [rows + 1] (exclusive scan, cu[rows] = T), ``tok_src`` [t_cap]
+    (r * S + p of packed token t, rows in order and positions ascending; -1 for
+    T <= t < t_cap) and ``tok_of`` [rows * S] (the packed token of (r, p), or
+    -1).  With T > t_cap nothing past t_cap is written and cu[rows] still holds
+    the true T: the caller checks it."""
+    _check(_load().tcamd_bert_pack_plan(mask, int(mask_stride), int(rows), int(S), int(t_cap), row_len, cu, tok_src,
+                                        tok_of, _vp(stream)), "bert_pack_plan")
+
+
+def embed_layernorm_packed(ids, types, tok_src, word, pos, type_, gamma, beta, out, t_cap, n_src, S, H, vocab, ntypes,
+                           eps, stream=None):
+    """BERT embeddings of the packed tokens: out [t_cap][H] bf16, token t from
+    the int32 request tensors ``ids`` / ``types`` [n_src] at ``tok_src[t]``
+    (ids wrap by remainder(vocab), types clamp to [0, ntypes - 1], position =
+    src % S); a pad token (tok_src = -1) is id 0, position 0, type 0.  A real
+    token has the bits ``embed_layernorm`` gives its (row, position)."""
+    _check(_load().tcamd_embed_layernorm_packed(ids, types, tok_src, word, pos, type_, gamma, beta, out, int(t_cap),
+                                                int(n_src), int(S), int(H), int(vocab), int(ntypes), float(eps),
+                                                _vp(stream)), "embed_layernorm_packed")
+
+
+def unpack_logits(packed_start, packed_end, tok_of, out_start, out_end, n, t_cap, stream=None):
+    """out_start / out_end fp32 [n] (n = rows * S): the packed logits of the
+    tokens ``tok_of`` names, BERT_PAD_LOGIT elsewhere, both planes in one launch."""
+    _check(_load().tcamd_unpack_logits(packed_start, packed_end, tok_of, out_start, out_end, int(n), int(t_cap),
+                                       _vp(stream)), "unpack_logits")
+
+
+def attention_packed(qkv, row_len, cu, out, rows, t_cap, heads, scale, stream=None, bias=None):
+    """K12v: K12 over packed rows.  ``qkv`` [t_cap][3*heads*64] bf16 holds row
+    r's tokens at cu[r] .. cu[r] + row_len[r] - 1 (int32 device arrays from
+    ``bert_pack_plan``; row_len <= ATTENTION_MAX_SEQ); ``out`` [t_cap][heads*64]
+    bf16, of which only the rows' own tokens are written.  ``bias`` as K12's."""
+    _check(_load().tcamd_attention_packed(qkv, _vp(bias), row_len, cu, out, int(rows), int(t_cap), int(heads),
+                                          float(scale), _vp(stream)), "attention_packed")
+
+
+def attention_packed_plan(rows, heads):
+    """(splits, waves) of K12v's launch, fixed per (rows, heads): K12's plan at S = 384.  Host only."""
+    sp, w = ctypes.c_int(0), ctypes.c_int(0)
+    _check(_load().tcamd_attention_packed_plan(int(rows), int(heads), ctypes.byref(sp), ctypes.byref(w)),
+           "attention_packed_plan")
+    return sp.value, w.value
 
 
 def x3_conv1x1_ws_bytes(M, K, N=128):

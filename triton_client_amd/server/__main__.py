@@ -43,9 +43,14 @@ def main(argv=None):
     ap.add_argument("--bert-vocab", default="",
                     help="vocab.txt of the bert_tokenizer model (one piece per line; handed down as "
                          "TCAMD_BERT_VOCAB); default: the demonstration vocabulary that ships with the package")
+    ap.add_argument("--bert-packed", action="store_true",
+                    help="bert_large: also capture the padding-free graphs and serve every batch whose valid tokens "
+                         "fit one of them over those tokens alone (handed down as TCAMD_BERT_PACKED=1)")
     args = ap.parse_args(argv)
     if args.bert_vocab:
         os.environ["TCAMD_BERT_VOCAB"] = os.path.abspath(args.bert_vocab)
+    if args.bert_packed:
+        os.environ["TCAMD_BERT_PACKED"] = "1"
     if args.hw_queues > 0:
         # before anything initialises HIP in this process.  The GPU boxes
         # export GPU_MAX_HW_QUEUES=4 (HIP's own default) into every job, so a

@@ -681,7 +681,23 @@ class BertLarge(DeviceModel):
     dynamic batching into HIP-graph buckets.  Inputs from device shm are
     gathered with K7 batched_copy (one launch per input tensor), outputs are
     scattered the same way; both the Python scheduler and the native front end
-    (execute_native) use it."""
+    (execute_native) use it.
+
+    ``TCAMD_BERT_PACKED=1`` (read at load; 0 by default) adds the padding-free
+    route: per row bucket ``b`` and fill ``f`` of ``PACKED_FILL`` a second kind
+    of graph that runs ``BertLargeQA.forward_packed`` over ``t_cap = b * f``
+    token slots (K30 plan over the bucket's rows of the slot's mask buffer --
+    the bucket's padding rows are zeroed, hence empty -- the packed embedding,
+    the layers with K12v attention, the unpack).  A batch counts its tokens
+    (mask >= 1: on the host for host-staged parts, one device reduction and
+    ``.item()`` on the slot's stream if a part came from device memory, in
+    place of ``_mask_all_ones``'s own) and ``packed_bucket`` picks the smallest
+    fill that holds them; a batch no fill holds runs the masked or dense padded
+    graph, chosen as without the knob.  On a packed batch the positions with
+    mask below 1 hold ``PAD_LOGIT`` (-10000); no consumer reads them (K27, K29
+    and utils/qa.py all go by the mask).  ``route_counts`` counts the batches
+    per route.  The fp32-parity ``bert_large_fp32`` has no packed attention
+    kernel and keeps the padded route whatever the knob says."""
 
     name = "bert_large"
     platform = "pytorch_libtorch"
@@ -712,11 +728,31 @@ class BertLarge(DeviceModel):
     # unmasked kernel is still 4-8 % faster (78-80 vs 82-87 us,
     # profiles/r6_k12/k12_allones.log), worth the sync.
     DENSE_FROM = 32
+    # the packed route's graphs: t_cap = bucket * fill token slots (a question
+    # plus a paragraph is typically 100-250 of the 384 tokens)
+    PACKED_FILL = (128, 256)
+    supports_packed = True
 
     def __init__(self, version=1, device_id=0, use_graphs=True, layers=24, **kw):
         super().__init__(version, device_id, **kw)
         self.use_graphs = use_graphs
         self.layers = int(layers)
+        self.packed = False
+        self.route_counts = {"packed": 0, "padded": 0}
+
+    @classmethod
+    def packed_bucket(cls, total_rows, tokens):
+        """(row bucket, fill) of the packed graph that serves ``total_rows`` rows
+        holding ``tokens`` valid tokens: the rows' bucket and the smallest fill
+        of PACKED_FILL with tokens <= bucket * fill; None when no fill holds
+        them (the padded graph serves the batch).  Host only."""
+        bucket = next((b for b in cls.BUCKETS if b >= total_rows), None)
+        if bucket is None or total_rows < 1:
+            return None
+        for f in cls.PACKED_FILL:
+            if tokens <= bucket * f:
+                return bucket, f
+        return None
 
     def load(self):
         from triton_client_amd.models import bert
@@ -724,6 +760,8 @@ class BertLarge(DeviceModel):
         torch, _, dev = self._gpu("bert_large requires a GPU")
         torch.cuda.set_device(self.device_id)
         self.model = self._build_model(bert, dev)
+        self.packed = self.supports_packed and os.environ.get("TCAMD_BERT_PACKED", "0") == "1"
+        self.route_counts = {"packed": 0, "padded": 0}
         # before the warm-up runs and graph captures below pick their GEMM solutions
         self.tuned_gemms = bert.use_tuned_gemms()
         for _ in range(max(1, self.instance_count)):
@@ -751,7 +789,15 @@ class BertLarge(DeviceModel):
             slot["outs"][0][:b].copy_(st)
             slot["outs"][1][:b].copy_(en)
 
+        def run_packed(b, fill):
+            ids, mask, tt = (t[:b] for t in slot["ins"])
+            # the kernels wrap the ids and clamp the types themselves; valid = mask >= 1
+            st, en = self.model.forward_packed(ids, mask, tt, b * fill)
+            slot["outs"][0][:b].copy_(st)
+            slot["outs"][1][:b].copy_(en)
+
         slot["run"] = run
+        slot["run_packed"] = run_packed
         # one graph per bucket with the key-padding mask, plus a "dense" one
         # without it from DENSE_FROM rows (no padding in any real row)
         with torch.cuda.stream(slot["stream"]), torch.no_grad():
@@ -763,6 +809,19 @@ class BertLarge(DeviceModel):
                         with torch.cuda.graph(g, stream=slot["stream"]):
                             run(b, dense)
                         slot["graphs"][(b, dense)] = g
+            if self.packed:
+                # captured with an all-empty mask (no row has a token): the
+                # warm-up run and the capture then touch no token at all
+                slot["ins"][1].zero_()
+                for b in self.BUCKETS:
+                    for fill in self.PACKED_FILL:
+                        run_packed(b, fill)
+                        if self.use_graphs:
+                            g = torch.cuda.CUDAGraph()
+                            with torch.cuda.graph(g, stream=slot["stream"]):
+                                run_packed(b, fill)
+                            slot["graphs"][(b, "packed", fill)] = g
+                slot["ins"][1].fill_(1)
         slot["stream"].synchronize()
         return slot
 
@@ -783,6 +842,17 @@ class BertLarge(DeviceModel):
         torch = self.torch
         with torch.cuda.stream(slot["stream"]):
             return not bool((slot["ins"][1][:total] < 1).any().item())
+
+    def _count_tokens(self, slot, parts, total):
+        """The batch's valid tokens (attention_mask >= 1) over its real rows:
+        counted on the host for host-staged parts; if any part came from device
+        memory, one reduction over the staged rows and ``.item()`` on the slot's
+        stream (the sync ``_mask_all_ones`` would otherwise take)."""
+        if any(kind == 1 for kind, _, _ in parts):
+            torch = self.torch
+            with torch.cuda.stream(slot["stream"]):
+                return int((slot["ins"][1][:total] >= 1).sum().item())
+        return sum(int((pinned_view(ptr, np.int32, rows * self.SEQ) >= 1).sum()) for _, ptr, rows in parts)
 
     def _run_batch(self, slot, srcs, outs, total):
         """srcs: per input a list of (kind, ptr, rows) in row order; outs: per
@@ -815,10 +885,23 @@ class BertLarge(DeviceModel):
                 hip.batched_copy(c_src, c_dst, c_n, sh)
             if bucket > total:  # padding rows: keep them deterministic (mask 1, ids 0)
                 hip.memset_async(base + total * row, 0, (bucket - total) * row, sh)
-        dense = bucket >= self.DENSE_FROM and self._mask_all_ones(slot, srcs[1], total)
+        pick = None
+        if self.packed:
+            tokens = self._count_tokens(slot, srcs[1], total)
+            pick = self.packed_bucket(total, tokens)
+            # all ones <=> every position of every real row counted: no second scan or sync
+            dense = pick is None and bucket >= self.DENSE_FROM and tokens == total * self.SEQ
+        else:
+            dense = bucket >= self.DENSE_FROM and self._mask_all_ones(slot, srcs[1], total)
+        self.route_counts["padded" if pick is None else "packed"] += 1
         ev[1].record(stream)
         with self.torch.cuda.stream(stream), self.torch.no_grad():
-            if self.use_graphs:
+            if pick is not None:
+                if self.use_graphs:
+                    slot["graphs"][(bucket, "packed", pick[1])].replay()
+                else:
+                    slot["run_packed"](bucket, pick[1])
+            elif self.use_graphs:
                 slot["graphs"][(bucket, dense)].replay()
             else:
                 slot["run"](bucket, dense)
@@ -942,7 +1025,9 @@ class BertLargeFP32(BertLarge):
     fp32 accumulate), LayerNorm / GELU / softmax attention in fp32.  Served
     logits match an fp32 forward of the fp32 weights to ~1e-5
     (tests/test_bert_accuracy_gpu.py); ~3x the bf16 model's GEMM work.  The
-    bf16 ``bert_large`` stays the config-4 serving default."""
+    bf16 ``bert_large`` stays the config-4 serving default.  It has no
+    padding-free route: K12x has no packed counterpart, so ``TCAMD_BERT_PACKED``
+    does not apply and every batch runs the padded graphs."""
 
     name = "bert_large_fp32"
     # 64 rows, as before bert_large went to 128: a bs128 fp32-parity forward
@@ -951,6 +1036,8 @@ class BertLargeFP32(BertLarge):
     # (profiles/r6_bert_batching/)
     max_batch_size = 64
     BUCKETS = tuple(b for b in BertLarge.BUCKETS if b <= 64)
+    # no packed route: K12x has no counterpart of K12v, so TCAMD_BERT_PACKED leaves this model on the padded graphs
+    supports_packed = False
 
     def _build_model(self, bert, dev):
         import torch

@@ -365,176 +365,64 @@ __device__ __forceinline__ f32x4 mma_x3(v4u ah, v4u al, v4u bh, v4u bl, f32x4 c)
 }
 
 // out3 (or null): write the output as the out-projection's bf16x3 operand,
-// bf16 [tokens][3H] = [hi | hi | lo], instead of fp32 into out
+// bf16 [tokens][3H] = [hi | hi | lo], instead of fp32 into out.
+//
+// The device code is a function of a row geometry, shared by K12x and K12xv
+// (packed rows, below), and lives in kernels/bert_attention_x3_row.h, which
+// says why it is a text and not a function, and why its barriers are
+// workgroup-uniform.  K12x gives it (seq * S, S / 64 chunks) and PACKED =
+// false, which folds every use of ``len`` away; K12xv (cu[r], ceil(len / 64)).
 template <int NW>
 __global__ void __launch_bounds__(64 * NW) attention_x3_kernel(const float* __restrict__ qkv,
                                                                const int* __restrict__ mask, float* __restrict__ out,
                                                                uint16_t* __restrict__ out3, int S, int heads,
                                                                float scale) {
-  extern __shared__ __attribute__((aligned(16))) uint8_t ldsa[];
-  // per buffer: K hi [64 keys][kXR] | K lo | V^T hi [64 d][kXR] | V^T lo | key bias [64]
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int seq = blockIdx.x / heads, h = blockIdx.x - seq * heads;
-  const int H = heads * 64, ld = 3 * H;
-  const float* const base = qkv + (size_t)seq * S * ld + h * 64;
-  const int g = lane >> 4, c = lane & 15;
-  const int q = blockIdx.y * (16 * NW) + wave * 16 + c;  // this lane's query
+  constexpr bool PACKED = false;
+#define TC_ATTN_X3_GEOMETRY const int seq = blockIdx.x / heads, h = blockIdx.x - seq * heads, len = S;
+#define TC_ATTN_X3_TOK0 ((size_t)seq * S)
+#include "kernels/bert_attention_x3_row.h"
+#undef TC_ATTN_X3_GEOMETRY
+#undef TC_ATTN_X3_TOK0
+}
 
-  // Q^T operand, pre-scaled (1/8: exact), d = 32 ks + 8 g .. +8
-  v4u qh[2], ql[2];
-#pragma unroll
-  for (int ks = 0; ks < 2; ++ks) {
-    const float4 a = *reinterpret_cast<const float4*>(base + (size_t)q * ld + 32 * ks + 8 * g);
-    const float4 b = *reinterpret_cast<const float4*>(base + (size_t)q * ld + 32 * ks + 8 * g + 4);
-    uint32_t hh[4], ll[4];
-    split_pk(a.x * scale, a.y * scale, hh[0], ll[0]);
-    split_pk(a.z * scale, a.w * scale, hh[1], ll[1]);
-    split_pk(b.x * scale, b.y * scale, hh[2], ll[2]);
-    split_pk(b.z * scale, b.w * scale, hh[3], ll[3]);
-    qh[ks] = v4u{hh[0], hh[1], hh[2], hh[3]};
-    ql[ks] = v4u{ll[0], ll[1], ll[2], ll[3]};
+// ---- K12xv: K12x over packed rows -------------------------------------------
+// qkv fp32 [t_cap][3 * heads * 64] holds the tokens of rows of different
+// lengths back to back (K30 bert_pack_plan): block (row r, head, query block of
+// 16 NW) attends queries and keys cu[r] .. cu[r] + row_len[r] - 1 and touches
+// no other token, so rows [T, t_cap) of qkv are never read and those of out
+// never written.  It runs ceil(len / 64) chunks, the keys at or past len
+// staged as copies of the row's last token under the -10000 bias: the chunks
+// K12x runs on the same row padded to 384 behind a prefix mask, minus the
+// trailing all-masked ones, which change nothing (corr = exp(0) = 1, p =
+// exp(-10000 - m) = 0), so the valid tokens get K12x's bits.  The grid is
+// fixed per (rows, heads) -- K12x's plan at S = 384 -- so a HIP graph can
+// capture it; an empty row's blocks, a row longer than 384 or one that does
+// not fit t_cap (a caller's error) and a query block starting at or past the
+// row's end return at once, on conditions uniform over the block.  A block
+// that stays keeps all its waves to the end: K12x stages every chunk
+// cooperatively, so each wave reaches each __syncthreads of the chunk loop
+// (kernels/bert_attention_x3_row.h says how waves without a query behave).
+template <int NW>
+__global__ void __launch_bounds__(64 * NW) attention_x3_packed_kernel(const float* __restrict__ qkv,
+                                                                      const int* __restrict__ row_len,
+                                                                      const int* __restrict__ cu,
+                                                                      float* __restrict__ out,
+                                                                      uint16_t* __restrict__ out3, int t_cap, int heads,
+                                                                      float scale) {
+  constexpr bool PACKED = true;
+  constexpr int S = kAMaxS;          // K12x's name; the packed text reads len instead
+  const int* const mask = nullptr;   // a key's validity is k < len
+  const int row = blockIdx.x / heads, first = cu[row];
+  {
+    const int len = row_len[row];
+    if (len <= 0 || len > kAMaxS || first < 0 || first > t_cap - len) return;
+    if ((int)(blockIdx.y * (16 * NW)) >= len) return;
   }
-  f32x4 o[4];
-#pragma unroll
-  for (int dt = 0; dt < 4; ++dt) o[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
-  float m = -INFINITY, l = 0.f;
-
-  // staging of one 64-key chunk, split so that its global loads are in
-  // flight during the previous chunk's math: K row-major (thread -> key, 4
-  // head dims), V transposed (thread -> key pair, 4 head dims: 4-B words of
-  // two keys, a wave's 32 key pairs one contiguous 128-B run per V^T row)
-  constexpr int KIT = 1024 / (64 * NW), VIT = 512 / (64 * NW);
-  float4 kr[KIT], va[VIT], vb[VIT];
-  float mkb = 0.f;
-  auto stage_load = [&](int c0) {
-#pragma unroll
-    for (int it = 0; it < KIT; ++it) {
-      const int i = it * 64 * NW + tid, key = i >> 4, d4 = (i & 15) * 4;
-      kr[it] = *reinterpret_cast<const float4*>(base + (size_t)(c0 + key) * ld + H + d4);
-    }
-#pragma unroll
-    for (int it = 0; it < VIT; ++it) {
-      const int u = it * 64 * NW + tid, kp = u & 31, d4 = (u >> 5) * 4;
-      const float* r0 = base + (size_t)(c0 + 2 * kp) * ld + 2 * H + d4;
-      va[it] = *reinterpret_cast<const float4*>(r0);
-      vb[it] = *reinterpret_cast<const float4*>(r0 + ld);
-    }
-    if (tid < 64) mkb = (mask && mask[seq * S + c0 + tid] == 0) ? -10000.f : 0.f;
-  };
-  auto stage_store = [&](uint8_t* buf) {
-#pragma unroll
-    for (int it = 0; it < KIT; ++it) {
-      const int i = it * 64 * NW + tid, key = i >> 4, d4 = (i & 15) * 4;
-      uint32_t h0, l0, h1, l1;
-      split_pk(kr[it].x, kr[it].y, h0, l0);
-      split_pk(kr[it].z, kr[it].w, h1, l1);
-      *reinterpret_cast<uint2*>(buf + key * kXR + d4 * 2) = make_uint2(h0, h1);
-      *reinterpret_cast<uint2*>(buf + 64 * kXR + key * kXR + d4 * 2) = make_uint2(l0, l1);
-    }
-#pragma unroll
-    for (int it = 0; it < VIT; ++it) {
-      const int u = it * 64 * NW + tid, kp = u & 31, d4 = (u >> 5) * 4;
-      const float a[4] = {va[it].x, va[it].y, va[it].z, va[it].w}, b[4] = {vb[it].x, vb[it].y, vb[it].z, vb[it].w};
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        uint32_t hh, ll;
-        split_pk(a[j], b[j], hh, ll);
-        *reinterpret_cast<uint32_t*>(buf + 128 * kXR + (d4 + j) * kXR + 4 * kp) = hh;
-        *reinterpret_cast<uint32_t*>(buf + 192 * kXR + (d4 + j) * kXR + 4 * kp) = ll;
-      }
-    }
-    if (tid < 64) reinterpret_cast<float*>(buf + 256 * kXR)[tid] = mkb;
-  };
-  stage_load(0);
-  stage_store(ldsa);
-  __syncthreads();
-  const int nch = S / 64;
-  for (int ci = 0; ci < nch; ++ci) {
-    uint8_t* const kh = ldsa + (ci & 1) * kBufAX;  // K lo follows at kh + 64 * kXR
-    uint8_t* const vth = kh + 128 * kXR;
-    uint8_t* const vtl = kh + 192 * kXR;
-    const float* const kb = reinterpret_cast<const float*>(kh + 256 * kXR);
-    if (ci + 1 < nch) stage_load(64 * (ci + 1));
-
-    // S^T tiles [16 keys][16 queries]
-    f32x4 st[4];
-    float mx = m;
-#pragma unroll
-    for (int kt = 0; kt < 4; ++kt) {
-      st[kt] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks) {
-        const uint8_t* ar = kh + (kt * 16 + c) * kXR + (32 * ks + 8 * g) * 2;
-        st[kt] = mma_x3(*reinterpret_cast<const v4u*>(ar), *reinterpret_cast<const v4u*>(ar + 64 * kXR), qh[ks],
-                        ql[ks], st[kt]);
-      }
-      const f32x4 kbv = *reinterpret_cast<const f32x4*>(kb + kt * 16 + 4 * g);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        st[kt][e] += kbv[e];
-        mx = fmaxf(mx, st[kt][e]);
-      }
-    }
-    mx = fmaxf(mx, __shfl_xor(mx, 16));
-    mx = fmaxf(mx, __shfl_xor(mx, 32));
-    const float corr = __expf(m - mx);
-    float sum = 0.f;
-#pragma unroll
-    for (int kt = 0; kt < 4; ++kt)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        st[kt][e] = __expf(st[kt][e] - mx);
-        sum += st[kt][e];
-      }
-    sum += __shfl_xor(sum, 16);
-    sum += __shfl_xor(sum, 32);
-    l = l * corr + sum;
-    m = mx;
-#pragma unroll
-    for (int dt = 0; dt < 4; ++dt) o[dt] *= corr;
-    // O^T += V^T P^T over the chunk's two 32-key steps
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      uint32_t ph[4], pl[4];
-      split_pk(st[2 * ks][0], st[2 * ks][1], ph[0], pl[0]);
-      split_pk(st[2 * ks][2], st[2 * ks][3], ph[1], pl[1]);
-      split_pk(st[2 * ks + 1][0], st[2 * ks + 1][1], ph[2], pl[2]);
-      split_pk(st[2 * ks + 1][2], st[2 * ks + 1][3], ph[3], pl[3]);
-      const v4u pbh = v4u{ph[0], ph[1], ph[2], ph[3]}, pbl = v4u{pl[0], pl[1], pl[2], pl[3]};
-#pragma unroll
-      for (int dt = 0; dt < 4; ++dt) {
-        const int off = (dt * 16 + c) * kXR + (ks * 32 + 4 * g) * 2;
-        const uint2 a0 = *reinterpret_cast<const uint2*>(vth + off), a1 = *reinterpret_cast<const uint2*>(vth + off + 32);
-        const uint2 b0 = *reinterpret_cast<const uint2*>(vtl + off), b1 = *reinterpret_cast<const uint2*>(vtl + off + 32);
-        o[dt] = mma_x3(v4u{a0.x, a0.y, a1.x, a1.y}, v4u{b0.x, b0.y, b1.x, b1.y}, pbh, pbl, o[dt]);
-      }
-    }
-    // chunk ci + 1 into the other buffer (read last in iteration ci - 1, which
-    // every wave left behind the previous barrier)
-    if (ci + 1 < nch) stage_store(ldsa + ((ci + 1) & 1) * kBufAX);
-    __syncthreads();
-  }
-  const float inv = 1.f / l;
-  if (out3) {
-    uint16_t* const op = out3 + ((size_t)seq * S + q) * 3 * H + h * 64 + 4 * g;
-#pragma unroll
-    for (int dt = 0; dt < 4; ++dt) {
-      f32x4 r = o[dt] * inv;
-      // the rounded product (hipcc would contract r - hi into fma(o, inv, -hi)):
-      // the operand is then bitwise x3_cat of the fp32 output
-      asm volatile("" : "+v"(r));
-      uint32_t h0, l0, h1, l1;
-      split_pk(r[0], r[1], h0, l0);
-      split_pk(r[2], r[3], h1, l1);
-      *reinterpret_cast<uint2*>(op + dt * 16) = make_uint2(h0, h1);
-      *reinterpret_cast<uint2*>(op + H + dt * 16) = make_uint2(h0, h1);
-      *reinterpret_cast<uint2*>(op + 2 * H + dt * 16) = make_uint2(l0, l1);
-    }
-    return;
-  }
-  float* const op = out + ((size_t)seq * S + q) * H + h * 64 + 4 * g;
-#pragma unroll
-  for (int dt = 0; dt < 4; ++dt) *reinterpret_cast<f32x4*>(op + dt * 16) = o[dt] * inv;
+#define TC_ATTN_X3_GEOMETRY const int seq = row, h = blockIdx.x - seq * heads, len = row_len[row];
+#define TC_ATTN_X3_TOK0 ((size_t)first)
+#include "kernels/bert_attention_x3_row.h"
+#undef TC_ATTN_X3_GEOMETRY
+#undef TC_ATTN_X3_TOK0
 }
 
 }  // namespace
@@ -789,6 +677,45 @@ int tcamd_attention_f32(const float* qkv, const int* mask, void* out, int seqs, 
   else
     hipLaunchKernelGGL(attention_x3_kernel<4>, dim3(seqs * heads, S / 64), dim3(256), kLdsAX, (hipStream_t)stream,
                        qkv, mask, o32, o3, S, heads, scale);
+  return hipGetLastError();
+}
+
+// K12xv's launch plan, fixed per (rows, heads) so a graph can capture it:
+// K12x's at S = 384 (a row may be that long).  Host only.
+int tcamd_attention_f32_packed_plan(int rows, int heads, int* waves) {
+  return tcamd_attention_f32_plan(rows, kAMaxS, heads, waves);
+}
+
+// K12xv: K12x over packed rows.  qkv [t_cap][3 * heads * 64] fp32 (bias
+// included), row r's tokens at cu[r] .. cu[r] + row_len[r] - 1 (row_len / cu
+// int32 on the device, from tcamd_bert_pack_plan; row_len <= 384) -> out
+// [t_cap][heads * 64] fp32 or, with x3, the out-projection's bf16x3 operand,
+// bf16 [t_cap][3 * heads * 64]; only the rows' own tokens are written.
+// rows <= 128; qkv / out 16-B aligned.
+int tcamd_attention_f32_packed(const float* qkv, const int* row_len, const int* cu, void* out, int rows, int t_cap,
+                               int heads, float scale, int x3, void* stream) {
+  if (rows <= 0 || t_cap <= 0) return hipSuccess;
+  if (!qkv || !out || !row_len || !cu || rows > 128 || heads <= 0 || ((uintptr_t)qkv | (uintptr_t)out) % 16 ||
+      ((uintptr_t)row_len | (uintptr_t)cu) % 4)
+    return hipErrorInvalidValue;
+  float* const o32 = x3 ? nullptr : (float*)out;
+  uint16_t* const o3 = x3 ? (uint16_t*)out : nullptr;
+  static std::atomic<bool> attr{false};  // its own flag: these are other functions than K12x's
+  if (!attr.load(std::memory_order_acquire)) {
+    for (const void* fn : {(const void*)attention_x3_packed_kernel<4>, (const void*)attention_x3_packed_kernel<8>}) {
+      const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsAX);
+      if (e != hipSuccess) return e;
+    }
+    attr.store(true, std::memory_order_release);
+  }
+  int waves = 4;
+  if (const int e = tcamd_attention_f32_packed_plan(rows, heads, &waves)) return e;
+  if (waves == 8)
+    hipLaunchKernelGGL(attention_x3_packed_kernel<8>, dim3(rows * heads, kAMaxS / 128), dim3(512), kLdsAX,
+                       (hipStream_t)stream, qkv, row_len, cu, o32, o3, t_cap, heads, scale);
+  else
+    hipLaunchKernelGGL(attention_x3_packed_kernel<4>, dim3(rows * heads, kAMaxS / 64), dim3(256), kLdsAX,
+                       (hipStream_t)stream, qkv, row_len, cu, o32, o3, t_cap, heads, scale);
   return hipGetLastError();
 }
 

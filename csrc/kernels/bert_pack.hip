@@ -23,7 +23,10 @@
 //                           (src = -1) is id 0, position 0, type 0, so it is
 //                           finite.  The bits of embed_layernorm for the same
 //                           (row, position): the same sum, the same
-//                           ln_store_row (kernels/bert_ln.h).
+//                           ln_store_row (kernels/bert_ln.h).  An fp32 form
+//                           for the fp32-parity model: fp32 tables and
+//                           output, optionally also the first QKV
+//                           projection's bf16x3 operand.
 //   unpack_logits           out[r][p] = tok_of >= 0 ? packed[tok_of] :
 //                           PAD_LOGIT for both logit planes in one launch.
 // Reference analog: none (the reference client runs no model).
@@ -131,6 +134,48 @@ __global__ void __launch_bounds__(256) embed_layernorm_packed_kernel(
   ln_store_row<E>(v, gamma, beta, out + (size_t)t * H, lane, eps);
 }
 
+// The fp32-parity model's form: fp32 tables, the fp32 sum in the bf16 kernel's
+// order, ln_store_row's fp32 form; out3 (or null) is the first QKV
+// projection's bf16x3 operand [t_cap][3H], so the packed graph runs no x3_cat.
+template <int E>
+__global__ void __launch_bounds__(256) embed_layernorm_packed_f32_kernel(
+    const int* __restrict__ ids, const int* __restrict__ types, const int* __restrict__ tok_src,
+    const float* __restrict__ word, const float* __restrict__ pos, const float* __restrict__ tok,
+    const float* __restrict__ gamma, const float* __restrict__ beta, float* __restrict__ out,
+    uint16_t* __restrict__ out3, int t_cap, int n_src, int S, int vocab, int ntypes, float eps) {
+  constexpr int H = 64 * E, C = E / 8;
+  const int lane = threadIdx.x & 63;
+  const int t = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (t >= t_cap) return;
+  const int src = tok_src[t];
+  int id = 0, ty = 0, p = 0;
+  if (src >= 0 && src < n_src) {  // else a pad token: id 0, position 0, type 0
+    id = ids[src] % vocab;
+    if (id < 0) id += vocab;
+    ty = min(max(types[src], 0), ntypes - 1);
+    p = src % S;
+  }
+  const float* rw = word + (size_t)id * H;
+  const float* rp = pos + (size_t)p * H;
+  const float* rt = tok + (size_t)ty * H;
+  float v[E];
+#pragma unroll
+  for (int c = 0; c < C; ++c) {
+    const int off = (c * 64 + lane) * 8;
+#pragma unroll
+    for (int hf = 0; hf < 2; ++hf) {
+      const float4 a = *reinterpret_cast<const float4*>(rw + off + 4 * hf);
+      const float4 b = *reinterpret_cast<const float4*>(rp + off + 4 * hf);
+      const float4 tt = *reinterpret_cast<const float4*>(rt + off + 4 * hf);
+      v[c * 8 + 4 * hf] = a.x + b.x + tt.x;
+      v[c * 8 + 4 * hf + 1] = a.y + b.y + tt.y;
+      v[c * 8 + 4 * hf + 2] = a.z + b.z + tt.z;
+      v[c * 8 + 4 * hf + 3] = a.w + b.w + tt.w;
+    }
+  }
+  ln_store_row<E>(v, gamma, beta, out + (size_t)t * H, out3 ? out3 + (size_t)t * 3 * H : nullptr, lane, eps);
+}
+
 __global__ void __launch_bounds__(256) unpack_logits_kernel(const float* __restrict__ ps, const float* __restrict__ pe,
                                                             const int* __restrict__ tok_of, float* __restrict__ os,
                                                             float* __restrict__ oe, int n, int t_cap) {
@@ -197,6 +242,35 @@ int tcamd_embed_layernorm_packed(const int* ids, const int* types, const int* to
     default: return hipErrorInvalidValue;
   }
 #undef TC_EMBP
+  return hipGetLastError();
+}
+
+// The fp32-parity form: fp32 tables / gamma / beta, out fp32 [t_cap][H]; out3
+// (or null): bf16 [t_cap][3H] = [hi | hi | lo], bitwise x3_cat of out.  The
+// same gather rule.  16-B aligned pointers.
+int tcamd_embed_layernorm_packed_f32(const int* ids, const int* types, const int* tok_src, const float* word,
+                                     const float* pos, const float* type, const float* gamma, const float* beta,
+                                     float* out, void* out3, int t_cap, int n_src, int S, int H, int vocab, int ntypes,
+                                     float eps, void* stream) {
+  if (t_cap <= 0) return hipSuccess;
+  if (!ids || !types || !tok_src || !word || !pos || !type || !gamma || !beta || !out || n_src <= 0 || S <= 0 ||
+      vocab <= 0 || ntypes <= 0 ||
+      ((uintptr_t)word | (uintptr_t)pos | (uintptr_t)type | (uintptr_t)gamma | (uintptr_t)beta | (uintptr_t)out |
+       (uintptr_t)out3) % 16)
+    return hipErrorInvalidValue;
+  const dim3 grid((t_cap + 3) / 4), block(256);
+  hipStream_t st = (hipStream_t)stream;
+#define TC_EMBPF(E)                                                                                                \
+  hipLaunchKernelGGL(embed_layernorm_packed_f32_kernel<E>, grid, block, 0, st, ids, types, tok_src, word, pos, type, \
+                     gamma, beta, out, (uint16_t*)out3, t_cap, n_src, S, vocab, ntypes, eps)
+  switch (H) {
+    case 512: TC_EMBPF(8); break;
+    case 1024: TC_EMBPF(16); break;
+    case 2048: TC_EMBPF(32); break;
+    case 4096: TC_EMBPF(64); break;
+    default: return hipErrorInvalidValue;
+  }
+#undef TC_EMBPF
   return hipGetLastError();
 }
 

@@ -4,6 +4,7 @@
   python tools/bert_probe.py --batch 64 --iters 10
   python tools/bert_probe.py --batch 1 8 64 --gemm lib,auto,ours --graphs   # projection routing A/B, HIP graphs
   python tools/bert_probe.py --packed --batch 1 8 32 64 128 --fill 64 128 192 256   # padded against padding-free
+  python tools/bert_probe.py --packed --fp32 --batch 1 8 32 64 --fill 64 128 192 256  # ... on the fp32-parity model
 
 ``--packed``: the graph forward as served, the padded arm (the masked graph of
 ``forward``) against the packed arm (``forward_packed`` at the t_cap the served
@@ -11,7 +12,10 @@ model would pick: rows x the smallest fill of 128 / 256 that holds the
 tokens), alternating inside one run, every round's time printed; rows of
 random lengths around each ``--fill`` (mean tokens per row).  Then the kernels
 alone at the same shapes, HIP events around ``--iters`` launches: K12 (masked)
-against K12v, and the plan, packed-embedding and unpack launches.
+against K12v, and the plan, packed-embedding and unpack launches.  With
+``--fp32`` both arms run the fp32-parity model (the padded arm is its served
+padded graph) and the kernels are K12x (masked) against K12xv and the fp32
+packed embedding.
 """
 
 import argparse
@@ -92,16 +96,18 @@ def packed_probe(a, model, dev):
             valid = mask >= 1
             diff = max(((outs["packed"][k][valid] - outs["padded"][k][valid]).norm()
                         / outs["padded"][k][valid].norm()).item() for k in range(2))
-            print(json.dumps({"probe": "graph", "rows": b, "fill": fill, "tokens": tokens, "t_cap": t_cap,
+            print(json.dumps({"probe": "graph", "fp32": a.fp32, "rows": b, "fill": fill, "tokens": tokens, "t_cap": t_cap,
                               "padded_ms": [round(x, 3) for x in ts["padded"]],
                               "packed_ms": [round(x, 3) for x in ts["packed"]],
-                              "packed_vs_padded_rel_l2": round(diff, 5)}), flush=True)
+                              "packed_vs_padded_rel_l2": float("%.3g" % diff)}), flush=True)
             # the kernels alone
-            qkv = (torch.randn(b * S, 3 * bert.HIDDEN, device=dev) * 1.5).bfloat16()
-            out = torch.empty(b * S, bert.HIDDEN, device=dev, dtype=torch.bfloat16)
+            dt = torch.float32 if a.fp32 else torch.bfloat16
+            qkv = (torch.randn(b * S, 3 * bert.HIDDEN, device=dev) * 1.5).to(dt)
+            out = torch.empty(b * S, bert.HIDDEN, device=dev, dtype=dt)
             plan = bert.pack_plan(mask, t_cap, True)
             scale = 1.0 / math.sqrt(64)
-            x = torch.empty(t_cap, bert.HIDDEN, device=dev, dtype=torch.bfloat16)
+            x = torch.empty(t_cap, bert.HIDDEN, device=dev, dtype=dt)
+            x3 = torch.empty(t_cap, 3 * bert.HIDDEN, device=dev, dtype=torch.bfloat16) if a.fp32 else None
             lg = torch.randn(2, t_cap, device=dev)
             o2 = torch.empty(2, b * S, device=dev)
             w = model
@@ -118,11 +124,26 @@ def packed_probe(a, model, dev):
                 "unpack": lambda: hip.unpack_logits(lg[0].data_ptr(), lg[1].data_ptr(), plan.tok_of.data_ptr(),
                                                     o2[0].data_ptr(), o2[1].data_ptr(), b * S, t_cap),
             }
+            if a.fp32:
+                del launches["k12_masked"], launches["k12v"]
+                launches = {
+                    "k12x_masked": lambda: hip.attention_f32(qkv.data_ptr(), mask.data_ptr(), out.data_ptr(), b, S,
+                                                             bert.HEADS, scale),
+                    "k12xv": lambda: hip.attention_f32_packed(qkv.data_ptr(), plan.row_len.data_ptr(),
+                                                              plan.cu.data_ptr(), out.data_ptr(), b, t_cap, bert.HEADS,
+                                                              scale),
+                    **launches,
+                    "embed_packed": lambda: hip.embed_layernorm_packed(
+                        ids.data_ptr(), tt.data_ptr(), plan.tok_src.data_ptr(), w.word.weight.data_ptr(),
+                        w.pos.weight.data_ptr(), w.tok_type.weight.data_ptr(), w.ln.weight.data_ptr(),
+                        w.ln.bias.data_ptr(), x.data_ptr(), t_cap, b * S, S, bert.HIDDEN, bert.VOCAB, bert.TYPES, 1e-12,
+                        f32=True, out3=x3.data_ptr()),
+                }
             us = {k: [] for k in launches}
             for _ in range(a.rounds):
                 for name, launch in launches.items():
                     us[name].append(round(_event_ms(launch, a.iters) * 1e3, 2))
-            print(json.dumps({"probe": "kernels_us", "rows": b, "fill": fill, "tokens": tokens, "t_cap": t_cap,
+            print(json.dumps({"probe": "kernels_us", "fp32": a.fp32, "rows": b, "fill": fill, "tokens": tokens, "t_cap": t_cap,
                               "plan_includes": "4 torch.empty and the launch", **us}), flush=True)
 
 
@@ -149,6 +170,8 @@ def main():
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
     if a.packed:
+        if a.fp32:
+            return packed_probe(a, bert.prepare_x3(bert.build(device=dev, dtype=torch.float32, layers=a.layers)), dev)
         return packed_probe(a, bert.build(device=dev, layers=a.layers), dev)
     model = (bert.prepare_x3(bert.build(device=dev, dtype=torch.float32)) if a.fp32 else bert.build(device=dev))
     for b in a.batch:

@@ -29,7 +29,10 @@ LayerNorms, GELU and the QA head are per-token operators, so they only see
 fewer tokens; attention is K12v, K12 over rows of different lengths -- and
 the unpack scatters the logits back to [b, s], PAD_LOGIT where the mask is
 below 1.  The work falls with the fill of the rows instead of staying at
-b x 384.
+b x 384.  The fp32-parity model (fp32 weights after ``prepare_x3``) has the
+same form: the fp32 packed embedding LayerNorm, which also writes the first
+QKV projection's bf16x3 operand, the bf16x3 projections and K11p over t_cap
+tokens, and K12xv, K12x over rows of different lengths.
 """
 
 import math
@@ -449,6 +452,48 @@ def _packed_ok(w, s):
     return s <= hip.ATTENTION_MAX_SEQ
 
 
+def _packed_f32_ok(model, s):
+    """The HIP form of the packed forward takes this fp32-parity model: fp32
+    weights on the GPU, every projection's bf16x3 weight prepared
+    (prepare_x3), s <= 384."""
+    w = model.word.weight
+    if not (FUSED and w.is_cuda and w.dtype == torch.float32):
+        return False
+    if not all(getattr(lin, "w3", None) is not None
+               for layer in model.layers for lin in (layer.qkv, layer.out, layer.ffn1, layer.ffn2)):
+        return False
+    from triton_client_amd.ops import hip
+
+    return s <= hip.ATTENTION_MAX_SEQ
+
+
+def _packed_f32_layer_ok(x, layer, plan):
+    """This layer runs K12xv on the packed fp32 activation ``x``: what
+    _packed_f32_ok says of the model, seen from one layer, and a K30 plan."""
+    if not (FUSED and x.is_cuda and x.dtype == torch.float32 and x.is_contiguous()
+            and getattr(layer.qkv, "w3", None) is not None and plan.row_len.dtype == torch.int32):
+        return False
+    from triton_client_amd.ops import hip
+
+    return plan.s <= hip.ATTENTION_MAX_SEQ
+
+
+def packed_x3_route_misses(t_caps):
+    """Every fp32-parity projection at every token count of ``t_caps`` either
+    goes to the library by the routing table or has a shape its routed kernel
+    accepts (_route_ok): the packed forward keys the row-independent
+    projections on M = t_cap.  Returns the (projection, t_cap) pairs that fall
+    back to the library although the table routes them to K17 / K18."""
+    shapes = {"qkv": (3 * HIDDEN, HIDDEN), "out": (HIDDEN, HIDDEN), "ffn_up": (FFN, HIDDEN), "ffn_down": (HIDDEN, FFN)}
+    bad = []
+    for M in t_caps:
+        for name, (N, K) in shapes.items():
+            route = gemm_route_x3(name, M, "auto")
+            if route[0] != "lib" and not _route_ok(route, M, N, 3 * K):
+                bad.append((name, M))
+    return bad
+
+
 def pack_plan(attention_mask, t_cap, fused):
     """The PackPlan of ``attention_mask`` [b, s] (valid = mask >= 1; any mask,
     not only a prefix): K30 on the GPU (no host sync: the caller guarantees
@@ -485,12 +530,26 @@ def pack_plan(attention_mask, t_cap, fused):
     return PackPlan(b, s, t_cap, row_len, cu, tok_src, tok_of)
 
 
-def _attention_packed(qkv, plan, qkv_bias=None):
+def _attention_packed(qkv, plan, qkv_bias=None, f32=False, x3_out=False):
     """Attention over the packed QKV projection [1, t_cap, 3H], every row
     within its own tokens: K12v on the GPU (``qkv`` computed without its bias,
     which the kernel applies; the pad tokens of the result are never written),
-    SDPA row by row elsewhere (``qkv`` with its bias; pad tokens zero)."""
+    K12xv with ``f32`` (the fp32-parity model: fp32 ``qkv`` with its bias;
+    ``x3_out``: the result is the out projection's bf16x3 operand, returned as
+    an _X3, as _attention does for K12x), SDPA row by row elsewhere (``qkv``
+    with its bias; pad tokens zero)."""
     t_cap = qkv.shape[1]
+    if f32:
+        from triton_client_amd.ops import hip
+
+        if x3_out:
+            out = torch.empty(t_cap, 3 * HIDDEN, device=qkv.device, dtype=torch.bfloat16)
+        else:
+            out = torch.empty(1, t_cap, HIDDEN, device=qkv.device, dtype=torch.float32)
+        hip.attention_f32_packed(qkv.data_ptr(), plan.row_len.data_ptr(), plan.cu.data_ptr(), out.data_ptr(), plan.b,
+                                 t_cap, HEADS, 1.0 / math.sqrt(HIDDEN // HEADS),
+                                 stream=torch.cuda.current_stream(qkv.device).cuda_stream, x3=x3_out)
+        return _X3(out, (1, t_cap, HIDDEN)) if x3_out else out
     if qkv_bias is not None:
         from triton_client_amd.ops import hip
 
@@ -546,6 +605,10 @@ class _Layer(nn.Module):
         if packed is not None:
             if _packed_ok(x, packed.s) and x.is_contiguous():
                 a = _attention_packed(_proj(x, self.qkv, "none", name="qkv"), packed, qkv_bias=self.qkv.bias)
+            elif _packed_f32_layer_ok(x, self, packed):
+                qkv = _proj(x, self.qkv, name="qkv")
+                a = _attention_packed(qkv.contiguous(), packed, f32=True,
+                                      x3_out=getattr(self.out, "w3", None) is not None)
             else:
                 a = _attention_packed(_proj(x, self.qkv, name="qkv"), packed)
         elif _k12_ok(x, s):
@@ -590,12 +653,29 @@ class BertLargeQA(nn.Module):
         pos = torch.arange(s, device=input_ids.device)
         return self.ln(self.word(input_ids) + self.pos(pos)[None] + self.tok_type(token_type_ids))
 
-    def _embed_packed(self, input_ids, token_type_ids, plan, fused):
+    def _embed_packed(self, input_ids, token_type_ids, plan, fused, f32=False):
         """The embedding LayerNorm of the plan's tokens -> [1, t_cap, H]: one HIP
         launch straight from the int32 inputs (ids wrapped by remainder(VOCAB),
         types clamped to [0, 1], as the served model applies them; a pad token
-        is id 0, position 0, type 0), a torch gather elsewhere."""
+        is id 0, position 0, type 0), a torch gather elsewhere.  ``f32`` (the
+        fp32-parity model's HIP form): the fp32 kernel, which also writes the
+        first QKV projection's bf16x3 operand, attached as ``out._x3``."""
         w = self.word.weight
+        if f32:
+            from triton_client_amd.ops import hip
+
+            ids = input_ids.to(torch.int32).contiguous()
+            tt = token_type_ids.to(torch.int32).contiguous()
+            out = torch.empty(1, plan.t_cap, HIDDEN, device=w.device, dtype=torch.float32)
+            xc = torch.empty(plan.t_cap, 3 * HIDDEN, device=w.device, dtype=torch.bfloat16)
+            hip.embed_layernorm_packed(ids.data_ptr(), tt.data_ptr(), plan.tok_src.data_ptr(), w.data_ptr(),
+                                       self.pos.weight.data_ptr(), self.tok_type.weight.data_ptr(),
+                                       self.ln.weight.data_ptr(), self.ln.bias.data_ptr(), out.data_ptr(), plan.t_cap,
+                                       plan.b * plan.s, plan.s, HIDDEN, VOCAB, TYPES, self.ln.eps,
+                                       stream=torch.cuda.current_stream(w.device).cuda_stream, f32=True,
+                                       out3=xc.data_ptr())
+            out._x3 = xc
+            return out
         if fused:
             from triton_client_amd.ops import hip
 
@@ -626,13 +706,17 @@ class BertLargeQA(nn.Module):
         must hold every valid token; the HIP form does not check it (no host
         sync, so a graph can capture it).  ids wrap by remainder(VOCAB) and
         types clamp to [0, 1], as the served model applies them.  HIP kernels
-        on the GPU in bf16, plain torch ops (gather, SDPA per row, scatter)
-        off the GPU, in another dtype or with TC_BERT_FUSED=0."""
+        on the GPU in bf16 and for the fp32-parity model (fp32 weights after
+        prepare_x3: the fp32 packed embedding, the bf16x3 projections and K11p
+        over t_cap tokens, K12xv), plain torch ops (gather, SDPA per row,
+        scatter) off the GPU, in another dtype or with TC_BERT_FUSED=0."""
         b, s = input_ids.shape
         t_cap = int(t_cap)
         fused = _packed_ok(self.word.weight, s) and input_ids.is_cuda
+        f32 = not fused and input_ids.is_cuda and _packed_f32_ok(self, s)
+        fused = fused or f32
         plan = pack_plan(attention_mask, t_cap, fused)
-        x = self._embed_packed(input_ids, token_type_ids, plan, fused)
+        x = self._embed_packed(input_ids, token_type_ids, plan, fused, f32=f32)
         for layer in self.layers:
             x = layer(x, None, packed=plan)
         st, en = _qa_head(x, self.qa)  # [1, t_cap]

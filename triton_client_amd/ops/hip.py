@@ -483,6 +483,21 @@ _SIGS = {
     "tcamd_attention_packed_plan": (
         [ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)], ctypes.c_int,
     ),
+    # ... and its fp32-parity form: the fp32 packed embedding, K12xv
+    "tcamd_embed_layernorm_packed_f32": (
+        [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+         ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_void_p],
+        ctypes.c_int,
+    ),
+    "tcamd_attention_f32_packed": (
+        [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+         ctypes.c_float, ctypes.c_int, ctypes.c_void_p],
+        ctypes.c_int,
+    ),
+    "tcamd_attention_f32_packed_plan": (
+        [ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int)], ctypes.c_int,
+    ),
     # native batch executor for pointer-table graph models (csrc/runtime/graph_exec.hip)
     "tcamd_pgx_create": (
         [ctypes.c_int32, ctypes.c_int32, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int32,
@@ -1264,12 +1279,24 @@ def bert_pack_plan(mask, mask_stride, rows, S, t_cap, row_len, cu, tok_src, tok_
 
 
 def embed_layernorm_packed(ids, types, tok_src, word, pos, type_, gamma, beta, out, t_cap, n_src, S, H, vocab, ntypes,
-                           eps, stream=None):
+                           eps, stream=None, f32=False, out3=None):
     """BERT embeddings of the packed tokens: out [t_cap][H] bf16, token t from
     the int32 request tensors ``ids`` / ``types`` [n_src] at ``tok_src[t]``
     (ids wrap by remainder(vocab), types clamp to [0, ntypes - 1], position =
     src % S); a pad token (tok_src = -1) is id 0, position 0, type 0.  A real
-    token has the bits ``embed_layernorm`` gives its (row, position)."""
+    token has the bits ``embed_layernorm`` gives its (row, position).
+    ``f32`` (the fp32-parity model): tables, gamma, beta and ``out`` are fp32,
+    the fp32 sum goes through a two-pass fp32 LayerNorm; ``out3`` (or None) is
+    then also written as the next bf16x3 GEMM's operand, bf16 [t_cap][3H] =
+    [hi | hi | lo], bitwise ``x3_cat`` of ``out``."""
+    if f32:
+        _check(_load().tcamd_embed_layernorm_packed_f32(ids, types, tok_src, word, pos, type_, gamma, beta, out,
+                                                        _vp(out3), int(t_cap), int(n_src), int(S), int(H), int(vocab),
+                                                        int(ntypes), float(eps), _vp(stream)),
+               "embed_layernorm_packed(f32)")
+        return
+    if out3 is not None:
+        raise ValueError("embed_layernorm_packed: out3 needs f32=True")
     _check(_load().tcamd_embed_layernorm_packed(ids, types, tok_src, word, pos, type_, gamma, beta, out, int(t_cap),
                                                 int(n_src), int(S), int(H), int(vocab), int(ntypes), float(eps),
                                                 _vp(stream)), "embed_layernorm_packed")
@@ -1297,6 +1324,25 @@ def attention_packed_plan(rows, heads):
     _check(_load().tcamd_attention_packed_plan(int(rows), int(heads), ctypes.byref(sp), ctypes.byref(w)),
            "attention_packed_plan")
     return sp.value, w.value
+
+
+def attention_f32_packed(qkv, row_len, cu, out, rows, t_cap, heads, scale, stream=None, x3=False):
+    """K12xv: K12x over packed rows.  ``qkv`` [t_cap][3*heads*64] fp32 (bias
+    included) holds row r's tokens at cu[r] .. cu[r] + row_len[r] - 1 (int32
+    device arrays from ``bert_pack_plan``; row_len <= ATTENTION_MAX_SEQ, rows
+    <= BERT_PACK_MAX_ROWS); ``out`` [t_cap][heads*64] fp32 or, with ``x3``, the
+    out projection's bf16x3 operand, bf16 [t_cap][3*heads*64].  Only the rows'
+    own tokens are read and written; a valid token gets the bits K12x gives it
+    in the row padded to 384 behind a prefix mask."""
+    _check(_load().tcamd_attention_f32_packed(qkv, row_len, cu, out, int(rows), int(t_cap), int(heads), float(scale),
+                                              1 if x3 else 0, _vp(stream)), "attention_f32_packed")
+
+
+def attention_f32_packed_plan(rows, heads):
+    """Waves per block (4 or 8) of K12xv's launch, fixed per (rows, heads): K12x's plan at S = 384.  Host only."""
+    w = ctypes.c_int(0)
+    _check(_load().tcamd_attention_f32_packed_plan(int(rows), int(heads), ctypes.byref(w)), "attention_f32_packed_plan")
+    return w.value
 
 
 def x3_conv1x1_ws_bytes(M, K, N=128):

@@ -44,7 +44,7 @@ def main(argv=None):
                     help="vocab.txt of the bert_tokenizer model (one piece per line; handed down as "
                          "TCAMD_BERT_VOCAB); default: the demonstration vocabulary that ships with the package")
     ap.add_argument("--bert-packed", action="store_true",
-                    help="bert_large: also capture the padding-free graphs and serve every batch whose valid tokens "
+                    help="bert_large and bert_large_fp32: also capture the padding-free graphs and serve every batch whose valid tokens "
                          "fit one of them over those tokens alone (handed down as TCAMD_BERT_PACKED=1)")
     args = ap.parse_args(argv)
     if args.bert_vocab:

@@ -696,8 +696,8 @@ class BertLarge(DeviceModel):
     graph, chosen as without the knob.  On a packed batch the positions with
     mask below 1 hold ``PAD_LOGIT`` (-10000); no consumer reads them (K27, K29
     and utils/qa.py all go by the mask).  ``route_counts`` counts the batches
-    per route.  The fp32-parity ``bert_large_fp32`` has no packed attention
-    kernel and keeps the padded route whatever the knob says."""
+    per route.  The fp32-parity ``bert_large_fp32`` takes the same route with
+    the fp32 form of ``forward_packed`` (K12xv attention)."""
 
     name = "bert_large"
     platform = "pytorch_libtorch"
@@ -1025,9 +1025,13 @@ class BertLargeFP32(BertLarge):
     fp32 accumulate), LayerNorm / GELU / softmax attention in fp32.  Served
     logits match an fp32 forward of the fp32 weights to ~1e-5
     (tests/test_bert_accuracy_gpu.py); ~3x the bf16 model's GEMM work.  The
-    bf16 ``bert_large`` stays the config-4 serving default.  It has no
-    padding-free route: K12x has no packed counterpart, so ``TCAMD_BERT_PACKED``
-    does not apply and every batch runs the padded graphs."""
+    bf16 ``bert_large`` stays the config-4 serving default.  With
+    ``TCAMD_BERT_PACKED=1`` it takes the padding-free route of the base class:
+    packed graphs per (bucket <= 64, fill 128 / 256) that run the fp32 form of
+    ``BertLargeQA.forward_packed`` -- the fp32 packed embedding LayerNorm, the
+    bf16x3 projections and K11p over ``t_cap`` tokens, K12xv (K12x over packed
+    rows, csrc/kernels/bert.hip); ``packed_bucket`` and ``route_counts`` as in
+    the base class.  Without the knob every batch runs the padded graphs."""
 
     name = "bert_large_fp32"
     # 64 rows, as before bert_large went to 128: a bs128 fp32-parity forward
@@ -1036,8 +1040,8 @@ class BertLargeFP32(BertLarge):
     # (profiles/r6_bert_batching/)
     max_batch_size = 64
     BUCKETS = tuple(b for b in BertLarge.BUCKETS if b <= 64)
-    # no packed route: K12x has no counterpart of K12v, so TCAMD_BERT_PACKED leaves this model on the padded graphs
-    supports_packed = False
+    # the packed route of the base class, in fp32: K12xv is K12x's counterpart of K12v
+    supports_packed = True
 
     def _build_model(self, bert, dev):
         import torch

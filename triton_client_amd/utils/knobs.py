@@ -110,9 +110,9 @@ KNOBS = [
          "into rows on the device; 0 = the host twin of the same rule",
          "tests/test_wordpiece_gpu.py::test_the_knob_changes_the_route_and_not_one_bit_of_the_rows"),
     Knob("TCAMD_BERT_PACKED", "python", 0, "server/gpu_models.py",
-         "bert_large: 1 = also capture padding-free graphs (K30 pack plan, K12v attention over packed rows) per row "
-         "bucket and fill 128 / 256, and serve a batch whose valid tokens fit one over those tokens alone (the "
-         "server's --bert-packed sets it); 0 = every batch runs the padded graphs",
+         "bert_large and bert_large_fp32: 1 = also capture padding-free graphs (K30 pack plan, K12v / K12xv attention "
+         "over packed rows) per row bucket and fill 128 / 256, and serve a batch whose valid tokens fit one over "
+         "those tokens alone (the server's --bert-packed sets it); 0 = every batch runs the padded graphs",
          "tests/test_bert_pack_gpu.py::test_served_short_rows_take_a_packed_graph"),
     Knob("TCAMD_BERT_VOCAB", "python", "", "utils/wordpiece.py",
          "bert_tokenizer: the vocab.txt to load (the server's --bert-vocab sets it); unset = the demonstration "

@@ -44,6 +44,7 @@
 
 #include "kernels/common.h"
 #include "kernels/knobs.h"
+#include "kernels/x3_ring_math.h"
 
 // Host-side per-device caches (CU count, dynamic-LDS opt-ins): indexed by the
 // current HIP device, clamped into the table.
@@ -74,7 +75,9 @@ __device__ __forceinline__ uint32_t pk(float a, float b) {
 
 // hi/lo split of two fp32: a ~= hi + lo to 2^-17 relative (a - hi is exact).
 // (A v_pk_fma_f32 / v_pk_add_f32 form of this and of the BN affine issues
-// fewer instructions but measured 3-8% slower in K14x / K8x / K11x: round 4.)
+// fewer instructions but measured 3-8% slower in K14x / K8x / K11x: round 4;
+// in K11x alone, bit-identical, behind the scalar form at 11 of 12 layer
+// shapes again: profiles/r24_k11x_index_math.md.)
 // (hipcc turns the hi << 16 below into a second v_cvt_pk_bf16_f32 of (a, 0)
 // plus a shift; a v_perm_b32 instead issued fewer instructions but measured
 // 1-5% slower in K14x, round 4.)
@@ -948,8 +951,40 @@ struct X3FusedParams {
 // Forced inline, each generates the code it generated written out in both
 // kernels (tools/isa_diff.py, profiles/r18_k11x_refactor.md).  Still written
 // out in both, because a function changed every instantiation's instruction
-// stream: the LDS carve, the BN1 table staging, br_off, the 3x3 row bases
-// (R / lfm / rtm), the partial exchange and the owners' sum.
+// stream: the LDS carve, the BN1 table staging, br_off, the partial exchange
+// and the owners' sum.
+
+// LDS addresses as the ds_read sees them (32-bit, address space 3)
+typedef const __attribute__((address_space(3))) uint8_t* x3f_lds_ptr;
+__device__ __forceinline__ uint32_t x3f_lds_addr(const uint8_t* q) {
+  return (uint32_t)reinterpret_cast<uintptr_t>((x3f_lds_ptr)q);
+}
+
+// The 3x3's tile state (x3_ring_math.h): the block's first tile by division,
+// carried from tile to tile after that; uniform, so it stays in SGPRs.  cbase
+// / zbase: the ring's LDS address + this lane's 16-B chunk / + the zero rows.
+struct X3fTileState {
+  x3r::X3Tile ts;
+  x3r::X3Step step;
+  uint32_t cbase, zbase;
+};
+__device__ __forceinline__ X3fTileState x3f_tile_state(const X3FusedParams& p, const uint8_t* ring, int t_begin, int kq,
+                                                       int lane) {
+  X3fTileState s;
+  int r0;
+  (void)fast_divmod(t_begin * kT2, p.H * p.W, p.mag_hw, r0);
+  s.ts.y = fast_divmod(r0, p.W, p.mag_w, s.ts.x);
+  (void)fast_divmod(t_begin * kT2 + p.W + 1, kRingF, kMagRingF, s.ts.pos);
+  s.step = x3r::x3r_step(p.H, p.W);
+  s.cbase = x3f_lds_addr(ring) + (uint32_t)((4 * kq + (lane >> 4)) << 4);
+  s.zbase = x3f_lds_addr(ring) + (uint32_t)(kZeroF * kRowF1);
+  return s;
+}
+// a tile's row bases, and the state moved on to the next tile
+__device__ __forceinline__ void x3f_rows(X3fTileState& s, const X3FusedParams& p, int m0, int lane, x3r::X3Rows& rows) {
+  x3r::x3r_rows<false>(s.ts, m0, lane & 15, p.M, p.H, p.W, s.cbase, s.zbase, rows);
+  x3r::x3r_advance(s.ts, s.step, p.H, p.W);
+}
 
 // 3x3 resident weights of wave (kq, oh): A[16oh + (lane&15)][tap t][32kq + 8(lane>>4) ..+8]
 __device__ __forceinline__ void x3f_load_w2(const uint16_t* w2_hi, const uint16_t* w2_lo, int kq, int oh, int lane,
@@ -1012,14 +1047,15 @@ __device__ __forceinline__ void x3f_mma1(const uint8_t* cvt, f32x16& acc, const 
 
 // C (32x32) of a chunk, z rows [g0, g0 + nrows) -> ring: lane col = pixel
 // bpx, reg 4g+e -> channel 32q1 + 8g + 4hh + e; ReLU, hi/lo split
+// (g0 is uniform: its ring position is scalar arithmetic, the lane adds bpx < 64)
 __device__ __forceinline__ void x3f_z_to_ring(uint8_t* ring, const f32x16& acc, int g0, int nrows, int W, int bpx,
                                               int hh, int q1) {
   if (bpx < nrows) {
-    int pos;
-    (void)fast_divmod(g0 + bpx + W + 1, kRingF, kMagRingF, pos);
+    int pos = (g0 + W + 1) % kRingF + bpx;  // g0 + W + 1 >= 0
+    if (pos >= kRingF) pos -= kRingF;
     // physical row pos + 1; logical rows 0 and 191 also go to the guard
     // rows 193 / 0 (same bank rotation: 192 rows x 8 banks is a multiple of 64)
-    uint8_t* rp = ring + (pos + 1) * kRowF1 + 8 * hh;
+    uint8_t* rp = ring + __mul24(pos + 1, kRowF1) + 8 * hh;
     const int mirror = pos == 0 ? kRingF * kRowF1 : (pos == kRingF - 1 ? -kRingF * kRowF1 : 0);
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
@@ -1041,19 +1077,16 @@ __device__ __forceinline__ void x3f_z_to_ring(uint8_t* ring, const f32x16& acc, 
 
 // the ring operands of 3x3 step (tap = step >> 2, pixel group = step & 3)
 // into the rolling buffer: the reads run kLead steps ahead of the MFMAs
-// ((kLead+1) x 8 VGPRs instead of whole taps)
+// ((kLead+1) x 8 VGPRs instead of whole taps).  The address is the tile's row
+// base (x3_ring_math.h) or, at an image edge, the zero rows: one select for a
+// dx != 0 step, none for dx = 0; dx and the plane are ds_read immediates.
 template <int kLead>
-__device__ __forceinline__ void x3f_rd(const uint8_t* ring, int step, const int (&R)[4][3], const bool (&lfm)[4],
-                                       const bool (&rtm)[4], int chunk16, v4u (&bq)[kLead + 1][2]) {
+__device__ __forceinline__ void x3f_rd(int step, const x3r::X3Rows& rows, uint32_t zero, v4u (&bq)[kLead + 1][2]) {
   const int t = step >> 2, pg = step & 3;
-  const int dy = t / 3, dx = t % 3 - 1;
-  const int a = R[pg][dy] + dx;  // logical row, -1 .. 192 (or a zero row)
-  int off = a * kRowF1 + chunk16;
-  if (dx < 0 && !lfm[pg]) off = kZeroF * kRowF1;
-  if (dx > 0 && !rtm[pg]) off = kZeroF * kRowF1;
-  const uint8_t* q = ring + kRowF1 + off;  // physical row = logical + 1
-  bq[step % (kLead + 1)][0] = ld16(q);
-  bq[step % (kLead + 1)][1] = ld16(q + 256);
+  const int dy = t / 3, dxi = t % 3;
+  const x3f_lds_ptr q = reinterpret_cast<x3f_lds_ptr>(x3r::x3r_tap(rows, pg, dy, dxi, zero)) + dxi * kRowF1;
+  bq[step % (kLead + 1)][0] = *reinterpret_cast<const __attribute__((address_space(3))) v4u*>(q);
+  bq[step % (kLead + 1)][1] = *reinterpret_cast<const __attribute__((address_space(3))) v4u*>(q + x3r::kLoPlane);
 }
 
 // NST = K / 32 (2..7): the k loop of a chunk is straight-line code, so the
@@ -1071,7 +1104,7 @@ __global__ void __launch_bounds__(512, 1) x3_dense_fused_kernel(X3FusedParams p)
   float* const bn = reinterpret_cast<float*>(cvt + 4 * kCvtF);            // s1 [kMaxKF] | t1 [kMaxKF]
   float* const ysum = bn + 2 * kMaxKF;                                     // [oh][owner][pg][16 px][4]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int W = p.W, HW = p.H * p.W;
+  const int W = p.W;
 
   // 3x3 roles and resident weights: A[16oh + (lane&15)][tap t][32kq + 8(lane>>4) ..+8]
   const int kq = wave & 3, oh = wave >> 2;
@@ -1162,6 +1195,7 @@ __global__ void __launch_bounds__(512, 1) x3_dense_fused_kernel(X3FusedParams p)
   }
 
   const int c4 = lane >> 4;
+  X3fTileState tst = x3f_tile_state(p, ring, t_begin, kq, lane);
   for (int tile = t_begin; tile < t_end; ++tile) {
     const int m0 = tile * kT2;
     __syncthreads();  // B0: the ring holds band(tile); the scratch is free
@@ -1177,40 +1211,16 @@ __global__ void __launch_bounds__(512, 1) x3_dense_fused_kernel(X3FusedParams p)
     {
     // Per pixel group pg (16 consecutive pixels; the host requires W >= 16,
     // so +16 pixels wraps an image row at most once) and tap
-    // row dy: the band row R[pg][dy] (logical 0..191), or the zero rows for
-    // an invalid dy; tap (dy, dx) reads logical row R + dx, which the guard
-    // rows (logical -1 and 192) keep in range without a second wrap.  Per
-    // (tap, pg) step that leaves: add dx, swizzle, address, and for dx != 0
-    // a select of the zero row: ~4 VALU beside 3 MFMAs (the first version's
-    // ~15 made the phase issue-bound, not MFMA-bound).
-    int R[4][3];
-    bool lfm[4], rtm[4];
-    {
-      const int m = m0 + (lane & 15);
-      int r, xx, pm;
-      (void)fast_divmod(m, HW, p.mag_hw, r);
-      int yy = fast_divmod(r, W, p.mag_w, xx);
-      (void)fast_divmod(m + W + 1, kRingF, kMagRingF, pm);
-#pragma unroll
-      for (int pg = 0; pg < 4; ++pg) {
-        if (pg) {
-          xx += 16;
-          if (xx >= W) {
-            xx -= W;
-            if (++yy == p.H) yy = 0;
-          }
-          pm += 16;
-          if (pm >= kRingF) pm -= kRingF;
-        }
-        const bool in = m + 16 * pg < p.M;
-        const int rm = pm - W, rp = pm + W;
-        R[pg][0] = (in && yy > 0) ? (rm < 0 ? rm + kRingF : rm) : kZeroF;
-        R[pg][1] = in ? pm : kZeroF;
-        R[pg][2] = (in && yy < p.H - 1) ? (rp >= kRingF ? rp - kRingF : rp) : kZeroF;
-        lfm[pg] = xx > 0;
-        rtm[pg] = xx < W - 1;
-      }
-    }
+    // row dy: the LDS address of the band row's dx = -1 operand (logical
+    // rows 0..191), or of the zero rows for an invalid dy; tap (dy, dx) is
+    // an immediate past it, and the guard rows (logical -1 and 192) keep
+    // row + dx in range without a second wrap.  Per (tap, pg) step that
+    // leaves one select of the zero rows for dx != 0 and nothing for
+    // dx = 0 beside 3 MFMAs (per-step row arithmetic cost ~4 VALU a step,
+    // the first version's ~15 made the phase issue-bound, not MFMA-bound;
+    // profiles/r24_k11x_index_math.md).
+    x3r::X3Rows rows;
+    x3f_rows(tst, p, m0, lane, rows);
     f32x4 acc[4];
 #pragma unroll
     for (int pg = 0; pg < 4; ++pg) acc[pg] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -1218,8 +1228,7 @@ __global__ void __launch_bounds__(512, 1) x3_dense_fused_kernel(X3FusedParams p)
     // ahead of the MFMAs ((kLead+1) x 8 VGPRs instead of whole taps)
     constexpr int kLead = 3;
     v4u bq[kLead + 1][2];
-    const int chunk16 = (4 * kq + (lane >> 4)) << 4;
-    auto rd = [&](int step) { x3f_rd<kLead>(ring, step, R, lfm, rtm, chunk16, bq); };
+    auto rd = [&](int step) { x3f_rd<kLead>(step, rows, tst.zbase, bq); };
 #pragma unroll
     for (int step = 0; step < kLead; ++step) rd(step);
 #pragma unroll
@@ -1314,7 +1323,7 @@ __global__ void __launch_bounds__(512, 1) x3_dense_fused3_kernel(X3FusedParams p
   float* const bias = ysum + kYsF;                                // b1 [128]
   auto bar = [](int) { __syncthreads(); };  // argument: the barrier's index within a tile
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int W = p.W, HW = p.H * p.W;
+  const int W = p.W;
 
   // 3x3 roles and resident weights (as v1)
   const int kq = wave & 3, oh = wave >> 2;
@@ -1423,42 +1432,20 @@ __global__ void __launch_bounds__(512, 1) x3_dense_fused3_kernel(X3FusedParams p
   __syncthreads();  // B: ring = band(t_begin), stage 0 ready
 
   // 3x3 row bases of a tile (see v1)
-  int R[4][3];
-  bool lfm[4], rtm[4];
-  auto rows3 = [&](int m0) {
-    const int m = m0 + (lane & 15);
-    int r, xx, pm;
-    (void)fast_divmod(m, HW, p.mag_hw, r);
-    int yy = fast_divmod(r, W, p.mag_w, xx);
-    (void)fast_divmod(m + W + 1, kRingF, kMagRingF, pm);
-#pragma unroll
-    for (int pg = 0; pg < 4; ++pg) {
-      if (pg) {
-        xx += 16;
-        if (xx >= W) {
-          xx -= W;
-          if (++yy == p.H) yy = 0;
-        }
-        pm += 16;
-        if (pm >= kRingF) pm -= kRingF;
-      }
-      const bool in = m + 16 * pg < p.M;
-      const int rm = pm - W, rp = pm + W;
-      R[pg][0] = (in && yy > 0) ? (rm < 0 ? rm + kRingF : rm) : kZeroF;
-      R[pg][1] = in ? pm : kZeroF;
-      R[pg][2] = (in && yy < p.H - 1) ? (rp >= kRingF ? rp - kRingF : rp) : kZeroF;
-      lfm[pg] = xx > 0;
-      rtm[pg] = xx < W - 1;
-    }
-  };
+  X3fTileState tst = x3f_tile_state(p, ring, t_begin, kq, lane);
+  x3r::X3Rows rows;
+  auto rows3 = [&](int m0) { x3f_rows(tst, p, m0, lane, rows); };
   constexpr int kLead = 2;
   constexpr int kSteps3 = 4 * kTaps;
   v4u bq[kLead + 1][2];
-  const int chunk16 = (4 * kq + (lane >> 4)) << 4;
-  auto rd = [&](int step) { x3f_rd<kLead>(ring, step, R, lfm, rtm, chunk16, bq); };
+  auto rd = [&](int step) { x3f_rd<kLead>(step, rows, tst.zbase, bq); };
   f32x4 acc3[4];
-  auto mma3 = [&](int step) {
+  // fence: keep the read where it is written, kLead steps ahead of its MFMAs
+  // (the 3x3-only path; left to itself the scheduler sinks each read to its
+  // use.  The interleaved path's order is the scheduler's)
+  auto mma3 = [&](int step, bool fence = false) {
     if (step + kLead < kSteps3) rd(step + kLead);
+    if (fence) __builtin_amdgcn_sched_barrier(0);
     const int t = step >> 2, pg = step & 3;
     acc3[pg] = x3_16(w2h[t], w2l[t], bq[step % (kLead + 1)][0], bq[step % (kLead + 1)][1], acc3[pg]);
   };
@@ -1542,7 +1529,7 @@ __global__ void __launch_bounds__(512, 1) x3_dense_fused3_kernel(X3FusedParams p
 #pragma unroll
       for (int s = 0; s < kLead; ++s) rd(s);
 #pragma unroll
-      for (int j = 0; j < kSteps3; ++j) mma3(j);
+      for (int j = 0; j < kSteps3; ++j) mma3(j, true);
       partials();
       __syncthreads();
       owner_sums(m0);

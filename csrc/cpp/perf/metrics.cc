@@ -2,8 +2,10 @@
 // GPU metrics"): the amdgpu driver's sysfs counters of the MI355X under test
 // — busy percent, board power, VRAM in use — sampled every
 // --metrics-interval ms on a background thread while a sweep point is
-// measured.  No ROCm library or server endpoint is needed, so the sampler
-// also works against a remote server when the tool runs on the GPU host.
+// measured.  No server endpoint is needed, so the sampler also works against
+// a remote server when the tool runs on the GPU host.  Where the driver does
+// not publish its VRAM counter (a virtual machine's card), VRAM in use comes
+// from the HIP runtime's device-wide hipMemGetInfo instead.
 #include <dirent.h>
 #include <limits.h>
 #include <stdlib.h>
@@ -128,6 +130,9 @@ GpuMetrics::GpuMetrics(int device, uint64_t interval_ms, const std::string& sysf
     dev_ = gpus[device];
   }
   power_file_ = PowerFile(dev_);
+  // a guest's amdgpu can lack mem_info_vram_used: ask the runtime for the real card then
+  uint64_t vram = 0;
+  if (sysfs_root.empty() && !ReadU64(dev_ + "/mem_info_vram_used", &vram)) hip_device_ = device;
 }
 
 GpuMetrics::~GpuMetrics() { Stop(); }
@@ -146,13 +151,20 @@ void GpuMetrics::Start()
   }
   running_ = true;
   th_ = std::thread([this] {
+    // the current device is per thread: this one's choice leaves the lanes alone
+    const bool hip_mem = hip_device_ >= 0 && hipSetDevice(hip_device_) == hipSuccess;
     std::unique_lock<std::mutex> lk(mu_);
     while (!stop_) {
       lk.unlock();
       uint64_t busy = 0, power = 0, mem = 0;
       const bool ok = ReadU64(dev_ + "/gpu_busy_percent", &busy);
       if (!power_file_.empty()) ReadU64(power_file_, &power);
-      ReadU64(dev_ + "/mem_info_vram_used", &mem);
+      size_t free_b = 0, total_b = 0;
+      if (!hip_mem) {
+        ReadU64(dev_ + "/mem_info_vram_used", &mem);
+      } else if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && total_b >= free_b) {
+        mem = total_b - free_b;  // device-wide, like the sysfs counter
+      }
       lk.lock();
       if (ok) {
         samples_++;

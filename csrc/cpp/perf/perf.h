@@ -175,6 +175,7 @@ class GpuMetrics {
  private:
   std::string dev_, power_file_;
   uint64_t interval_ms_;
+  int hip_device_ = -1;  // >= 0: VRAM in use from hipMemGetInfo, the sysfs counter is missing
   mutable std::mutex mu_;
   std::condition_variable cv_;
   std::thread th_;

@@ -58,11 +58,6 @@ void check_crc(const Ctx& cx, const Span& s, const char* name) {
   if ((uint32_t)c != s.crc) cx.fail(TCAMD_PNG_MALFORMED, "bad CRC in %s", name);
 }
 
-// the seven Adam7 sub-images: first column and row, column and row step
-const int kAdam7[7][4] = {{0, 0, 8, 8}, {4, 0, 8, 8}, {0, 4, 4, 8}, {2, 0, 4, 4}, {0, 2, 2, 4}, {1, 0, 2, 2}, {0, 1, 1, 2}};
-
-int pass_size(int full, int first, int step) { return full > first ? (full - first + step - 1) / step : 0; }
-
 Parsed parse(const Ctx& cx, const uint8_t* blob, uint64_t n) {
   Parsed out;
   if (!blob || n < 8 || memcmp(blob, kSignature, 8) != 0) cx.fail(TCAMD_PNG_MALFORMED, "no PNG signature");
@@ -120,11 +115,7 @@ Parsed parse(const Ctx& cx, const uint8_t* blob, uint64_t n) {
     info.filtered_bytes = s.filtered_bytes, info.palette_off = s.palette_off, info.line_off = s.line_off;
     info.stage_bytes = s.stage_bytes;
   } else {
-    for (const auto& a : kAdam7) {
-      const int pw = pass_size(info.w, a[0], a[2]), ph = pass_size(info.h, a[1], a[3]);
-      if (pw && ph) info.filtered_bytes += (uint64_t)ph * (1 + row_bytes(pw, info.ctype, info.depth));
-    }
-    info.stage_bytes = info.filtered_bytes;
+    info.stage_bytes = info.filtered_bytes = stage_layout_adam7(info.h, info.w, info.ctype, info.depth).filtered_bytes;
   }
   return out;
 }
@@ -210,6 +201,20 @@ void unfilter(const uint8_t* filt, int h, int w, int ctype, int depth, const uin
   }
 }
 
+void check_adam7_filter_bytes(const Ctx& cx, const uint8_t* filt, const Adam7Layout& lay, const TcamdPngInfo& info) {
+  for (int p = 0; p < kAdam7Passes; ++p)
+    if (lay.w[p] && lay.h[p]) check_filter_bytes(cx, filt + lay.off[p], lay.h[p], row_bytes(lay.w[p], info.ctype, info.depth), 0);
+}
+
+// the seven sub-images at filt + lay.off[] -> the uint8 HWC image of info at out
+void unfilter_adam7(const uint8_t* filt, const Adam7Layout& lay, const TcamdPngInfo& info, const uint8_t* pal, uint8_t* out) {
+  for (int p = 0; p < kAdam7Passes; ++p) {
+    if (!lay.w[p] || !lay.h[p]) continue;
+    const Adam7Pass a = adam7_pass(p);
+    unfilter(filt + lay.off[p], lay.h[p], lay.w[p], info.ctype, info.depth, pal, out, info.w, a.x0, a.dx, a.y0, a.dy);
+  }
+}
+
 template <class F>
 int guarded(char* msg, int msg_cap, F&& body) {
   if (msg && msg_cap > 0) msg[0] = 0;
@@ -266,6 +271,51 @@ int tcamd_host_png_unfilter(const uint8_t* staged, uint64_t staged_bytes, const 
   return 0;
 }
 
+int tcamd_host_png_adam7_layout(const TcamdPngInfo* info, TcamdPngAdam7Layout* out) {
+  if (!info || !out || info->interlace != 1) return -1;
+  if (info->h < 1 || info->w < 1 || info->h > kMaxDim || info->w > kMaxDim || !pair_ok(info->ctype, info->depth))
+    return -1;
+  const Adam7Layout lay = stage_layout_adam7(info->h, info->w, info->ctype, info->depth);
+  for (int p = 0; p < kAdam7Passes; ++p) {
+    out->off[p] = lay.off[p], out->line_off[p] = lay.line_off[p];
+    out->h[p] = lay.h[p], out->w[p] = lay.w[p];
+  }
+  out->filtered_bytes = lay.filtered_bytes, out->palette_off = lay.palette_off, out->stage_bytes = lay.stage_bytes;
+  return 0;
+}
+
+int tcamd_host_png_inflate_adam7(const uint8_t* blob, uint64_t n, uint8_t* out, uint64_t cap, char* msg, int msg_cap) {
+  return guarded(msg, msg_cap, [&](const Ctx& cx) {
+    const Parsed p = parse(cx, blob, n);
+    const TcamdPngInfo& info = p.info;
+    if (!info.interlace) cx.fail(TCAMD_PNG_UNSUPPORTED, "not an interlaced file");
+    const Adam7Layout lay = stage_layout_adam7(info.h, info.w, info.ctype, info.depth);
+    if (!out || cap < lay.stage_bytes) cx.fail(TCAMD_PNG_MALFORMED, "output buffer too small");
+    inflate_idat(cx, p, out, lay.filtered_bytes);
+    check_adam7_filter_bytes(cx, out, lay, info);
+    if (lay.palette_off) {
+      memset(out + lay.filtered_bytes, 0, lay.palette_off - lay.filtered_bytes);
+      write_palette(p.plte, out + lay.palette_off);
+    }
+  });
+}
+
+int tcamd_host_png_unfilter_adam7(const uint8_t* staged, uint64_t staged_bytes, const TcamdPngInfo* info, uint8_t* out,
+                                  uint64_t cap) {
+  if (!staged || !info || !out || info->interlace != 1) return -1;
+  if (info->h < 1 || info->w < 1 || info->h > kMaxDim || info->w > kMaxDim || !pair_ok(info->ctype, info->depth))
+    return -1;
+  const Adam7Layout lay = stage_layout_adam7(info->h, info->w, info->ctype, info->depth);
+  if (lay.filtered_bytes != info->filtered_bytes || staged_bytes < lay.stage_bytes) return -1;
+  if (cap < (uint64_t)info->h * info->w * out_channels(info->ctype)) return -1;
+  try {
+    unfilter_adam7(staged, lay, *info, staged + lay.palette_off, out);
+  } catch (const std::bad_alloc&) {
+    return -1;
+  }
+  return 0;
+}
+
 int tcamd_host_png_decode(const uint8_t* blob, uint64_t n, uint8_t* out, uint64_t cap, char* msg, int msg_cap) {
   return guarded(msg, msg_cap, [&](const Ctx& cx) {
     const Parsed p = parse(cx, blob, n);
@@ -280,15 +330,9 @@ int tcamd_host_png_decode(const uint8_t* blob, uint64_t n, uint8_t* out, uint64_
       unfilter(filt.data(), info.h, info.w, info.ctype, info.depth, pal, out, info.w, 0, 1, 0, 1);
       return;
     }
-    uint64_t at = 0;
-    for (const auto& a : kAdam7) {
-      const int pw = pass_size(info.w, a[0], a[2]), ph = pass_size(info.h, a[1], a[3]);
-      if (!pw || !ph) continue;
-      const uint32_t rb = row_bytes(pw, info.ctype, info.depth);
-      check_filter_bytes(cx, filt.data() + at, ph, rb, 0);
-      unfilter(filt.data() + at, ph, pw, info.ctype, info.depth, pal, out, info.w, a[0], a[2], a[1], a[3]);
-      at += (uint64_t)ph * (1 + rb);
-    }
+    const Adam7Layout lay = stage_layout_adam7(info.h, info.w, info.ctype, info.depth);
+    check_adam7_filter_bytes(cx, filt.data(), lay, info);
+    unfilter_adam7(filt.data(), lay, info, pal, out);
   });
 }
 

@@ -1,7 +1,8 @@
 // PNG on the host (libtcamd_host): chunk parse, inflate of the IDAT stream into
 // the staged bytes K25 png_unfilter (csrc/kernels/png.hip) reads, the unfilter
 // and sample conversion to uint8 HWC pixels, K25's bitwise twin, and the whole
-// decode, Adam7 included.  The per-byte arithmetic and the layout of the staged
+// decode, Adam7 included; for an interlaced file the same three steps in the
+// layout K25i png_unfilter_adam7 reads.  The per-byte arithmetic and the layout of the staged
 // bytes are csrc/kernels/png_math.h; the contract is written out in
 // tests/png_cases.py.
 #pragma once
@@ -49,5 +50,32 @@ int tcamd_host_png_unfilter(const uint8_t* staged, uint64_t staged_bytes, const 
 // The whole decode, either interlace method: out receives h * w * channels
 // bytes, HWC (cap is checked).
 int tcamd_host_png_decode(const uint8_t* blob, uint64_t n, uint8_t* out, uint64_t cap, char* msg, int msg_cap);
+
+// The staged bytes of an interlaced image, which K25i png_unfilter_adam7 reads
+// (tcamd_png::stage_layout_adam7): sub-image p of the seven is h[p] x w[p] (one
+// of them 0: it has no bytes) and its filtered scanlines start at off[p], end
+// to end in the order of the zlib stream, filtered_bytes in all; then for
+// colour type 3 the palette at palette_off; then for each sub-image of more
+// rows than a pass of the kernel one scanline of scratch at line_off[p], which
+// only the kernel touches.  An offset that is 0 means the part is absent
+// (off[0] is 0 by itself).  stage_bytes is the whole; the stage_bytes of
+// TcamdPngInfo stays filtered_bytes for an interlaced file.
+struct TcamdPngAdam7Layout {
+  uint64_t off[7], line_off[7];
+  int32_t h[7], w[7];
+  uint64_t filtered_bytes, palette_off, stage_bytes;
+};
+// Returns 0, or -1 when info is not one tcamd_host_png_parse gives for an interlaced file.
+int tcamd_host_png_adam7_layout(const TcamdPngInfo* info, TcamdPngAdam7Layout* out);
+// tcamd_host_png_inflate for an interlaced file (a non-interlaced one is
+// TCAMD_PNG_UNSUPPORTED): inflates straight into out (at least the layout's
+// stage_bytes; cap is checked), checks the filter-type bytes of every
+// sub-image, writes the palette and leaves the scratch scanlines alone.
+int tcamd_host_png_inflate_adam7(const uint8_t* blob, uint64_t n, uint8_t* out, uint64_t cap, char* msg, int msg_cap);
+// K25i on the host: the staged bytes tcamd_host_png_inflate_adam7 wrote for info
+// -> info.pixel_bytes of uint8 HWC in out.  Returns 0, or -1 as
+// tcamd_host_png_unfilter does, here for an info that is not interlaced.
+int tcamd_host_png_unfilter_adam7(const uint8_t* staged, uint64_t staged_bytes, const TcamdPngInfo* info, uint8_t* out,
+                                  uint64_t cap);
 
 }  // extern "C"

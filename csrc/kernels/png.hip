@@ -38,6 +38,12 @@
 // [dst, dst + h * w * channels) is written, and of src only the scratch scanline.
 // A step is bound by its instructions (one wave per SIMD; loading the filtered
 // bytes four steps ahead instead of one changed nothing: profiles/r15_png.md).
+//
+// K25i png_unfilter_adam7 is the same wavefront, the same text, for an
+// interlaced file, whose seven sub-images are independent of each other: one
+// workgroup per (image, sub-image), all seven at once, and only the store
+// differs (the Map of unfilter_image).  Its launch lasts as long as pass 7, half
+// the rows at full width (profiles/r24_png_adam7.md).
 
 #include <type_traits>
 
@@ -59,6 +65,19 @@ struct PngParams {
   uint8_t* dst[kMaxImgs];
   int32_t h[kMaxImgs], w[kMaxImgs];
   uint8_t ctype[kMaxImgs], depth[kMaxImgs];
+};
+
+// K25i's table: one record of 32 bytes per image, read whole at img + (block / 7) * 32.
+// With PngParams' columns the compiler formed the address of h[block / 7] as
+// (table + n) + 3 * n; a scalar load rounds that base down to a multiple of 4,
+// so images whose index is no multiple of 4 were decoded with a neighbour's height.
+struct Adam7Img {
+  uint8_t* src;
+  uint8_t* dst;
+  int32_t h, w, ctype, depth;
+};
+struct Adam7Params {
+  Adam7Img img[kMaxImgs];
 };
 
 struct Lds {
@@ -83,11 +102,26 @@ __device__ __forceinline__ void store_unit(uint8_t* p, Unit<BPP> v) {
   for (int k = 0; k < BPP; ++k) p[k] = (uint8_t)(v >> (8 * k));
 }
 
-template <int BPP>
-__device__ __forceinline__ void unfilter_image(Lds& s, uint8_t* src, uint8_t* __restrict__ dst, int H, int W,
-                                               int ctype, int depth) {
+// Where the pixels of the H x W scanlines go in dst.  Whole: dst is that image.
+// Laced: the scanlines are one Adam7 sub-image, and its pixel (x, y) is pixel
+// (x0 + x * dx, y0 + y * dy) of the full_w-wide image at dst.
+struct Whole {
+  __device__ __forceinline__ size_t at(int x, int y, int W) const { return (size_t)y * W + x; }
+};
+struct Laced {
+  int x0, y0, dx, dy, full_w;
+  __device__ __forceinline__ size_t at(int x, int y, int) const {
+    return (size_t)(y0 + y * dy) * full_w + (x0 + x * dx);
+  }
+};
+
+// H x W filtered scanlines at src (palette: kPaletteBytes of colour type 3, 16-byte
+// aligned; line: the scratch scanline of more than kRowsPerPass rows) -> pixels in dst
+template <int BPP, class Map>
+__device__ __forceinline__ void unfilter_image(Lds& s, const uint8_t* src, const uint8_t* palette, uint8_t* line,
+                                               uint8_t* __restrict__ dst, int H, int W, int ctype, int depth,
+                                               const Map map) {
   using U = Unit<BPP>;
-  const StageLayout lay = stage_layout(H, W, ctype, depth);
   const uint32_t rb = row_bytes(W, ctype, depth);
   const int nunits = (int)(rb / BPP);
   const int nchunks = (nunits + kColChunk - 1) / kColChunk;
@@ -97,10 +131,9 @@ __device__ __forceinline__ void unfilter_image(Lds& s, uint8_t* src, uint8_t* __
   const int wave = threadIdx.x / kWave, lane = threadIdx.x % kWave;
   const int nc = out_channels(ctype);
   const int per = depth < 8 ? 8 / depth : 1;  // pixels in a unit
-  uint8_t* line = src + lay.line_off;
 
   if (ctype == kPalette) {
-    const uint32_t* p = reinterpret_cast<const uint32_t*>(src + lay.palette_off);
+    const uint32_t* p = reinterpret_cast<const uint32_t*>(palette);
     for (int i = threadIdx.x; i < kPaletteBytes / 4; i += kBlock) reinterpret_cast<uint32_t*>(s.pal)[i] = p[i];
   }
   __syncthreads();
@@ -150,11 +183,13 @@ __device__ __forceinline__ void unfilter_image(Lds& s, uint8_t* src, uint8_t* __
           }
           a = r;
           c = b;
-          if (depth >= 8) {
-            convert_pixel(ctype, depth, px, s.pal, dst + ((size_t)row * W + x) * nc);
+          if (depth == 16) {  // the depth as a constant: px is indexed by it and stays in registers
+            convert_pixel(ctype, 16, px, s.pal, dst + map.at(x, row, W) * nc);
+          } else if (depth == 8) {
+            convert_pixel(ctype, 8, px, s.pal, dst + map.at(x, row, W) * nc);
           } else {
             for (int k = 0; k < per && x * per + k < W; ++k)
-              convert_low(ctype, depth, low_sample(px[0], depth, k), s.pal, dst + ((size_t)row * W + x * per + k) * nc);
+              convert_low(ctype, depth, low_sample(px[0], depth, k), s.pal, dst + map.at(x * per + k, row, W) * nc);
           }
           if (lane == kWave - 1) {
             if (hand_out) hand_out[u] = r;
@@ -167,19 +202,52 @@ __device__ __forceinline__ void unfilter_image(Lds& s, uint8_t* src, uint8_t* __
   }
 }
 
+template <class Map>
+__device__ __forceinline__ void unfilter_by_bpp(Lds& s, const uint8_t* src, const uint8_t* palette, uint8_t* line,
+                                                uint8_t* dst, int H, int W, int ctype, int depth, const Map map) {
+  switch (filter_bpp(ctype, depth)) {
+    case 1: unfilter_image<1>(s, src, palette, line, dst, H, W, ctype, depth, map); break;
+    case 2: unfilter_image<2>(s, src, palette, line, dst, H, W, ctype, depth, map); break;
+    case 3: unfilter_image<3>(s, src, palette, line, dst, H, W, ctype, depth, map); break;
+    case 4: unfilter_image<4>(s, src, palette, line, dst, H, W, ctype, depth, map); break;
+    case 6: unfilter_image<6>(s, src, palette, line, dst, H, W, ctype, depth, map); break;
+    default: unfilter_image<8>(s, src, palette, line, dst, H, W, ctype, depth, map); break;
+  }
+}
+
 // grid: x = image
 __global__ void __launch_bounds__(kBlock) png_unfilter(PngParams p) {
   __shared__ __attribute__((aligned(16))) Lds s;
   const int n = blockIdx.x;
   const int H = p.h[n], W = p.w[n], ctype = p.ctype[n], depth = p.depth[n];
-  switch (filter_bpp(ctype, depth)) {
-    case 1: unfilter_image<1>(s, p.src[n], p.dst[n], H, W, ctype, depth); break;
-    case 2: unfilter_image<2>(s, p.src[n], p.dst[n], H, W, ctype, depth); break;
-    case 3: unfilter_image<3>(s, p.src[n], p.dst[n], H, W, ctype, depth); break;
-    case 4: unfilter_image<4>(s, p.src[n], p.dst[n], H, W, ctype, depth); break;
-    case 6: unfilter_image<6>(s, p.src[n], p.dst[n], H, W, ctype, depth); break;
-    default: unfilter_image<8>(s, p.src[n], p.dst[n], H, W, ctype, depth); break;
+  const StageLayout lay = stage_layout(H, W, ctype, depth);
+  uint8_t* src = p.src[n];
+  unfilter_by_bpp(s, src, src + lay.palette_off, src + lay.line_off, p.dst[n], H, W, ctype, depth, Whole{});
+}
+
+// K25i.  grid: x = image * 7 + slot, and slot k takes sub-image 6 - k: the largest
+// (pass 7, half the rows at full width, the launch's critical path) is
+// dispatched first.  The seven workgroups of an image run K25's wavefront side
+// by side, each over its own scanlines, zero row above, scratch scanline and
+// barrier count; they share the staged bytes they only read, and the pixels of
+// dst, which the seven sub-images partition.
+__global__ void __launch_bounds__(kBlock) png_unfilter_adam7(Adam7Params p) {
+  __shared__ __attribute__((aligned(16))) Lds s;
+  const int n = blockIdx.x / kAdam7Passes, pass = kAdam7Passes - 1 - (int)(blockIdx.x % kAdam7Passes);
+  const Adam7Img im = p.img[n];
+  const int W = im.w, ctype = im.ctype, depth = im.depth;
+  const Adam7Layout lay = stage_layout_adam7(im.h, W, ctype, depth);
+  uint64_t off = 0, line_off = 0;
+  int ph = 0, pw = 0;
+#pragma unroll
+  for (int k = 0; k < kAdam7Passes; ++k) {  // no indexing by pass: the layout stays in registers
+    if (k == pass) off = lay.off[k], line_off = lay.line_off[k], ph = lay.h[k], pw = lay.w[k];
   }
+  if (pw == 0 || ph == 0) return;  // an empty sub-image: the whole workgroup leaves, before any barrier
+  const Adam7Pass a = adam7_pass(pass);
+  uint8_t* src = im.src;
+  unfilter_by_bpp(s, src + off, src + lay.palette_off, src + line_off, im.dst, ph, pw, ctype, depth,
+                  Laced{a.x0, a.y0, a.dx, a.dy, W});
 }
 
 }  // namespace
@@ -191,6 +259,22 @@ extern "C" void tcamd_png_unfilter_geometry(int32_t* out3) {
   out3[1] = kRowsPerPass;
   out3[2] = kColChunk;
 }
+
+namespace {
+
+// the argument checks of both entry points; lace is the interlace method they take
+bool args_ok(void* const* srcs, const int32_t* h, const int32_t* w, const int32_t* ctype, const int32_t* depth,
+             const int32_t* interlace, int n_imgs, void* const* dsts, int lace) {
+  if (!srcs || !h || !w || !ctype || !depth || !interlace || !dsts) return false;
+  for (int i = 0; i < n_imgs; ++i) {
+    if (!srcs[i] || !dsts[i] || ((uintptr_t)srcs[i]) % 16) return false;
+    if (h[i] < 1 || w[i] < 1 || h[i] > kMaxDim || w[i] > kMaxDim) return false;
+    if (interlace[i] != lace || !pair_ok(ctype[i], depth[i])) return false;
+  }
+  return true;
+}
+
+}  // namespace
 
 // srcs / h / w / ctype / depth / interlace / dsts: host arrays of n_imgs entries.
 // srcs[i] is a device pointer, 16-byte aligned, to image i's staged bytes in the
@@ -207,12 +291,7 @@ extern "C" int tcamd_png_unfilter(void* const* srcs, const int32_t* h, const int
                                   void* stream) {
   if (n_imgs < 0) return hipErrorInvalidValue;
   if (n_imgs == 0) return hipSuccess;
-  if (!srcs || !h || !w || !ctype || !depth || !interlace || !dsts) return hipErrorInvalidValue;
-  for (int i = 0; i < n_imgs; ++i) {
-    if (!srcs[i] || !dsts[i] || ((uintptr_t)srcs[i]) % 16) return hipErrorInvalidValue;
-    if (h[i] < 1 || w[i] < 1 || h[i] > kMaxDim || w[i] > kMaxDim) return hipErrorInvalidValue;
-    if (interlace[i] != 0 || !pair_ok(ctype[i], depth[i])) return hipErrorInvalidValue;
-  }
+  if (!args_ok(srcs, h, w, ctype, depth, interlace, n_imgs, dsts, 0)) return hipErrorInvalidValue;
   hipStream_t s = (hipStream_t)stream;
   for (int base = 0; base < n_imgs; base += kMaxImgs) {
     PngParams p;
@@ -227,6 +306,33 @@ extern "C" int tcamd_png_unfilter(void* const* srcs, const int32_t* h, const int
       p.depth[i] = (uint8_t)depth[j];
     }
     hipLaunchKernelGGL(png_unfilter, dim3((unsigned)cnt), dim3(kBlock), 0, s, p);
+    const int rc = hipGetLastError();
+    if (rc != hipSuccess) return rc;
+  }
+  return hipSuccess;
+}
+
+// K25i: tcamd_png_unfilter for interlaced (Adam7) images.  The arguments and
+// the checks are the same, but interlace[i] must be 1 and srcs[i] holds the
+// staged bytes of stage_layout_adam7 (what tcamd_host_png_inflate_adam7 writes,
+// plus one scratch scanline per sub-image of more than kRowsPerPass rows, which
+// the kernel writes).  Seven workgroups per image, one per sub-image, 64 images
+// per launch.  Every byte of dsts[i] is written by exactly one of them.
+extern "C" int tcamd_png_unfilter_adam7(void* const* srcs, const int32_t* h, const int32_t* w, const int32_t* ctype,
+                                        const int32_t* depth, const int32_t* interlace, int n_imgs, void* const* dsts,
+                                        void* stream) {
+  if (n_imgs < 0) return hipErrorInvalidValue;
+  if (n_imgs == 0) return hipSuccess;
+  if (!args_ok(srcs, h, w, ctype, depth, interlace, n_imgs, dsts, 1)) return hipErrorInvalidValue;
+  hipStream_t s = (hipStream_t)stream;
+  for (int base = 0; base < n_imgs; base += kMaxImgs) {
+    Adam7Params p;
+    const int cnt = n_imgs - base < kMaxImgs ? n_imgs - base : kMaxImgs;
+    for (int i = 0; i < kMaxImgs; ++i) {
+      const int j = base + (i < cnt ? i : 0);
+      p.img[i] = Adam7Img{static_cast<uint8_t*>(srcs[j]), static_cast<uint8_t*>(dsts[j]), h[j], w[j], ctype[j], depth[j]};
+    }
+    hipLaunchKernelGGL(png_unfilter_adam7, dim3((unsigned)(cnt * kAdam7Passes)), dim3(kBlock), 0, s, p);
     const int rc = hipGetLastError();
     if (rc != hipSuccess) return rc;
   }

@@ -1,7 +1,8 @@
 // The per-byte arithmetic of the PNG decode after inflate, shared by the host
 // decoder (csrc/host/png.cc) and K25 png_unfilter (csrc/kernels/png.hip) so that
 // the two agree bit for bit: the Paeth predictor, the five reconstruction rules,
-// the sample conversion to uint8, and the layout of an image's staged bytes.
+// the sample conversion to uint8, the layout of an image's staged bytes, and
+// for an interlaced file (K25i png_unfilter_adam7) the Adam7 table and layout.
 // The contract is written out in tests/png_cases.py, which implements it a
 // second time in Python.
 #pragma once
@@ -78,6 +79,58 @@ TCAMD_PNG_HD StageLayout stage_layout(int h, int w, int ctype, int depth) {
   if (h > kRowsPerPass) {
     s.line_off = (end + 15) / 16 * 16;
     end = s.line_off + rb;
+  }
+  s.stage_bytes = end;
+  return s;
+}
+
+// The seven Adam7 sub-images of an interlaced file, in the order of the file:
+// sub-image pixel (x, y) of pass p is pixel (x0 + x * dx, y0 + y * dy) of the image.
+constexpr int kAdam7Passes = 7;
+struct Adam7Pass {
+  int x0, y0, dx, dy;
+};
+TCAMD_PNG_HD Adam7Pass adam7_pass(int p) {
+  constexpr int t[kAdam7Passes][4] = {{0, 0, 8, 8}, {4, 0, 8, 8}, {0, 4, 4, 8}, {2, 0, 4, 4},
+                                      {0, 2, 2, 4}, {1, 0, 2, 2}, {0, 1, 1, 2}};
+  return Adam7Pass{t[p][0], t[p][1], t[p][2], t[p][3]};
+}
+// the columns (rows) of a sub-image that starts at first and steps by step, of full columns (rows)
+TCAMD_PNG_HD int pass_size(int full, int first, int step) { return full > first ? (full - first + step - 1) / step : 0; }
+
+// An interlaced image's staged bytes: the filtered scanlines of the seven
+// sub-images end to end, as the zlib stream delivers them (an empty sub-image,
+// w == 0 or h == 0, has none); for colour type 3 the palette, kPaletteBytes at
+// the next 16-byte boundary; then, for each sub-image of more than kRowsPerPass
+// rows, one scanline of scratch of that sub-image's row_bytes, each at the
+// next 16-byte boundary (line_off; 0 = none), which K25i uses as K25 uses
+// StageLayout::line_off.  off[p] is where sub-image p starts.
+struct Adam7Layout {
+  uint64_t off[kAdam7Passes], line_off[kAdam7Passes];
+  int32_t h[kAdam7Passes], w[kAdam7Passes];
+  uint64_t filtered_bytes, palette_off, stage_bytes;
+};
+TCAMD_PNG_HD Adam7Layout stage_layout_adam7(int h, int w, int ctype, int depth) {
+  Adam7Layout s;
+  uint64_t end = 0;
+  for (int p = 0; p < kAdam7Passes; ++p) {
+    const Adam7Pass a = adam7_pass(p);
+    s.w[p] = pass_size(w, a.x0, a.dx), s.h[p] = pass_size(h, a.y0, a.dy);
+    s.off[p] = end;
+    if (s.w[p] && s.h[p]) end += (uint64_t)s.h[p] * (1 + row_bytes(s.w[p], ctype, depth));
+  }
+  s.filtered_bytes = end;
+  s.palette_off = 0;
+  if (ctype == kPalette) {
+    s.palette_off = (end + 15) / 16 * 16;
+    end = s.palette_off + kPaletteBytes;
+  }
+  for (int p = 0; p < kAdam7Passes; ++p) {
+    s.line_off[p] = 0;
+    if (s.w[p] && s.h[p] > kRowsPerPass) {
+      s.line_off[p] = (end + 15) / 16 * 16;
+      end = s.line_off[p] + row_bytes(s.w[p], ctype, depth);
+    }
   }
   s.stage_bytes = end;
   return s;

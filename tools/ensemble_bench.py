@@ -7,6 +7,7 @@
     python tools/ensemble_bench.py --kernel --jpeg  # K22 jpeg_decode, K23 jpeg_huffman alone: 8 copies of that fixture
     python tools/ensemble_bench.py --png          # served: that fixture's pixels as a PNG, TCAMD_DEVICE_PNG 1 against 0
     python tools/ensemble_bench.py --kernel --png # K25 png_unfilter alone, next to the host's unfilter and inflate
+    python tools/ensemble_bench.py --png --adam7  # the same pixels interlaced: TCAMD_DEVICE_PNG_ADAM7 1 against 0 (--kernel: K25i)
 
 The served mode starts the bench server (densenet_onnx, preprocess_inception
 and the ensemble, 2 instances) as a child process, keeps ``--concurrency``
@@ -228,12 +229,11 @@ def jpeg_kernel_time(n, iters, scale=1, path=None):
 _PNG_FILTERS = ("none", "sub", "up", "average", "paeth")
 
 
-def write_png(img, how="adaptive"):
-    """An 8-bit RGB or grey PNG of the uint8 HWC array ``img``: filter type ``how`` on every row, or
-    per row the one of the five with the smallest sum of absolute (signed) differences."""
-    import struct
-    import zlib
+_ADAM7 = ((0, 0, 8, 8), (4, 0, 8, 8), (0, 4, 4, 8), (2, 0, 4, 4), (0, 2, 2, 4), (1, 0, 2, 2), (0, 1, 1, 2))  # x0 y0 dx dy
 
+
+def _filtered(img, how):
+    """The filtered scanlines of the uint8 HWC array ``img`` (an image, or one Adam7 sub-image)."""
     import numpy as np
 
     h, w, c = img.shape
@@ -250,12 +250,27 @@ def write_png(img, how="adaptive"):
     else:
         pick = np.full(h, _PNG_FILTERS.index(how))
     rows = cand[pick, np.arange(h)]
-    filt = np.concatenate([pick[:, None].astype(np.uint8), rows], axis=1).tobytes()
+    return np.concatenate([pick[:, None].astype(np.uint8), rows], axis=1).tobytes()
+
+
+def write_png(img, how="adaptive", adam7=False):
+    """An 8-bit RGB or grey PNG of the uint8 HWC array ``img``: filter type ``how`` on every row, or
+    per row the one of the five with the smallest sum of absolute (signed) differences; ``adam7``
+    writes it interlaced, every sub-image filtered on its own."""
+    import struct
+    import zlib
+
+    h, w, c = img.shape
+    if adam7:
+        subs = [img[y0::dy, x0::dx] for x0, y0, dx, dy in _ADAM7]
+        filt = b"".join(_filtered(sub, how) for sub in subs if sub.size)
+    else:
+        filt = _filtered(img, how)
 
     def chunk(kind, data):
         return struct.pack(">I", len(data)) + kind + data + struct.pack(">I", zlib.crc32(kind + data) & 0xffffffff)
 
-    return b"\x89PNG\r\n\x1a\n" + chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, 8, 2 if c == 3 else 0, 0, 0, 0)) \
+    return b"\x89PNG\r\n\x1a\n" + chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, 8, 2 if c == 3 else 0, 0, 0, int(adam7))) \
         + chunk(b"IDAT", zlib.compress(filt, 6)) + chunk(b"IEND", b"")
 
 
@@ -268,7 +283,7 @@ def png_fixture(args):
         with open(args.png_file, "rb") as f:
             blob = f.read()
     else:
-        blob = write_png(hc.jpeg_decode(jpeg_fixture()), args.png_filter)
+        blob = write_png(hc.jpeg_decode(jpeg_fixture()), args.png_filter, args.adam7)
     return blob, hc.png_decode(blob)
 
 
@@ -292,25 +307,28 @@ def png_kernel_time(args):
     hc = host_codec.load()
     blob, want = png_fixture(args)
     info = hc.png_parse(blob)
-    staged = host_codec.aligned_buffer(info.stage_bytes)
-    inflate = _host_ms(lambda: hc.png_inflate(blob, staged))
-    unfilter = _host_ms(lambda: hc.png_unfilter(staged, info))
+    laced = bool(info.interlace)
+    stage_bytes = hc.png_adam7_layout(info).stage_bytes if laced else info.stage_bytes
+    staged = host_codec.aligned_buffer(stage_bytes)
+    inflate = _host_ms(lambda: (hc.png_inflate_adam7 if laced else hc.png_inflate)(blob, staged))
+    unfilter = _host_ms(lambda: (hc.png_unfilter_adam7 if laced else hc.png_unfilter)(staged, info))
     decode = _host_ms(lambda: hc.png_decode(blob))
     n = max(1, args.images)
-    stride = -(-info.stage_bytes // 16) * 16
+    stride = -(-stage_bytes // 16) * 16
     src = torch.from_numpy(np.concatenate([np.pad(staged, (0, stride - staged.size))] * n)).cuda()
     dst = torch.zeros(n, info.pixel_bytes, device="cuda", dtype=torch.uint8)
     s = torch.cuda.current_stream().cuda_stream
     srcs = [src.data_ptr() + i * stride for i in range(n)]
     dsts = [dst[i].data_ptr() for i in range(n)]
-    line = {"kernel": "K25 png_unfilter", "image": list(info.shape), "colour_type": info.ctype, "depth": info.depth,
+    line = {"kernel": "K25i png_unfilter_adam7" if laced else "K25 png_unfilter", "image": list(info.shape), "colour_type": info.ctype, "depth": info.depth,
             "filter": "file" if args.png_file else args.png_filter, "png_bytes": len(blob),
-            "stage_bytes": int(info.stage_bytes), "pixel_bytes": int(info.pixel_bytes), "timed_launches": args.iters}
-    rows = np.frombuffer(staged[:info.filtered_bytes], dtype=np.uint8).reshape(info.h, -1)[:, 0]
-    line["rows_per_filter_type"] = [int((rows == f).sum()) for f in range(5)]
+            "stage_bytes": int(stage_bytes), "pixel_bytes": int(info.pixel_bytes), "timed_launches": args.iters}
+    if not laced:
+        rows = np.frombuffer(staged[:info.filtered_bytes], dtype=np.uint8).reshape(info.h, -1)[:, 0]
+        line["rows_per_filter_type"] = [int((rows == f).sum()) for f in range(5)]
     for m in sorted({1, n}):
         def launch():
-            hip.png_unfilter(srcs[:m], [info] * m, dsts[:m], stream=s)
+            (hip.png_unfilter_adam7 if laced else hip.png_unfilter)(srcs[:m], [info] * m, dsts[:m], stream=s)
 
         for _ in range(5):
             launch()
@@ -331,7 +349,8 @@ def png_kernel_time(args):
 
 
 def served_png(args):
-    """Two servers, TCAMD_DEVICE_PNG=1 and =0, loaded in turn with the PNG and with its TCIMG twin."""
+    """Two servers, TCAMD_DEVICE_PNG=1 and =0 (with ``--adam7``: TCAMD_DEVICE_PNG_ADAM7=1 and =0, and
+    the PNG interlaced), loaded in turn with the PNG and with its TCIMG twin."""
     import numpy as np
 
     import tritonclient.grpc as grpcclient
@@ -348,7 +367,7 @@ def served_png(args):
         for knob in ("1", "0"):
             servers[knob] = ServerProcess(device=0, models="densenet_onnx,preprocess_inception,preprocess_inception_ensemble",
                                           log_path=log and "%s.png%s" % (log, knob), extra_args=["--instance-count", "2"],
-                                          env={"TCAMD_DEVICE_PNG": knob})
+                                          env={"TCAMD_DEVICE_PNG_ADAM7" if args.adam7 else "TCAMD_DEVICE_PNG": knob})
         first = {}
         for knob, srv in servers.items():
             srv.wait_ready(timeout=900, model="preprocess_inception_ensemble")
@@ -367,7 +386,8 @@ def served_png(args):
                 for knob in ("1", "0"):
                     for enc in ("PNG", "TCIMG"):
                         res = closed_loop(clients[knob], grpcclient, inputs[enc], conc, args.warmup, args.seconds, params)
-                        res.update(round=rep_, device_png=int(knob), encoding=enc, image=list(pixels.shape),
+                        res.update(round=rep_, **{"device_png_adam7" if args.adam7 else "device_png": int(knob)})
+                        res.update(encoding=enc, image=list(pixels.shape),
                                    blob_bytes=len(blobs[enc]), antialias=args.antialias,
                                    filter="file" if args.png_file else args.png_filter,
                                    all_four_first_answers_equal=bool(same))
@@ -569,6 +589,9 @@ def main():
                          "next to the TCIMG of the same pixels; K25 alone (--kernel)")
     ap.add_argument("--png-filter", choices=("adaptive",) + _PNG_FILTERS, default="adaptive",
                     help="--png: the filter type of every row of the PNG this tool writes")
+    ap.add_argument("--adam7", action="store_true",
+                    help="--png: write the PNG interlaced; served, the two servers differ in TCAMD_DEVICE_PNG_ADAM7; "
+                         "with --kernel, K25i png_unfilter_adam7 is what is timed")
     ap.add_argument("--png-file", default="", metavar="PATH", help="--png: this PNG file instead")
     ap.add_argument("--reps", type=int, default=3, help="--png, served: rounds over the concurrencies and arms")
     ap.add_argument("--concurrency", type=int, nargs="+", default=[1, 8])

@@ -11,6 +11,7 @@ events, peer access.  Kernels (csrc/kernels/*.hip, gfx950):
 * :func:`jpeg_huffman`    K23 Huffman decode of packed JPEG scans into the coefficients K22 reads
 * :func:`jpeg_huffman_wide`  K24 the same across workgroups: scans up to 32 MiB, the compact buffer of any scale
 * :func:`png_unfilter`    K25 PNG unfilter + palette / depth / alpha conversion of inflated scanlines
+* :func:`png_unfilter_adam7`  K25i the same for interlaced files, the seven sub-images on seven workgroups
 * :func:`compare_expected` K26 outputs against expectations on the device: mismatches, first index, largest difference
 * :func:`batched_copy`    K7 one-launch gather/concat/scatter of byte ranges
 * :func:`pack_bytes`      K2 BYTES serialisation (LDS block scan + scatter)
@@ -169,6 +170,14 @@ _SIGS = {
     ),
     "tcamd_png_unfilter_geometry": ([ctypes.POINTER(ctypes.c_int32)], None),
     "tcamd_png_unfilter": (
+        [
+            ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32),
+            ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32),
+            ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.c_void_p,
+        ],
+        ctypes.c_int,
+    ),
+    "tcamd_png_unfilter_adam7": (
         [
             ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32),
             ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32),
@@ -968,14 +977,31 @@ def png_unfilter(srcs, infos, dsts, stream=None):
     parse, a side outside [1, :data:`RESIZE_MAX_DIM`], a colour type / depth
     pair PNG does not have, or a null or misaligned source raises
     (hipErrorInvalidValue) without a launch."""
+    _png_call("png_unfilter", srcs, infos, dsts, stream)
+
+
+def _png_call(name, srcs, infos, dsts, stream):
     n = len(srcs)
     if len(infos) != n or len(dsts) != n:
-        raise ValueError("png_unfilter: srcs, infos and dsts must have one entry per image")
+        raise ValueError("%s: srcs, infos and dsts must have one entry per image" % name)
     s = (ctypes.c_void_p * max(n, 1))(*[int(p) for p in srcs])
     d = (ctypes.c_void_p * max(n, 1))(*[int(p) for p in dsts])
     cols = [(ctypes.c_int32 * max(n, 1))(*[int(getattr(i, f)) for i in infos])
             for f in ("h", "w", "ctype", "depth", "interlace")]
-    _check(_load().tcamd_png_unfilter(s, *cols, n, d, _vp(stream)), "png_unfilter")
+    _check(getattr(_load(), "tcamd_" + name)(s, *cols, n, d, _vp(stream)), name)
+
+
+def png_unfilter_adam7(srcs, infos, dsts, stream=None):
+    """K25i: :func:`png_unfilter` for interlaced (Adam7) images, the seven
+    sub-images of an image on seven workgroups at once.  ``srcs[i]`` is a
+    device pointer, 16-byte aligned, to the staged bytes of
+    ``HostCodec.png_adam7_layout``: what ``HostCodec.png_inflate_adam7`` wrote,
+    and behind it the scratch scanlines, which the kernel writes; ``infos[i]``
+    is the parse, with ``interlace`` 1; ``dsts[i]`` receives the ``h * w *
+    channels`` uint8 HWC pixels, bitwise those of
+    ``HostCodec.png_unfilter_adam7``.  64 images per launch.  The refusals are
+    those of :func:`png_unfilter`, here of a parse that is not interlaced."""
+    _png_call("png_unfilter_adam7", srcs, infos, dsts, stream)
 
 
 COMPARE_MAX_PAIRS = dtypes.COMPARE_MAX_PAIRS

@@ -50,6 +50,20 @@ class PngInfo(ctypes.Structure):
         return (self.h, self.w, self.channels)
 
 
+class PngAdam7Layout(ctypes.Structure):
+    """TcamdPngAdam7Layout of csrc/host/png.h: the staged bytes K25i
+    ``png_unfilter_adam7`` reads (``stage_bytes`` in all).  Sub-image p of the
+    seven is ``h[p] x w[p]`` (empty when either is 0) and its filtered
+    scanlines start at ``off[p]``, end to end as the zlib stream delivers them
+    (``filtered_bytes``); then the palette of colour type 3 at ``palette_off``;
+    then one scanline of scratch at ``line_off[p]`` for each sub-image of more
+    rows than a pass of the kernel (0 = absent)."""
+
+    _fields_ = [("off", ctypes.c_uint64 * 7), ("line_off", ctypes.c_uint64 * 7), ("h", ctypes.c_int32 * 7),
+                ("w", ctypes.c_int32 * 7), ("filtered_bytes", ctypes.c_uint64), ("palette_off", ctypes.c_uint64),
+                ("stage_bytes", ctypes.c_uint64)]
+
+
 PNG_SIGNATURE = b"\x89PNG\r\n\x1a\n"
 _PNG_KIND = {1: "unsupported PNG: ", 2: "malformed PNG: "}
 
@@ -114,13 +128,15 @@ class HostCodec:
         lib.tcamd_host_png_parse.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(PngInfo), ctypes.c_char_p,
                                              ctypes.c_int]
         lib.tcamd_host_png_parse.restype = ctypes.c_int
-        for fn in (lib.tcamd_host_png_inflate, lib.tcamd_host_png_decode):
+        for fn in (lib.tcamd_host_png_inflate, lib.tcamd_host_png_decode, lib.tcamd_host_png_inflate_adam7):
             fn.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_char_p,
                            ctypes.c_int]
             fn.restype = ctypes.c_int
-        lib.tcamd_host_png_unfilter.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(PngInfo), ctypes.c_void_p,
-                                                ctypes.c_uint64]
-        lib.tcamd_host_png_unfilter.restype = ctypes.c_int
+        for fn in (lib.tcamd_host_png_unfilter, lib.tcamd_host_png_unfilter_adam7):
+            fn.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(PngInfo), ctypes.c_void_p, ctypes.c_uint64]
+            fn.restype = ctypes.c_int
+        lib.tcamd_host_png_adam7_layout.argtypes = [ctypes.POINTER(PngInfo), ctypes.POINTER(PngAdam7Layout)]
+        lib.tcamd_host_png_adam7_layout.restype = ctypes.c_int
         lib.tcamd_host_compare_expected.argtypes = [ctypes.POINTER(dtypes.ComparePair), ctypes.c_int, ctypes.c_double,
                                                     ctypes.c_double, ctypes.POINTER(dtypes.CompareRecord)]
         lib.tcamd_host_compare_expected.restype = ctypes.c_int
@@ -605,6 +621,36 @@ class HostCodec:
         if self._lib.tcamd_host_png_unfilter(staged.ctypes.data, staged.size, ctypes.byref(info), out.ctypes.data,
                                              out.size):
             raise ValueError("png_unfilter: the staged bytes and the parse do not belong together")
+        return out
+
+    def png_adam7_layout(self, info):
+        """The :class:`PngAdam7Layout` of the parse of an interlaced file;
+        ``ValueError`` for any other parse."""
+        lay = PngAdam7Layout()
+        if self._lib.tcamd_host_png_adam7_layout(ctypes.byref(info), ctypes.byref(lay)):
+            raise ValueError("png_adam7_layout: not the parse of an interlaced PNG")
+        return lay
+
+    def png_inflate_adam7(self, blob, out):
+        """:meth:`png_inflate` for an interlaced ``blob`` (any other is
+        "unsupported PNG: not an interlaced file"): the IDAT stream straight
+        into the uint8 array ``out`` (at least ``stage_bytes`` of
+        :meth:`png_adam7_layout`), the seven sub-images end to end, then the
+        palette of colour type 3: the staged bytes
+        ``ops.hip.png_unfilter_adam7`` reads.  The scratch scanlines behind
+        them are not written."""
+        msg = ctypes.create_string_buffer(96)
+        self._png_check(self._lib.tcamd_host_png_inflate_adam7(blob, len(blob), out.ctypes.data, out.size, msg,
+                                                               len(msg)), msg)
+
+    def png_unfilter_adam7(self, staged, info):
+        """K25i ``png_unfilter_adam7`` on the host, bitwise: the staged bytes
+        of :meth:`png_inflate_adam7` (a uint8 array) -> uint8 [h, w, 1 or 3]."""
+        out = np.empty(info.shape, dtype=np.uint8)
+        staged = np.ascontiguousarray(staged, dtype=np.uint8)
+        if self._lib.tcamd_host_png_unfilter_adam7(staged.ctypes.data, staged.size, ctypes.byref(info),
+                                                   out.ctypes.data, out.size):
+            raise ValueError("png_unfilter_adam7: the staged bytes and the parse do not belong together")
         return out
 
     def png_decode(self, blob):

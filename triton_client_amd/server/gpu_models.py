@@ -475,8 +475,11 @@ class PreprocessInception(DeviceModel):
     headers and inflates its IDAT stream straight into the pinned staging area,
     the filtered scanlines go up in the batch's one copy, and K25
     ``png_unfilter`` writes the pixels where K20 / K21 read them, after the JPEG
-    kernels and before the resize on the slot's stream.  An interlaced PNG, one
-    that does not fit, or any PNG with the knob at 0 is decoded by the host and
+    kernels and before the resize on the slot's stream.  An interlaced PNG takes
+    that route with ``TCAMD_DEVICE_PNG_ADAM7=1`` (read at load; 0 by default):
+    K25i ``png_unfilter_adam7`` unfilters its seven sub-images at once, in one
+    call per batch after K25.  An interlaced PNG without that knob, a PNG
+    that does not fit, or any PNG with ``TCAMD_DEVICE_PNG`` at 0 is decoded by the host and
     goes on as raw pixels; the rows are the same bit for bit.  A PNG that does
     not decode fails its own request with the host decoder's message.
 
@@ -514,6 +517,7 @@ class PreprocessInception(DeviceModel):
         self.device_huffman = jpeg_stage.device_huffman_knob()
         self.device_huffman_wide = jpeg_stage.device_huffman_wide_knob()
         self.device_png = jpeg_stage.device_png_knob()
+        self.device_png_adam7 = jpeg_stage.device_png_adam7_knob()
         if not self._load_twin(_cpu.PreprocessInception, os.environ.get("TCAMD_DEVICE_PREPROCESS", "1") != "0"):
             return
         from triton_client_amd.ops import host_codec
@@ -539,7 +543,7 @@ class PreprocessInception(DeviceModel):
             return e
 
     def _open(self, blob, scale=1):
-        """A decoded image, or (blob, parse) of a JPEG or a non-interlaced PNG whose decode is
+        """A decoded image, or (blob, parse) of a JPEG or a PNG of a device route whose decode is
         still to be routed; ``scale`` is the request's ``jpeg_scale``, 0 for automatic."""
         from triton_client_amd.utils.image import PNG_SIGNATURE, decode_image
 
@@ -548,7 +552,7 @@ class PreprocessInception(DeviceModel):
             return blob, jpeg_stage.parse_at_scale(self._codec, blob, scale, self.H, self.W)
         if self.device_png and blob[:8] == PNG_SIGNATURE:
             info = self._codec.png_parse(blob)
-            if not info.interlace:
+            if not info.interlace or self.device_png_adam7:
                 return blob, info
         return decode_image(blob)
 
@@ -569,7 +573,7 @@ class PreprocessInception(DeviceModel):
 
         img_bytes = self.C * self.H * self.W * 4
         stage = jpeg_stage.StagePlan(slot["stage_np"][:self.STAGE_BYTES], self._codec, self.device_huffman,
-                                     self.device_huffman_wide, hip.RESIZE_MAX_DIM)
+                                     self.device_huffman_wide, hip.RESIZE_MAX_DIM, self.device_png_adam7)
         plan = []  # per request: (first_row, n_rows), or its exception
         for r in requests:
             mark = stage.mark()
@@ -607,8 +611,9 @@ class PreprocessInception(DeviceModel):
                 hip.memcpy_async(src, slot["stage_host"], stage.used, sh)
             ran = jpeg_stage.launch_decode(
                 hip, stage.jpegs, src, src, src + stage.workspace, stage.ws_need - 16,
-                lambda n: torch.empty(n, device=stream.device, dtype=torch.int32), sh, pngs=stage.pngs)
-            staged = sorted(stage.jpegs + stage.pngs + [j for j in stage.raws if j.pix is not None],
+                lambda n: torch.empty(n, device=stream.device, dtype=torch.int32), sh, pngs=stage.pngs,
+                adam7s=stage.adam7s)
+            staged = sorted(stage.jpegs + stage.pngs + stage.adam7s + [j for j in stage.raws if j.pix is not None],
                             key=lambda j: j.row)
             for aa in (False, True):
                 jobs = [j for j in staged if j.antialias == aa]

@@ -267,7 +267,7 @@ def preprocess_batch_device(resized, scaling="INCEPTION", fmt="NCHW", dtype="FP3
 
 def preprocess_raw_batch_device(images, c, h, w, scaling="INCEPTION", fmt="NCHW", dtype="FP32", device=0,
                                 antialias=False, device_huffman=None, jpeg_scale=1, device_huffman_wide=None,
-                                device_png=None):
+                                device_png=None, device_png_adam7=None):
     """``preprocess`` of a batch of decoded uint8 HWC images of any sizes on
     the GPU: the raw pixels go up in ONE uint8 host->device copy (a quarter of
     the bytes of the resized fp32 images, and no host resize), K20
@@ -293,7 +293,11 @@ def preprocess_raw_batch_device(images, c, h, w, scaling="INCEPTION", fmt="NCHW"
     that is not interlaced the host inflates the IDAT stream straight into the
     upload and K25 ``png_unfilter`` writes the pixels into the device-only
     allocation; otherwise the host decodes it and the pixels go up like an
-    array's.  The result is the same bit for bit.  Returns None when the
+    array's.  With ``device_png_adam7`` as well (default:
+    ``TCAMD_DEVICE_PNG_ADAM7`` in the environment, 0 unless set to 1) an
+    interlaced file is inflated into the upload too and K25i
+    ``png_unfilter_adam7`` writes its pixels; a batch makes at most one K25 and
+    one K25i call.  The result is the same bit for bit.  Returns None when the
     datatype has no device path (integer models)."""
     if dtype not in _DEVICE_DTYPES:
         return None
@@ -309,13 +313,15 @@ def preprocess_raw_batch_device(images, c, h, w, scaling="INCEPTION", fmt="NCHW"
         device_huffman_wide = jpeg_stage.device_huffman_wide_knob()
     if device_png is None:
         device_png = jpeg_stage.device_png_knob()
+    if device_png_adam7 is None:
+        device_png_adam7 = jpeg_stage.device_png_adam7_knob()
     items = []  # a uint8 HWC array, or (blob, parse) of a JPEG or of a PNG that K25 takes
     for im in images:
         if isinstance(im, (bytes, bytearray, memoryview)):
             blob = bytes(im)
             if blob[:8] == PNG_SIGNATURE:
                 info = _png_codec().png_parse(blob)
-                if device_png and not info.interlace:
+                if device_png and (not info.interlace or device_png_adam7):
                     items.append((blob, info))
                 else:
                     items.append(_png_codec().png_decode(blob))
@@ -333,7 +339,7 @@ def preprocess_raw_batch_device(images, c, h, w, scaling="INCEPTION", fmt="NCHW"
     # allocation, on the device only (``only`` bytes): the coefficient buffers K23 / K24 write, at 128-byte
     # boundaries, and the pixels K22 / K25 write.
     codec = _jpeg_codec() if any(isinstance(im, tuple) for im in items) else None
-    raws, jobs, pngs, up, only = [], [], [], 0, 0
+    raws, jobs, pngs, adam7s, up, only = [], [], [], [], 0, 0
     packs = {}  # row -> the stream its pack wrote
     for row, im in enumerate(items):
         if not isinstance(im, tuple):
@@ -343,8 +349,13 @@ def preprocess_raw_batch_device(images, c, h, w, scaling="INCEPTION", fmt="NCHW"
         blob, info = im
         if isinstance(info, host_codec.PngInfo):
             at = -(-up // 16) * 16
-            up = at + info.stage_bytes
-            pngs.append(jpeg_stage.PngJob(at, only, info, row, blob, antialias, 0))
+            if info.interlace:
+                layout = codec.png_adam7_layout(info)
+                up = at + layout.stage_bytes
+                adam7s.append(jpeg_stage.Adam7Job(at, only, info, layout, row, blob, antialias, 0))
+            else:
+                up = at + info.stage_bytes
+                pngs.append(jpeg_stage.PngJob(at, only, info, row, blob, antialias, 0))
             only += info.pixel_bytes
             continue
         room = None
@@ -375,6 +386,8 @@ def preprocess_raw_batch_device(images, c, h, w, scaling="INCEPTION", fmt="NCHW"
             raw[j.stream:j.stream + packs[j.row].size] = packs[j.row]
     for j in pngs:
         codec.png_inflate(j.blob, raw[j.stream:j.stream + j.info.stage_bytes])
+    for j in adam7s:
+        codec.png_inflate_adam7(j.blob, raw[j.stream:j.stream + j.layout.stage_bytes])
     src = torch.from_numpy(raw).to(dev, non_blocking=False)
     stream = torch.cuda.current_stream(dev).cuda_stream
     scratch = torch.empty(only, device=dev, dtype=torch.uint8)
@@ -382,8 +395,9 @@ def preprocess_raw_batch_device(images, c, h, w, scaling="INCEPTION", fmt="NCHW"
     need = hip.jpeg_huffman_wide_workspace(nsubs) if nsubs else 0
     workspace = torch.empty(need, device=dev, dtype=torch.uint8)
     ran = jpeg_stage.launch_decode(hip, jobs, src.data_ptr(), scratch.data_ptr(), workspace.data_ptr(), need,
-                                   lambda n: torch.empty(n, device=dev, dtype=torch.int32), stream, pngs=pngs)
-    staged = sorted(jobs + pngs + raws, key=lambda j: j.row)
+                                   lambda n: torch.empty(n, device=dev, dtype=torch.int32), stream, pngs=pngs,
+                                   adam7s=adam7s)
+    staged = sorted(jobs + pngs + adam7s + raws, key=lambda j: j.row)
     shape = (len(items), c, h, w) if fmt == "NCHW" else (len(items), h, w, c)
     dst = torch.empty(shape, device=dev, dtype=torch.float32 if dtype == "FP32" else torch.float16)
     scale, bias = _SCALE_BIAS[scaling](c)
@@ -395,5 +409,5 @@ def preprocess_raw_batch_device(images, c, h, w, scaling="INCEPTION", fmt="NCHW"
     if any(status.cpu().numpy().any() for _, status in ran):
         return preprocess_raw_batch_device(images, c, h, w, scaling, fmt, dtype, device, antialias,
                                            device_huffman=False, jpeg_scale=jpeg_scale, device_huffman_wide=0,
-                                           device_png=device_png)
+                                           device_png=device_png, device_png_adam7=device_png_adam7)
     return out

@@ -32,6 +32,16 @@ alone, so a PNG that does not fit is never inflated twice: like an interlaced
 one, or any PNG with the knob off, the caller decodes it on the host
 (``HostCodec.png_decode``) and offers the pixels as a raw image.
 
+With ``TCAMD_DEVICE_PNG_ADAM7=1`` on top of ``TCAMD_DEVICE_PNG=1`` an interlaced
+(Adam7) PNG has the same route through kernel K25i: ``HostCodec.png_inflate_adam7``
+inflates the stream, which is the filtered scanlines of the seven sub-images end
+to end, straight into the staging area, in the layout of
+``HostCodec.png_adam7_layout`` (the palette and one scratch scanline per
+sub-image of more rows than a pass behind them), and K25i
+``png_unfilter_adam7`` unfilters the seven sub-images side by side and stores
+each pixel where it belongs in the image.  The fit rule and the fallback are
+those of the non-interlaced route, with the layout's ``stage_bytes``.
+
 The staging area of a :class:`StagePlan` is ``capacity`` bytes that exist on
 the host (the view) and on the device:
 
@@ -77,6 +87,14 @@ def device_png_knob():
     return os.environ.get("TCAMD_DEVICE_PNG", "1") != "0"
 
 
+def device_png_adam7_knob():
+    """``TCAMD_DEVICE_PNG_ADAM7``: 1 = with ``TCAMD_DEVICE_PNG`` at 1, an
+    interlaced PNG is inflated into the staging area too and K25i
+    ``png_unfilter_adam7`` makes the pixels on the device; 0 (the default) =
+    the host decodes every interlaced file."""
+    return device_png_knob() and os.environ.get("TCAMD_DEVICE_PNG_ADAM7", "0") == "1"
+
+
 def parse_at_scale(codec, blob, jpeg_scale, h_out, w_out):
     """The parse of a JPEG blob at ``jpeg_scale`` (1, 2, 4 or 8); 0 picks
     :func:`utils.image.jpeg_auto_scale` for an ``h_out x w_out`` target."""
@@ -105,6 +123,18 @@ class PngJob(namedtuple("PngJob", "stream pix info row blob antialias request"))
     """A staged PNG: the offsets of its staged bytes (``info.stage_bytes`` in
     the upload region) and of its pixels; its parse; its row of the batch, its
     blob, its antialias flag and the index of its request."""
+
+    __slots__ = ()
+
+    @property
+    def shape(self):
+        return self.info.shape
+
+
+class Adam7Job(namedtuple("Adam7Job", "stream pix info layout row blob antialias request")):
+    """A staged interlaced PNG: a :class:`PngJob` with the ``layout`` of its
+    staged bytes (``HostCodec.png_adam7_layout``; ``layout.stage_bytes`` in the
+    upload region)."""
 
     __slots__ = ()
 
@@ -144,16 +174,17 @@ class StagePlan:
     """The plan of one batch over ``stage``, a uint8 numpy view whose first
     byte is 16-byte aligned and whose size is the capacity (the layout: the
     module's docstring).  ``huffman`` and ``huffman_wide`` are the two knobs,
-    ``max_dim`` the largest image side the device resize takes.  ``jpegs``,
-    ``pngs`` and ``raws`` list the batch's images in the order they were added;
-    ``rows`` counts them."""
+    ``max_dim`` the largest image side the device resize takes, ``png_adam7``
+    whether interlaced PNGs are staged (for K25i) or turned away.  ``jpegs``,
+    ``pngs``, ``adam7s`` and ``raws`` list the batch's images in the order they
+    were added; ``rows`` counts them."""
 
-    def __init__(self, stage, codec, huffman=False, huffman_wide=0, max_dim=16384):
+    def __init__(self, stage, codec, huffman=False, huffman_wide=0, max_dim=16384, png_adam7=False):
         self.stage, self.codec = stage, codec
-        self.huffman, self.huffman_wide, self.max_dim = huffman, huffman_wide, max_dim
+        self.huffman, self.huffman_wide, self.max_dim, self.png_adam7 = huffman, huffman_wide, max_dim, png_adam7
         self.rows = self.used = self.ws_need = 0
         self.top = stage.size
-        self.jpegs, self.raws, self.pngs = [], [], []
+        self.jpegs, self.raws, self.pngs, self.adam7s = [], [], [], []
 
     @property
     def workspace(self):
@@ -161,12 +192,13 @@ class StagePlan:
         return (self.top - self.ws_need + 15) // 16 * 16
 
     def mark(self):
-        return self.rows, self.used, self.top, self.ws_need, len(self.jpegs), len(self.raws), len(self.pngs)
+        return (self.rows, self.used, self.top, self.ws_need, len(self.jpegs), len(self.raws), len(self.pngs),
+                len(self.adam7s))
 
     def rollback(self, mark):
         """Forget everything added since ``mark``."""
         self.rows, self.used, self.top, self.ws_need = mark[:4]
-        del self.jpegs[mark[4]:], self.raws[mark[5]:], self.pngs[mark[6]:]
+        del self.jpegs[mark[4]:], self.raws[mark[5]:], self.pngs[mark[6]:], self.adam7s[mark[7]:]
 
     def add_raw(self, image, antialias=False):
         """Stage a uint8 HWC array if the device resize takes it and it fits."""
@@ -215,26 +247,39 @@ class StagePlan:
 
 
     def add_png(self, blob, info, antialias=False, request=0):
-        """Stage a non-interlaced PNG blob with parse ``info`` for K25: None,
-        with nothing inflated, when its staged bytes and its pixels do not fit
-        (or the device resize does not take its size).  A blob that does not
+        """Stage a PNG blob with parse ``info``: a non-interlaced one for K25
+        (a :class:`PngJob` in ``pngs``), an interlaced one, if the plan takes
+        them (``png_adam7``), for K25i (an :class:`Adam7Job` in ``adam7s``).
+        None, with nothing inflated, when its staged bytes and its pixels do
+        not fit (or the device resize does not take its size, or it is
+        interlaced and the plan takes no such file).  A blob that does not
         inflate raises the host decoder's error and leaves the plan as it was."""
         at = -(-self.used // 16) * 16
-        if info.interlace or not (1 <= info.h <= self.max_dim and 1 <= info.w <= self.max_dim) \
-                or at + info.stage_bytes > self.top - info.pixel_bytes - self.ws_need:
+        if (info.interlace and not self.png_adam7) or not (1 <= info.h <= self.max_dim and 1 <= info.w <= self.max_dim):
             return None
-        self.codec.png_inflate(blob, self.stage[at:at + info.stage_bytes])
-        self.used = at + info.stage_bytes
+        layout = self.codec.png_adam7_layout(info) if info.interlace else None
+        stage_bytes = layout.stage_bytes if layout else info.stage_bytes
+        if at + stage_bytes > self.top - info.pixel_bytes - self.ws_need:
+            return None
+        if layout:
+            self.codec.png_inflate_adam7(blob, self.stage[at:at + stage_bytes])
+            job = Adam7Job(at, self.top - info.pixel_bytes, info, layout, self.rows, blob, antialias, request)
+            self.adam7s.append(job)
+        else:
+            self.codec.png_inflate(blob, self.stage[at:at + stage_bytes])
+            job = PngJob(at, self.top - info.pixel_bytes, info, self.rows, blob, antialias, request)
+            self.pngs.append(job)
+        self.used = at + stage_bytes
         self.top -= info.pixel_bytes
-        job = PngJob(at, self.top, info, self.rows, blob, antialias, request)
-        self.pngs.append(job)
         self.rows += 1
         return job
 
 
-def launch_decode(hip, jobs, upload, device_only, workspace, workspace_bytes, alloc_status, stream, pngs=()):
-    """Issue K23, then K24, then K22 for the :class:`JpegJob` list ``jobs`` and
-    K25, once, for the :class:`PngJob` list ``pngs`` on ``stream``.  ``upload`` and ``device_only`` are the device addresses that
+def launch_decode(hip, jobs, upload, device_only, workspace, workspace_bytes, alloc_status, stream, pngs=(),
+                  adam7s=()):
+    """Issue K23, then K24, then K22 for the :class:`JpegJob` list ``jobs``,
+    K25, once, for the :class:`PngJob` list ``pngs`` and then K25i, once, for
+    the :class:`Adam7Job` list ``adam7s`` on ``stream``.  ``upload`` and ``device_only`` are the device addresses that
     the offsets of the two regions count from (the same address for a
     :class:`StagePlan`); ``workspace`` is the device address of K24's
     ``workspace_bytes``; ``alloc_status(n)`` gives ``n`` int32 status words on
@@ -260,4 +305,7 @@ def launch_decode(hip, jobs, upload, device_only, workspace, workspace_bytes, al
     if pngs:
         hip.png_unfilter([upload + j.stream for j in pngs], [j.info for j in pngs],
                          [device_only + j.pix for j in pngs], stream=stream)
+    if adam7s:
+        hip.png_unfilter_adam7([upload + j.stream for j in adam7s], [j.info for j in adam7s],
+                               [device_only + j.pix for j in adam7s], stream=stream)
     return ran

@@ -101,6 +101,11 @@ KNOBS = [
          "PNG: 1 = the host inflates a non-interlaced file into the staging area and K25 png_unfilter reverses the "
          "filters and converts the samples on the device; 0 = the host decodes it and the pixels go up",
          "tests/test_png_gpu.py::test_the_png_knob_changes_the_route_and_not_one_bit_of_the_rows"),
+    Knob("TCAMD_DEVICE_PNG_ADAM7", "python", 0, "utils/jpeg_stage.py",
+         "PNG: 1 = with TCAMD_DEVICE_PNG at 1, the host inflates an interlaced (Adam7) file into the staging area "
+         "too and K25i png_unfilter_adam7 unfilters its seven sub-images at once on the device; 0 = the host decodes "
+         "every interlaced file and the pixels go up",
+         "tests/test_png_adam7_gpu.py::test_the_adam7_knob_changes_the_route_and_not_one_bit_of_the_rows"),
     Knob("TCAMD_DEVICE_QA_SPANS", "python", 1, "server/gpu_models.py",
          "GPU qa_spans and qa_doc_spans: K27 qa_spans (and K29 qa_merge) pick the answer spans on the device; 0 = the "
          "host twins of the same rules",

@@ -27,6 +27,10 @@ build/%.o: csrc/%.hip $(wildcard csrc/kernels/*.h) $(wildcard csrc/hipshm/*.h) c
 	@mkdir -p $(dir $@)
 	$(HIPCC) $(HIPFLAGS) -Icsrc -c -o $@ $<
 
+# K10c promises the same bits for a row in every batch: keep the packed fp32
+# VALU forms (v_pk_add_f32 and kin) out of its object
+build/kernels/densenet_head.o: HIPFLAGS += -Xclang -target-feature -Xclang -packed-fp32-ops
+
 $(HIPLIB): $(HIP_OBJS)
 	@mkdir -p $(dir $@)
 	$(HIPCC) -shared -fPIC --offload-arch=$(ARCH) -o $@ $^ -L$(ROCM)/lib -lamdhip64

@@ -2562,13 +2562,12 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))
 // per lane in flight) and sum through LDS.  The first version (one block per
 // image, each thread a serial pixel loop) paid an L2 round trip per pixel:
 // 14 us at bs1, 1.4% of that forward.
-__global__ void __launch_bounds__(256) x3_head_pool_kernel(const float* __restrict__ x, const float* __restrict__ s,
-                                                           const float* __restrict__ b, float* __restrict__ out, int HW,
-                                                           int C) {
+// The block's sum for its lane's 4 channels (c4, clamped where not live), on
+// the lanes of wave 0, before the 1 / HW.
+__device__ __forceinline__ f32x4 x3_head_pool_sum(const float* __restrict__ x, const float* __restrict__ s,
+                                                  const float* __restrict__ b, int HW, int C, int c4, bool live) {
   __shared__ f32x4 part[4][64];
   const int img = blockIdx.x, lane = threadIdx.x & 63, ph = threadIdx.x >> 6;
-  const int c4 = blockIdx.y * 64 + lane;
-  const bool live = c4 < C / 4;
   const int cc = live ? c4 : 0;
   const f32x4 sc = ldf4(s + cc * 4), bi = ldf4(b + cc * 4);
   f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -2590,10 +2589,40 @@ __global__ void __launch_bounds__(256) x3_head_pool_kernel(const float* __restri
   }
   part[ph][lane] = acc;
   __syncthreads();
-  if (ph == 0 && live) {
-    const f32x4 t = part[0][lane] + part[1][lane] + part[2][lane] + part[3][lane];
-    *reinterpret_cast<f32x4*>(out + (size_t)img * C + c4 * 4) = t * (1.0f / (float)HW);
-  }
+  return part[0][lane] + part[1][lane] + part[2][lane] + part[3][lane];
+}
+
+__global__ void __launch_bounds__(256) x3_head_pool_kernel(const float* __restrict__ x, const float* __restrict__ s,
+                                                           const float* __restrict__ b, float* __restrict__ out, int HW,
+                                                           int C) {
+  const int img = blockIdx.x, c4 = blockIdx.y * 64 + (threadIdx.x & 63);
+  const bool live = c4 < C / 4;
+  const f32x4 t = x3_head_pool_sum(x, s, b, HW, C, c4, live);
+  if (threadIdx.x < 64 && live) *reinterpret_cast<f32x4*>(out + (size_t)img * C + c4 * 4) = t * (1.0f / (float)HW);
+}
+
+// The head for K10c (csrc/kernels/densenet_head.hip): the same pooled value,
+// written as the classifier's bf16x3 operand, planes hi / lo [imgs][C] (and as
+// fp32 into out where that is given).  Without the packed fp32 VALU forms: the
+// classifier's bits must be a function of the row alone.
+#if defined(__HIP_DEVICE_COMPILE__)
+#define X3_NO_PK_F32 __attribute__((target("no-packed-fp32-ops")))
+#else
+#define X3_NO_PK_F32  // the host pass does not know the feature
+#endif
+__global__ void __launch_bounds__(256) X3_NO_PK_F32
+x3_head_pool_split_kernel(const float* __restrict__ x, const float* __restrict__ s, const float* __restrict__ b,
+                          float* __restrict__ out, uint16_t* __restrict__ hi, uint16_t* __restrict__ lo, int HW, int C) {
+  const int img = blockIdx.x, c4 = blockIdx.y * 64 + (threadIdx.x & 63);
+  const bool live = c4 < C / 4;
+  const f32x4 t = x3_head_pool_sum(x, s, b, HW, C, c4, live) * (1.0f / (float)HW);
+  if (threadIdx.x >= 64 || !live) return;
+  const size_t at = (size_t)img * C + c4 * 4;
+  if (out) *reinterpret_cast<f32x4*>(out + at) = t;
+  v2u h, l;
+  split4(t, h, l);
+  *reinterpret_cast<v2u*>(hi + at) = h;
+  *reinterpret_cast<v2u*>(lo + at) = l;
 }
 
 __global__ void x3_split_kernel(const float* __restrict__ w, uint16_t* __restrict__ hi, uint16_t* __restrict__ lo,
@@ -3138,6 +3167,19 @@ int tcamd_x3_head_pool(const float* x, const float* s, const float* b, float* ou
   if (C % 4 || !aligned16(x) || !aligned16(s) || !aligned16(b) || !aligned16(out)) return hipErrorInvalidValue;
   hipLaunchKernelGGL(x3_head_pool_kernel, dim3(imgs, (C / 4 + 63) / 64), dim3(256), 0, (hipStream_t)stream, x, s, b,
                      out, HW, C);
+  return hipGetLastError();
+}
+
+// K10x head for K10c: hi / lo bf16 [imgs][C] planes of the pooled rows, and
+// the fp32 rows themselves into out where out is not null.
+int tcamd_x3_head_pool_split(const float* x, const float* s, const float* b, float* out, void* hi, void* lo, int imgs,
+                             int HW, int C, void* stream) {
+  if (imgs <= 0) return hipSuccess;
+  if (C % 4 || HW <= 0 || !x || !s || !b || !hi || !lo) return hipErrorInvalidValue;
+  if (!aligned16(x) || !aligned16(s) || !aligned16(b) || !aligned16(out) || !aligned16(hi) || !aligned16(lo))
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL(x3_head_pool_split_kernel, dim3(imgs, (C / 4 + 63) / 64), dim3(256), 0, (hipStream_t)stream, x, s,
+                     b, out, (uint16_t*)hi, (uint16_t*)lo, HW, C);
   return hipGetLastError();
 }
 

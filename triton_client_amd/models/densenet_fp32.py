@@ -36,6 +36,11 @@ Network walk (same as :class:`densenet_fused.FusedDenseNet`, fp32 activations):
                         -> next block buffer ch[0 : C/2] (fp32)
    -> K10x head: relu(BN5(x)) global average -> [b,1024] fp32
    -> classifier: fp32 GEMM (hipBLASLt) -> fp32 logits
+      or (classifier="fused"): the head writes the pooled rows as bf16 hi / lo
+      planes and K10c (csrc/kernels/densenet_head.hip) computes the logits as
+      a bf16x3 product, a row's bits the same in every batch; the dense
+      layers then run K11x (56x56, 28x28) or the K8x + K9x pair, unsplit, so
+      that an image's pooled row does not depend on the batch either
 
 All launches go to the caller's current HIP stream with no host sync, so a
 forward captures into one HIP graph per batch bucket.
@@ -75,7 +80,10 @@ class FusedDenseNetFP32:
     H0 = 224
     precision = "fp32"
 
-    def __init__(self, model, max_batch, device):
+    def __init__(self, model, max_batch, device, classifier="lib"):
+        if classifier not in ("lib", "fused"):
+            raise ValueError("classifier must be 'lib' or 'fused', not %r" % (classifier,))
+        self.classifier = classifier
         assert all(layer.folded for blk in model.blocks for layer in blk), "call fold_for_inference first"
         dev = torch.device(device)
         self.device = dev
@@ -122,6 +130,8 @@ class FusedDenseNetFP32:
             self.s5, self.t5 = s5.to(dev), t5.to(dev)
             self.wc = model.classifier.weight.float().to(dev).contiguous()
             self.bc = model.classifier.bias.float().to(dev).contiguous()
+            if classifier == "fused":
+                self.wc_hi, self.wc_lo = hip.x3_classifier_weights(self.wc)
             self.num_features = c
         # K11x runs a layer when every block gets at least this many 64-pixel
         # tiles (its per-block prologue recomputes a (2W+2)-row halo of z, yet it
@@ -177,6 +187,10 @@ class FusedDenseNetFP32:
         self.z_hi = torch.empty(n * h1 * h1, BN_SIZE * GROWTH, device=dev, dtype=torch.bfloat16)
         self.z_lo = torch.empty_like(self.z_hi)
         self.pooled = torch.empty(n, self.num_features, device=dev, dtype=torch.float32)
+        if self.classifier == "fused":
+            # K10c's operand: the pooled rows as bf16 hi / lo planes
+            self.pooled_hi = torch.empty(n, self.num_features, device=dev, dtype=torch.bfloat16)
+            self.pooled_lo = torch.empty_like(self.pooled_hi)
         self.ptrs = torch.zeros(n, device=dev, dtype=torch.int64)
         self._img_off = torch.arange(n, device=dev, dtype=torch.int64) * (IMG_ELEMS * 4)
         # split-K partials: the largest request over every 1x1 conv at EVERY
@@ -240,7 +254,13 @@ class FusedDenseNetFP32:
         hw0, c0 = self.block_dims[0]
         hip.x3_stem(self.ptrs.data_ptr(), self.w0_hi.data_ptr(), self.w0_lo.data_ptr(), self.b0.data_ptr(),
                     self.feat[0].data_ptr(), b, c0, stream=st)
-        ws, wsb = self.ws.data_ptr(), self.ws.numel()
+        # the fused head promises a row the same bits in every batch: the body
+        # then keeps to the routes whose result for an image does not depend on
+        # the batch (K11x at 56x56 / 28x28, the K8x + K9x pair without split-K
+        # below); the K13x layers sum with float atomics, and K14x and a
+        # split 1x1 order their sums by the batch's tiling
+        inv = self.classifier == "fused"
+        ws, wsb = (None, 0) if inv else (self.ws.data_ptr(), self.ws.numel())
         zh, zl = self.z_hi.data_ptr(), self.z_lo.data_ptr()
         zacc = None  # K13x: index of the zeroed accumulator, None before the first small layer
         for bi, layers in enumerate(self.blocks):
@@ -249,8 +269,8 @@ class FusedDenseNetFP32:
             M = b * hw * hw
             fused = self._fuse(M, hw)
             fmax = self._fuse_max_k(M)
-            small = 0 < M <= self.small_m and M <= self.zacc.shape[1]
-            if self._small_fused(b, hw):
+            small = not inv and 0 < M <= self.small_m and M <= self.zacc.shape[1]
+            if not inv and self._small_fused(b, hw):
                 # K14x: the 14x14 / 7x7 blocks, one launch per layer, z on chip;
                 tiles = self._small_tiles(b, hw)
                 # ... two layers per launch on one read of the block input
@@ -271,7 +291,7 @@ class FusedDenseNetFP32:
                     j += 1
                 self._transition(bi, fp, ctot, b, hw, ws, wsb, st)
                 continue
-            ch = self.chain[bi]
+            ch = None if inv else self.chain[bi]
             if ch is not None and 0 < M <= ch[2]:
                 # the whole block runs as one chain (at bs1-2 a 28x28 K11x layer
                 # takes 13-15 us, a chain layer ~5.5; starting the chain after
@@ -298,12 +318,19 @@ class FusedDenseNetFP32:
                                         L["w2h"].data_ptr(), L["w2l"].data_ptr(), fp + 4 * L["cin"], ctot, stream=st)
                     zacc ^= 1
                     continue
-                hip.x3_dense_layer(fp, ctot, b, hw, hw, L["cin"], L["s1"].data_ptr(), L["t1"].data_ptr(),
-                                   L["w1h"].data_ptr(), L["w1l"].data_ptr(), L["b1"].data_ptr(), zh, zl,
-                                   L["w2h"].data_ptr(), L["w2l"].data_ptr(), fp + 4 * L["cin"], ctot, ws=ws,
-                                   ws_bytes=wsb, stream=st)
+                # ... and at most 64 images a launch: from 16384 pixels the 1x1
+                # is the warp-specialised kernel, which sums in another order
+                step = 64 if inv else b
+                for r in range(0, b, step):
+                    at = fp + 4 * r * hw * hw * ctot
+                    hip.x3_dense_layer(at, ctot, min(step, b - r), hw, hw, L["cin"], L["s1"].data_ptr(),
+                                       L["t1"].data_ptr(), L["w1h"].data_ptr(), L["w1l"].data_ptr(),
+                                       L["b1"].data_ptr(), zh, zl, L["w2h"].data_ptr(), L["w2l"].data_ptr(),
+                                       at + 4 * L["cin"], ctot, ws=ws, ws_bytes=wsb, stream=st)
             self._transition(bi, fp, ctot, b, hw, ws, wsb, st)
         hw4, c4 = self.block_dims[-1]
+        if self.classifier == "fused":
+            return self._fused_head(b, hw4, c4, out, st)
         hip.x3_head_pool(self.feat[-1].data_ptr(), self.s5.data_ptr(), self.t5.data_ptr(), self.pooled.data_ptr(),
                          b, hw4 * hw4, c4, stream=st)
         if out is None:
@@ -312,6 +339,23 @@ class FusedDenseNetFP32:
         return out[:b]
 
     __call__ = forward
+
+    def _fused_head(self, b, hw, c, out, st):
+        """The head on our kernels: K10x writes the pooled rows split, K10c the
+        logits (at most 128 rows a launch), into ``out[:b]`` or a fresh tensor."""
+        hip.x3_head_pool_split(self.feat[-1].data_ptr(), self.s5.data_ptr(), self.t5.data_ptr(),
+                               self.pooled_hi.data_ptr(), self.pooled_lo.data_ptr(), b, hw * hw, c, stream=st)
+        n = self.bc.numel()
+        if out is None:
+            out = torch.empty(b, n, device=self.device, dtype=torch.float32)
+        if out.dtype != torch.float32 or out.stride(1) != 1 or out.shape[1] != n:
+            raise ValueError("out must be fp32 [>= b, %d] with unit column stride" % n)
+        for r in range(0, b, 128):
+            rows = min(128, b - r)
+            hip.x3_classifier(self.pooled_hi[r:].data_ptr(), self.pooled_lo[r:].data_ptr(), self.wc_hi.data_ptr(),
+                              self.wc_lo.data_ptr(), self.bc.data_ptr(), out[r:].data_ptr(), rows, n, c,
+                              ldc=out.stride(0), stream=st)
+        return out[:b]
 
     def _fused_layer(self, fused, L, fp, ctot, b, hw, st):
         """K11x: the whole dense layer in one kernel.  v3 (the next chunk's 1x1
@@ -400,9 +444,10 @@ def _cu_count(dev):
     return _CU[key]
 
 
-def build(max_batch, device="cuda", seed=0):
+def build(max_batch, device="cuda", seed=0, classifier="lib"):
     """Random-init, BN-calibrated, folded DenseNet-121 as an fp32-parity engine.
-    Returns (engine, the fp32 torch module it must match)."""
+    Returns (engine, the fp32 torch module it must match).  ``classifier``:
+    "lib" (the library's fp32 GEMM) or "fused" (K10c, batch-invariant bits)."""
     from . import densenet
 
     model = densenet.DenseNet121()
@@ -410,4 +455,4 @@ def build(max_batch, device="cuda", seed=0):
     densenet.calibrate_bn(model, device="cpu")
     densenet.fold_for_inference(model)
     model.eval()
-    return FusedDenseNetFP32(model, max_batch, device), model
+    return FusedDenseNetFP32(model, max_batch, device, classifier=classifier), model

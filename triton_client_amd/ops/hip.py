@@ -429,6 +429,16 @@ _SIGS = {
          ctypes.c_void_p],
         ctypes.c_int,
     ),
+    "tcamd_x3_head_pool_split": (
+        [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+         ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p],
+        ctypes.c_int,
+    ),
+    "tcamd_x3_classifier": (
+        [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+         ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p],
+        ctypes.c_int,
+    ),
     "tcamd_x3_split": (
         [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p],
         ctypes.c_int,
@@ -1549,6 +1559,40 @@ def x3_stem(srcs, w_hi, w_lo, bias, y, imgs, ldy, stream=None):
 def x3_head_pool(x, scale, bias, out, imgs, HW, C, stream=None):
     """K10x head: out[i, c] = mean_p relu(x[i, p, c]*scale[c] + bias[c]), fp32."""
     _check(_load().tcamd_x3_head_pool(x, scale, bias, out, imgs, HW, C, _vp(stream)), "x3_head_pool")
+
+
+def x3_head_pool_split(x, scale, bias, hi, lo, imgs, HW, C, out=None, stream=None):
+    """K10x head for K10c: the pooled rows of :func:`x3_head_pool` as the
+    classifier's bf16x3 operand, bf16 planes ``hi`` / ``lo`` [imgs][C] (hi =
+    RNE of the fp32 value, lo = RNE of the rest); ``out`` (fp32 [imgs][C] or
+    None) also gets the fp32 rows, bitwise those of :func:`x3_head_pool`."""
+    _check(_load().tcamd_x3_head_pool_split(x, scale, bias, _vp(out), hi, lo, int(imgs), int(HW), int(C),
+                                            _vp(stream)), "x3_head_pool_split")
+
+
+def x3_classifier_weights(w):
+    """K10c weight layout: fp32 [N][K] -> (hi, lo) bf16 planes [16 ceil(N/16)][K]
+    on ``w``'s device, w ~= hi + lo (RNE both), the rows past N zero."""
+    import torch
+
+    w = w.float()
+    n, k = w.shape
+    hi = torch.zeros((n + 15) // 16 * 16, k, dtype=torch.bfloat16, device=w.device)
+    lo = torch.zeros_like(hi)
+    hi[:n] = w.to(torch.bfloat16)
+    lo[:n] = (w - hi[:n].float()).to(torch.bfloat16)
+    return hi, lo
+
+
+def x3_classifier(a_hi, a_lo, w_hi, w_lo, bias, out, b, N, K, ldc=None, stream=None):
+    """K10c: out[b][ldc] fp32 (columns 0..N-1 written, nothing else) = a . W^T +
+    bias as a bf16x3 product; ``a_hi`` / ``a_lo`` bf16 [b][K]
+    (:func:`x3_head_pool_split`), ``w_hi`` / ``w_lo`` from
+    :func:`x3_classifier_weights`, ``bias`` fp32 [N].  1 <= b <= 128, K % 64
+    == 0, ``ldc`` >= N (default N), 16-byte aligned operands.  A row's logits
+    are the same bits at every ``b`` and every position in the batch."""
+    _check(_load().tcamd_x3_classifier(a_hi, a_lo, w_hi, w_lo, bias, out, int(b), int(N), int(K),
+                                       int(N if ldc is None else ldc), _vp(stream)), "x3_classifier")
 
 
 def x3_split(w, hi, lo, n, stream=None):

@@ -87,6 +87,14 @@ class DensenetOnnx(DeviceModel):
         self.use_graphs = use_graphs
 
     # -- load ----------------------------------------------------------------------
+    @staticmethod
+    def head_classifier():
+        """The fp32 engine's classifier: ``TCAMD_DENSENET_HEAD=1`` (read at load; 0
+        by default) = "fused", the batch-invariant K10c and body routes (an image's
+        logits are the same bits in every batch the server forms, at a lower
+        speed); anything else = "lib"."""
+        return "fused" if os.environ.get("TCAMD_DENSENET_HEAD", "0") == "1" else "lib"
+
     def load(self):
         from triton_client_amd.models import densenet
 
@@ -95,7 +103,7 @@ class DensenetOnnx(DeviceModel):
         if self.engine == "fp32":
             from triton_client_amd.models import densenet_fp32
 
-            self.model, _ = densenet_fp32.build(max(self.buckets), device=dev)
+            self.model, _ = densenet_fp32.build(max(self.buckets), device=dev, classifier=self.head_classifier())
         elif self.engine == "fused":
             from triton_client_amd.models import densenet_fused
 

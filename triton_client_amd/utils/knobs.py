@@ -119,6 +119,11 @@ KNOBS = [
          "over packed rows) per row bucket and fill 128 / 256, and serve a batch whose valid tokens fit one over "
          "those tokens alone (the server's --bert-packed sets it); 0 = every batch runs the padded graphs",
          "tests/test_bert_pack_gpu.py::test_served_short_rows_take_a_packed_graph"),
+    Knob("TCAMD_DENSENET_HEAD", "python", 0, "server/gpu_models.py",
+         "densenet_onnx (fp32 engine): 1 = the head runs on K10c x3_classifier and the dense layers keep to "
+         "batch-invariant routes: an image's logits are the same bits in every batch, at a lower speed; 0 = the "
+         "library's fp32 GEMM and the fastest routes",
+         "tests/test_densenet_head_knob.py::test_the_knob_selects_the_classifier"),
     Knob("TCAMD_BERT_VOCAB", "python", "", "utils/wordpiece.py",
          "bert_tokenizer: the vocab.txt to load (the server's --bert-vocab sets it); unset = the demonstration "
          "vocabulary triton_client_amd/data/bert_demo_vocab.txt",

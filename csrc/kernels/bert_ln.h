@@ -1,5 +1,6 @@
 // Row LayerNorm pieces shared by the BERT kernels (csrc/kernels/bert.hip K11 /
-// embedding LayerNorm, csrc/kernels/bert_pack.hip packed embedding LayerNorm): one wave
+// embedding LayerNorm, csrc/kernels/bert_pack.hip packed embedding LayerNorm,
+// csrc/kernels/bert_pool.hip K32 pooled LayerNorm): one wave
 // owns one row of H = 64 * E elements, lane l the 8-element chunks l, l + 64, ...
 // (16 B of a bf16 row, 32 B of an fp32 one)
 #pragma once
@@ -24,24 +25,33 @@ __device__ __forceinline__ float wave_sum(float v) {
   return v;
 }
 
-// LayerNorm of one row held as v[E] per lane (lane l owns the 16-B chunks
-// l, l + 64, ...) -> bf16 out row: exact two-pass mean / variance over the
-// register copy, wave butterflies through DPP-backed shuffles
+// Mean and 1 / sqrt(variance + eps) of one row held as v[E] per lane: exact
+// two-pass statistics over the register copy, wave butterflies through
+// DPP-backed shuffles (every lane gets both)
 template <int E>
-__device__ __forceinline__ void ln_store_row(const float (&v)[E], const uint16_t* __restrict__ gamma,
-                                             const uint16_t* __restrict__ beta, uint16_t* orow, int lane, float eps) {
-  constexpr int H = 64 * E, C = E / 8;
+__device__ __forceinline__ void ln_stats(const float (&v)[E], float eps, float& mean, float& rstd) {
+  constexpr int H = 64 * E;
   float s = 0.f;
 #pragma unroll
   for (int e = 0; e < E; ++e) s += v[e];
-  const float mean = wave_sum(s) * (1.0f / H);
+  mean = wave_sum(s) * (1.0f / H);
   float ss = 0.f;
 #pragma unroll
   for (int e = 0; e < E; ++e) {
     const float d = v[e] - mean;
     ss += d * d;
   }
-  const float rstd = rsqrtf(wave_sum(ss) * (1.0f / H) + eps);
+  rstd = rsqrtf(wave_sum(ss) * (1.0f / H) + eps);
+}
+
+// LayerNorm of one row held as v[E] per lane (lane l owns the 16-B chunks
+// l, l + 64, ...) -> bf16 out row
+template <int E>
+__device__ __forceinline__ void ln_store_row(const float (&v)[E], const uint16_t* __restrict__ gamma,
+                                             const uint16_t* __restrict__ beta, uint16_t* orow, int lane, float eps) {
+  constexpr int C = E / 8;
+  float mean, rstd;
+  ln_stats<E>(v, eps, mean, rstd);
 #pragma unroll
   for (int c = 0; c < C; ++c) {
     const int off = (c * 64 + lane) * 8;
@@ -68,17 +78,8 @@ __device__ __forceinline__ void ln_store_row(const float (&v)[E], const float* _
                                              const float* __restrict__ beta, float* orow, uint16_t* orow3, int lane,
                                              float eps) {
   constexpr int H = 64 * E, C = E / 8;
-  float s = 0.f;
-#pragma unroll
-  for (int e = 0; e < E; ++e) s += v[e];
-  const float mean = wave_sum(s) * (1.0f / H);
-  float ss = 0.f;
-#pragma unroll
-  for (int e = 0; e < E; ++e) {
-    const float d = v[e] - mean;
-    ss += d * d;
-  }
-  const float rstd = rsqrtf(wave_sum(ss) * (1.0f / H) + eps);
+  float mean, rstd;
+  ln_stats<E>(v, eps, mean, rstd);
 #pragma unroll
   for (int c = 0; c < C; ++c) {
     const int off = (c * 64 + lane) * 8;

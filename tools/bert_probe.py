@@ -5,6 +5,7 @@
   python tools/bert_probe.py --batch 1 8 64 --gemm lib,auto,ours --graphs   # projection routing A/B, HIP graphs
   python tools/bert_probe.py --packed --batch 1 8 32 64 128 --fill 64 128 192 256   # padded against padding-free
   python tools/bert_probe.py --packed --fp32 --batch 1 8 32 64 --fill 64 128 192 256  # ... on the fp32-parity model
+  python tools/bert_probe.py --embed --batch 1 8 64 128   # embed against forward, K32 against the torch tail
 
 ``--packed``: the graph forward as served, the padded arm (the masked graph of
 ``forward``) against the packed arm (``forward_packed`` at the t_cap the served
@@ -16,6 +17,14 @@ against K12v, and the plan, packed-embedding and unpack launches.  With
 ``--fp32`` both arms run the fp32-parity model (the padded arm is its served
 padded graph) and the kernels are K12x (masked) against K12xv and the fp32
 packed embedding.
+
+``--embed``: the served graphs of ``forward`` and ``embed`` (masked, rows of
+random lengths), alternating inside one run; then K32 ``pool_layernorm`` alone
+(K11's bf16 form, the same mask) against what it replaces as separate launches:
+K11 ``add_layernorm`` writing the last hidden state, then the torch tail over
+it (masked mean and F.normalize, ``bert._pool_torch``).  Every launch is timed
+by its own pair of events; the figures are medians over ``--iters`` x
+``--rounds`` launches.
 """
 
 import argparse
@@ -147,6 +156,81 @@ def packed_probe(a, model, dev):
                               "plan_includes": "4 torch.empty and the launch", **us}), flush=True)
 
 
+def _median_us(launch, n):
+    """Median over ``n`` warm launches, each between its own pair of events."""
+    for _ in range(3):
+        launch()
+    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(n)]
+    for e0, e1 in ev:
+        e0.record()
+        launch()
+        e1.record()
+    torch.cuda.synchronize()
+    return round(sorted(e0.elapsed_time(e1) for e0, e1 in ev)[n // 2] * 1e3, 2)
+
+
+def embed_probe(a, model, dev):
+    import json
+
+    from triton_client_amd.ops import hip
+
+    S, H = 384, bert.HIDDEN
+    n = max(20, a.iters * a.rounds)
+    for b in a.batch:
+        lens = _lengths(b, 192, 77 * b)
+        mask = (torch.arange(S)[None, :] < lens[:, None]).to(torch.int32).to(dev)
+        ids = torch.randint(0, bert.VOCAB, (b, S), device=dev) * mask
+        tt = torch.zeros(b, S, device=dev, dtype=torch.int64)
+        arms = {"forward": lambda: model(ids, mask, tt), "embed": lambda: model.embed(ids, mask, tt)}
+        graphs = {}
+        with torch.no_grad():
+            for name, run in arms.items():
+                s = torch.cuda.Stream()
+                s.wait_stream(torch.cuda.current_stream())
+                with torch.cuda.stream(s):
+                    for _ in range(2):
+                        run()
+                    g = torch.cuda.CUDAGraph()
+                    with torch.cuda.graph(g, stream=s):
+                        run()
+                torch.cuda.current_stream().wait_stream(s)
+                graphs[name] = g
+            torch.cuda.synchronize()
+            ts = {k: [] for k in arms}
+            for _ in range(a.rounds):
+                for name in arms:
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    for _ in range(a.iters):
+                        graphs[name].replay()
+                    torch.cuda.synchronize()
+                    ts[name].append(round((time.perf_counter() - t0) / a.iters * 1e3, 3))
+        print(json.dumps({"probe": "graph", "rows": b, "tokens": int(lens.sum()), "layers": a.layers,
+                          "forward_ms": ts["forward"], "embed_ms": ts["embed"]}), flush=True)
+        # the kernels alone
+        x = torch.randn(b, S, H, device=dev).bfloat16()
+        y = (torch.randn(b, S, H, device=dev) * 0.5).bfloat16()
+        ln = model.layers[-1].ln2
+        hid = torch.empty_like(x)
+        ws = torch.empty(hip.pool_layernorm_workspace(b, S) // 4, device=dev)
+        out = torch.empty(b, H, device=dev)
+        st = torch.cuda.current_stream().cuda_stream
+        launches = {
+            "k32": lambda: hip.pool_layernorm(x.data_ptr(), y.data_ptr(), ln.weight.data_ptr(), ln.bias.data_ptr(),
+                                              mask.data_ptr(), None, ws.data_ptr(), out.data_ptr(), b, S, H, ln.eps,
+                                              stream=st),
+            "k11": lambda: hip.add_layernorm(x.data_ptr(), y.data_ptr(), ln.weight.data_ptr(), ln.bias.data_ptr(),
+                                             hid.data_ptr(), b * S, H, ln.eps, stream=st),
+            "torch_tail": lambda: bert._pool_torch(hid, mask, None),
+        }
+        with torch.no_grad():
+            us = {name: _median_us(launch, n) for name, launch in launches.items()}
+            diff = (out - bert._pool_torch(hid, mask, None)).abs().max().item()
+        print(json.dumps({"probe": "kernels_us", "rows": b, "tokens": int(lens.sum()), "launches": n, **us,
+                          "k11_plus_tail": round(us["k11"] + us["torch_tail"], 2),
+                          "k32_vs_tail_max_abs": float("%.3g" % diff)}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, nargs="+", default=[64])
@@ -166,9 +250,13 @@ def main():
                     help="padded graph against padding-free graph at each --batch (rows) and --fill, then the kernels")
     ap.add_argument("--fill", type=int, nargs="+", default=[64, 128, 192, 256],
                     help="--packed: mean valid tokens per row")
+    ap.add_argument("--embed", action="store_true",
+                    help="the embed graph against the forward graph at each --batch, then K32 against K11 + the torch tail")
     ap.add_argument("--layers", type=int, default=bert.LAYERS)
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
+    if a.embed:
+        return embed_probe(a, bert.build(device=dev, layers=a.layers), dev)
     if a.packed:
         if a.fp32:
             return packed_probe(a, bert.prepare_x3(bert.build(device=dev, dtype=torch.float32, layers=a.layers)), dev)

@@ -33,6 +33,11 @@ b x 384.  The fp32-parity model (fp32 weights after ``prepare_x3``) has the
 same form: the fp32 packed embedding LayerNorm, which also writes the first
 QKV projection's bf16x3 operand, the bf16x3 projections and K11p over t_cap
 tokens, and K12xv, K12x over rows of different lengths.
+
+Sentence embeddings (``BertLargeQA.embed``): the same encoder, with the last
+layer's residual add + LayerNorm fused into the pooling (K32,
+csrc/kernels/bert_pool.hip): masked mean or first token, L2-normalised, fp32
+[b, 1024]; the last hidden state is never written.
 """
 
 import math
@@ -319,21 +324,33 @@ def prepare_x3(model):
     return model
 
 
+def _proj_operands(x, a, lin, name):
+    """What the add + LayerNorm behind the projection lin(a) reads, by the
+    route that projection takes at this token count: ("parts", slabs, bias)
+    -- a split-K route's fp32 partial slabs [splits, tokens, N] and the fp32
+    bias, K11p's operand form -- or ("y", lin(a)), K11's."""
+    y = _proj(a, lin, "bias", name=name, allow_split=True)
+    if isinstance(y, _Parts):
+        p = y.slabs
+        assert x.is_contiguous() and x.numel() == p.shape[1] * p.shape[2]
+        bias = lin.bias.detach() if x.dtype == torch.float32 else _bias_f32(lin, x.device)
+        return "parts", p, bias
+    return "y", y, None
+
+
 def _proj_add_ln(x, a, lin, ln, name):
     """LayerNorm(x + lin(a)): the attention-out / FFN-down projection and the
     residual add + LayerNorm behind it.  A split-K route hands its fp32
     partial slabs to K11p, which sums them with the bias and the residual on
     its way into the LayerNorm (no reduce launch, no bf16 y)."""
-    y = _proj(a, lin, "bias", name=name, allow_split=True)
-    if isinstance(y, _Parts):
+    form, y, bias = _proj_operands(x, a, lin, name)
+    if form == "parts":
         from triton_client_amd.ops import hip
 
-        p = y.slabs
+        p = y
         out = torch.empty_like(x)
         rows, H = p.shape[1], p.shape[2]
-        assert x.is_contiguous() and x.numel() == rows * H
         f32 = x.dtype == torch.float32
-        bias = lin.bias.detach() if f32 else _bias_f32(lin, x.device)
         xc = _x3_buffer(x, lin, rows, H)
         hip.add_layernorm_parts(x.data_ptr(), p.data_ptr(), p.shape[0], rows * H, bias.data_ptr(),
                                 ln.weight.data_ptr(), ln.bias.data_ptr(), out.data_ptr(), rows, H, ln.eps, f32=f32,
@@ -343,6 +360,51 @@ def _proj_add_ln(x, a, lin, ln, name):
             out._x3 = xc
         return out
     return _add_ln(x, y, ln, x3=getattr(lin, "w3", None) is not None)
+
+
+POOL_CLS = 1  # embed() per-row flag bits (K32's): the first token instead of the masked mean
+POOL_RAW = 2  # no L2 normalisation
+
+
+def _pool_torch(h, attention_mask, flags):
+    """K32's rules in torch ops over the last hidden state h [b, s, H]: the mean
+    over the tokens with attention_mask >= 1 (None: all), zeros for a row
+    that has none, token 0 where flags has POOL_CLS, then F.normalize (a zero
+    row stays zero) unless POOL_RAW.  fp32 [b, H]."""
+    h = h.float()
+    b, s, _ = h.shape
+    valid = h.new_ones(b, s) if attention_mask is None else (attention_mask >= 1).to(h.dtype)
+    e = (h * valid[..., None]).sum(1) / valid.sum(1, keepdim=True).clamp(min=1)
+    if flags is None:
+        return F.normalize(e, dim=1)
+    e = torch.where((flags & POOL_CLS).bool()[:, None], h[:, 0], e)
+    return torch.where((flags & POOL_RAW).bool()[:, None], e, F.normalize(e, dim=1))
+
+
+def _proj_pool_ln(x, a, lin, ln, name, attention_mask, mask_i32, flags):
+    """The pooled LayerNorm(x + lin(a)) of embed(): _proj_add_ln with K32
+    (csrc/kernels/bert_pool.hip) in the place of K11 / K11p, on the operands
+    that the projection's route hands over, so the last hidden state is never
+    written.  Where _add_ln would run torch ops, so does this (_pool_torch)."""
+    form, y, bias = _proj_operands(x, a, lin, name)
+    b, s, H = x.shape
+    if form == "y" and not (FUSED and x.is_cuda and x.dtype in (torch.bfloat16, torch.float32)
+                            and y.dtype == x.dtype and x.is_contiguous() and y.is_contiguous()):
+        return _pool_torch(ln(x + y), attention_mask, flags)
+    from triton_client_amd.ops import hip
+
+    f32 = x.dtype == torch.float32
+    ws = torch.empty(hip.pool_layernorm_workspace(b, s) // 4, device=x.device, dtype=torch.float32)
+    out = torch.empty(b, H, device=x.device, dtype=torch.float32)
+    tail = (ln.weight.data_ptr(), ln.bias.data_ptr(), None if mask_i32 is None else mask_i32.data_ptr(),
+            None if flags is None else flags.data_ptr(), ws.data_ptr(), out.data_ptr(), b, s, H, ln.eps)
+    st = torch.cuda.current_stream(x.device).cuda_stream
+    if form == "parts":
+        hip.pool_layernorm_parts(x.data_ptr(), y.data_ptr(), y.shape[0], b * s * H, bias.data_ptr(), *tail, f32=f32,
+                                 stream=st)
+    else:
+        hip.pool_layernorm(x.data_ptr(), y.data_ptr(), *tail, f32=f32, stream=st)
+    return out
 
 
 def _x3_buffer(x, lin, rows, H):
@@ -601,27 +663,35 @@ class _Layer(nn.Module):
     def forward(self, x, bias, mask_i32=None, packed=None):
         """packed (a PackPlan): x is the packed token list [1, t_cap, H] and
         attention stays within each row's own tokens."""
+        x = _proj_add_ln(x, self._attend(x, bias, mask_i32, packed), self.out, self.ln1, "out")
+        return _proj_add_ln(x, _proj(x, self.ffn1, "bias_gelu", name="ffn_up", x3_out=True), self.ffn2, self.ln2,
+                            "ffn_down")
+
+    def pooled(self, x, bias, mask_i32, attention_mask, flags):
+        """forward with the pooled LayerNorm (K32) as the layer's last step:
+        fp32 [b, H] sentence vectors instead of the hidden state."""
+        x = _proj_add_ln(x, self._attend(x, bias, mask_i32, None), self.out, self.ln1, "out")
+        return _proj_pool_ln(x, _proj(x, self.ffn1, "bias_gelu", name="ffn_up", x3_out=True), self.ffn2, self.ln2,
+                             "ffn_down", attention_mask, mask_i32, flags)
+
+    def _attend(self, x, bias, mask_i32, packed):
+        """The QKV projection and the attention behind it."""
         b, s, _ = x.shape
         if packed is not None:
             if _packed_ok(x, packed.s) and x.is_contiguous():
-                a = _attention_packed(_proj(x, self.qkv, "none", name="qkv"), packed, qkv_bias=self.qkv.bias)
-            elif _packed_f32_layer_ok(x, self, packed):
+                return _attention_packed(_proj(x, self.qkv, "none", name="qkv"), packed, qkv_bias=self.qkv.bias)
+            if _packed_f32_layer_ok(x, self, packed):
                 qkv = _proj(x, self.qkv, name="qkv")
-                a = _attention_packed(qkv.contiguous(), packed, f32=True,
-                                      x3_out=getattr(self.out, "w3", None) is not None)
-            else:
-                a = _attention_packed(_proj(x, self.qkv, name="qkv"), packed)
-        elif _k12_ok(x, s):
+                return _attention_packed(qkv.contiguous(), packed, f32=True,
+                                         x3_out=getattr(self.out, "w3", None) is not None)
+            return _attention_packed(_proj(x, self.qkv, name="qkv"), packed)
+        if _k12_ok(x, s):
             # plain GEMM (no bias epilogue: 152 vs 171 us at bs64 x 384,
             # profiles/r3_bert_gemm_layout.log); K12 applies the bias
             qkv = _proj(x, self.qkv, "none", name="qkv")
-            a = _attention(qkv, b, s, mask_i32, bias, qkv_bias=self.qkv.bias)
-        else:
-            a = _attention(_proj(x, self.qkv, name="qkv"), b, s, mask_i32, bias,
-                           x3_out=getattr(self.out, "w3", None) is not None and x.is_cuda)
-        x = _proj_add_ln(x, a, self.out, self.ln1, "out")
-        return _proj_add_ln(x, _proj(x, self.ffn1, "bias_gelu", name="ffn_up", x3_out=True), self.ffn2, self.ln2,
-                            "ffn_down")
+            return _attention(qkv, b, s, mask_i32, bias, qkv_bias=self.qkv.bias)
+        return _attention(_proj(x, self.qkv, name="qkv"), b, s, mask_i32, bias,
+                          x3_out=getattr(self.out, "w3", None) is not None and x.is_cuda)
 
 
 class BertLargeQA(nn.Module):
@@ -745,6 +815,30 @@ class BertLargeQA(nn.Module):
         for layer in self.layers:
             x = layer(x, bias, mask_i32)
         return _qa_head(x, self.qa)
+
+    def embed(self, input_ids, attention_mask, token_type_ids, flags=None, dense=False):
+        """Sentence embeddings, fp32 [b, 1024]: per row the mean of the last
+        hidden state over the tokens with attention_mask >= 1 (zeros for a row
+        without one), divided by its L2 norm.  ``flags`` (int [b], or None =
+        all 0) sets per row POOL_CLS (token 0 instead of the mean) and
+        POOL_RAW (no normalisation).  The encoder runs as in ``forward``
+        (``dense`` as there; it also promises every token is valid); the last
+        layer's FFN-down projection hands its result -- K11's or K11p's
+        operand form, whichever its route at this token count produces -- to
+        K32 (csrc/kernels/bert_pool.hip), which normalises and pools in one
+        pass and never writes the last hidden state.  bf16, and the
+        fp32-parity model (prepare_x3) in K32's fp32 form.  A row's embedding
+        is the same bits in any batch.  Off the GPU, in another dtype or with
+        TC_BERT_FUSED=0: plain torch ops with the same rules.  This is the
+        padded forward only: there is no packed (padding-free) form."""
+        x = self._embed(input_ids, token_type_ids)
+        if flags is not None:
+            flags = torch.as_tensor(flags, dtype=torch.int32, device=x.device).contiguous()
+        bias = None if dense else ((1.0 - attention_mask[:, None, None, :].to(x.dtype)) * -10000.0).to(x.dtype)
+        mask_i32 = None if dense else attention_mask.to(torch.int32).contiguous()
+        for layer in self.layers[:-1]:
+            x = layer(x, bias, mask_i32)
+        return self.layers[-1].pooled(x, bias, mask_i32, None if dense else attention_mask, flags)
 
 
 def init_weights(model, seed=0):

@@ -417,6 +417,19 @@ _SIGS = {
          ctypes.c_void_p],
         ctypes.c_int,
     ),
+    "tcamd_pool_layernorm": (
+        [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong,
+         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_float,
+         ctypes.c_int, ctypes.c_void_p],
+        ctypes.c_int,
+    ),
+    "tcamd_pool_layernorm_parts": (
+        [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_void_p,
+         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+         ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_int, ctypes.c_void_p],
+        ctypes.c_int,
+    ),
+    "tcamd_pool_layernorm_workspace": ([ctypes.c_int, ctypes.c_int], ctypes.c_size_t),
     "tcamd_k17_calls": ([], ctypes.c_longlong),
     "tcamd_x3_cat": ([ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p], ctypes.c_int),
     "tcamd_x3_stem": (
@@ -1695,6 +1708,38 @@ def add_layernorm_parts(x, parts, nparts, pstride, bias, gamma, beta, out, rows,
     _check(_load().tcamd_add_layernorm_parts3(x, _vp(parts), int(nparts), int(pstride), _vp(bias), gamma, beta, out,
                                               _vp(out3), int(rows), int(H), float(eps), 1 if f32 else 0, _vp(stream)),
            "add_layernorm_parts")
+
+
+def pool_layernorm_workspace(rows, S):
+    """Bytes of device workspace :func:`pool_layernorm` / :func:`pool_layernorm_parts`
+    need for ``rows`` rows of ``S`` tokens ([rows, ceil(S / 48), H + 1] fp32)."""
+    return int(_load().tcamd_pool_layernorm_workspace(int(rows), int(S)))
+
+
+def pool_layernorm(x, y, gamma, beta, mask, flags, workspace, out, rows, S, H, eps, f32=False, mask_stride=None,
+                   stream=None):
+    """K32, K11's operand form: out fp32 [rows][H] = the pooled LayerNorm(x + y)
+    * gamma + beta over x, y [rows][S][H] -- the mean over the tokens with
+    mask >= 1 (or token 0 where ``flags`` [rows] int32 has bit 0), divided
+    by its L2 norm (unless bit 1 is set).  x / y / gamma / beta bf16, or fp32 with
+    ``f32``; ``mask`` int32 [rows][S] at ``mask_stride`` elements per row
+    (default S) or None (every token valid); ``flags`` may be None (all 0).
+    A row without a valid token gives zeros.  H = 1024, 1 <= S <= 512.  A
+    row's result does not depend on the batch around it."""
+    _check(_load().tcamd_pool_layernorm(x, y, gamma, beta, _vp(mask), int(S if mask_stride is None else mask_stride),
+                                        _vp(flags), workspace, out, int(rows), int(S), int(H), float(eps),
+                                        1 if f32 else 0, _vp(stream)), "pool_layernorm")
+
+
+def pool_layernorm_parts(x, parts, nparts, pstride, bias, gamma, beta, mask, flags, workspace, out, rows, S, H, eps,
+                         f32=False, mask_stride=None, stream=None):
+    """K32, K11p's operand form: as :func:`pool_layernorm` with the LayerNorm's
+    input x + bias + the sum of ``nparts`` fp32 partial slabs (``parts`` + z *
+    ``pstride`` elements, [rows][S][H] each); bias fp32 [H] or None."""
+    _check(_load().tcamd_pool_layernorm_parts(x, _vp(parts), int(nparts), int(pstride), _vp(bias), gamma, beta,
+                                              _vp(mask), int(S if mask_stride is None else mask_stride), _vp(flags),
+                                              workspace, out, int(rows), int(S), int(H), float(eps),
+                                              1 if f32 else 0, _vp(stream)), "pool_layernorm_parts")
 
 
 def k17_last_tm():

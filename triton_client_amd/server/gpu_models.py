@@ -745,6 +745,9 @@ class BertLarge(DeviceModel):
     # plus a paragraph is typically 100-250 of the 384 tokens)
     PACKED_FILL = (128, 256)
     supports_packed = True
+    # elements of one row of every output (a subclass with other outputs sets
+    # it; the staging below goes by it and by len(outputs))
+    OUT_ROW = 384
 
     def __init__(self, version=1, device_id=0, use_graphs=True, layers=24, **kw):
         super().__init__(version, device_id, **kw)
@@ -783,24 +786,34 @@ class BertLarge(DeviceModel):
     def _build_model(self, bert, dev):
         return bert.build(device=dev, layers=self.layers)
 
-    def _make_slot(self, dev):
+    def _new_slot(self, dev):
+        """A slot's stream, device and pinned buffers, before any graph is captured."""
         torch = self.torch
-        n, s = self.max_batch_size, self.SEQ
+        n, s, k = self.max_batch_size, self.SEQ, len(self.outputs)
         slot = {"stream": torch.cuda.Stream(device=dev), "graphs": {},
                 "ins": [torch.zeros(n, s, device=dev, dtype=torch.int32) for _ in range(3)],
-                "outs": [torch.zeros(n, s, device=dev, dtype=torch.float32) for _ in range(2)],
+                "outs": [torch.zeros(n, self.OUT_ROW, device=dev, dtype=torch.float32) for _ in range(k)],
                 "ev": [torch.cuda.Event(enable_timing=True) for _ in range(4)]}
         slot["ins"][1].fill_(1)
         self._pinned(slot, "stage_host", 3 * n * s * 4)
-        self._pinned(slot, "out_host", 2 * n * s * 4)
+        self._pinned(slot, "out_host", k * n * self.OUT_ROW * 4)
+        return slot
+
+    def _forward(self, slot, b, dense):
+        """The model over the first ``b`` rows of the slot's inputs into its outputs."""
+        ids, mask, tt = (t[:b] for t in slot["ins"])
+        # synthetic load generators send arbitrary INT32: keep indices in range
+        # (an out-of-range embedding index is a device fault, not an error)
+        st, en = self.model(ids.long().remainder(30522), mask.clamp(0, 1), tt.long().clamp(0, 1), dense=dense)
+        slot["outs"][0][:b].copy_(st)
+        slot["outs"][1][:b].copy_(en)
+
+    def _make_slot(self, dev):
+        torch = self.torch
+        slot = self._new_slot(dev)
 
         def run(b, dense=False):
-            ids, mask, tt = (t[:b] for t in slot["ins"])
-            # synthetic load generators send arbitrary INT32: keep indices in range
-            # (an out-of-range embedding index is a device fault, not an error)
-            st, en = self.model(ids.long().remainder(30522), mask.clamp(0, 1), tt.long().clamp(0, 1), dense=dense)
-            slot["outs"][0][:b].copy_(st)
-            slot["outs"][1][:b].copy_(en)
+            self._forward(slot, b, dense)
 
         def run_packed(b, fill):
             ids, mask, tt = (t[:b] for t in slot["ins"])
@@ -867,12 +880,14 @@ class BertLarge(DeviceModel):
                 return int((slot["ins"][1][:total] >= 1).sum().item())
         return sum(int((pinned_view(ptr, np.int32, rows * self.SEQ) >= 1).sum()) for _, ptr, rows in parts)
 
-    def _run_batch(self, slot, srcs, outs, total):
+    def _run_batch(self, slot, srcs, outs, total, flags=None):
         """srcs: per input a list of (kind, ptr, rows) in row order; outs: per
-        output a list of (kind, ptr, first_row, rows).  Returns timings (ns)."""
+        output a list of (kind, ptr, first_row, rows); flags: per-row words for
+        the slot's ``flags`` array (a model whose graphs read one).  Returns
+        timings (ns)."""
         from triton_client_amd.ops import hip
 
-        row = self.SEQ * 4
+        row, orow = self.SEQ * 4, self.OUT_ROW * 4
         bucket = next(b for b in self.BUCKETS if b >= total)
         stream = slot["stream"]
         sh = stream.cuda_stream
@@ -898,6 +913,11 @@ class BertLarge(DeviceModel):
                 hip.batched_copy(c_src, c_dst, c_n, sh)
             if bucket > total:  # padding rows: keep them deterministic (mask 1, ids 0)
                 hip.memset_async(base + total * row, 0, (bucket - total) * row, sh)
+        if flags is not None:
+            words = pinned_view(slot["flags_host"], np.int32, self.max_batch_size)
+            words[:total] = flags
+            words[total:bucket] = 0
+            hip.memcpy_async(slot["flags"].data_ptr(), slot["flags_host"], bucket * 4, sh)
         pick = None
         if self.packed:
             tokens = self._count_tokens(slot, srcs[1], total)
@@ -927,21 +947,21 @@ class BertLarge(DeviceModel):
                 if not ptr:
                     continue
                 if kind == 1:
-                    c_src.append(base + first * row)
+                    c_src.append(base + first * orow)
                     c_dst.append(ptr)
-                    c_n.append(rows * row)
+                    c_n.append(rows * orow)
                 else:
                     host_outs.append((k, ptr, first, rows))
             if c_src:
                 hip.batched_copy(c_src, c_dst, c_n, sh)
         if host_outs:
-            for k in range(2):
-                hip.memcpy_async(slot["out_host"] + k * self.max_batch_size * row, slot["outs"][k].data_ptr(),
-                                 total * row, sh)
+            for k in range(len(outs)):
+                hip.memcpy_async(slot["out_host"] + k * self.max_batch_size * orow, slot["outs"][k].data_ptr(),
+                                 total * orow, sh)
         ev[3].record(stream)
         hip.stream_synchronize(sh)
         for k, ptr, first, rows in host_outs:
-            ctypes.memmove(ptr, slot["out_host"] + k * self.max_batch_size * row + first * row, rows * row)
+            ctypes.memmove(ptr, slot["out_host"] + k * self.max_batch_size * orow + first * orow, rows * orow)
         return [int(ev[0].elapsed_time(ev[1]) * 1e6), int(ev[1].elapsed_time(ev[2]) * 1e6),
                 int(ev[2].elapsed_time(ev[3]) * 1e6)]
 
@@ -966,7 +986,8 @@ class BertLarge(DeviceModel):
         for k in range(3):
             b.timing_ns[k] = t[k]
 
-    def execute(self, requests):
+    def execute(self, requests, flags=None):
+        """flags: per request the word its rows get in the slot's ``flags`` array."""
         total = 0
         plan = []
         for r in requests:
@@ -987,19 +1008,21 @@ class BertLarge(DeviceModel):
                     a = np.ascontiguousarray(t.data, dtype=np.int32)
                     keep.append(a)
                     srcs[k].append((0, a.ctypes.data, n))
+        if flags is not None:
+            flags = np.repeat(np.asarray(flags, dtype=np.int32), [n for _, _, n in plan])
         if all(getattr(r, "accepts_device_outputs", False) for r in requests):
-            return self._execute_device_outputs(requests, plan, srcs, total)
+            return self._execute_device_outputs(requests, plan, srcs, total, flags)
         # outputs come back to host; shm targets are filled by the server (deliver_to_shm)
-        res = np.empty((2, total, self.SEQ), dtype=np.float32)
-        outs = [[(0, res[k].ctypes.data, 0, total)] for k in range(2)]
+        res = np.empty((len(self.outputs), total, self.OUT_ROW), dtype=np.float32)
+        outs = [[(0, res[k].ctypes.data, 0, total)] for k in range(len(self.outputs))]
         with self._slots.slot() as (_, slot):
-            t = self._run_batch(slot, srcs, outs, total)
+            t = self._run_batch(slot, srcs, outs, total, flags)
         if self._batch_stats is not None:
             self._batch_stats(total, len(requests), *t)
-        return [[OutputTensor("start_logits", "FP32", [n, self.SEQ], res[0, f:f + n]),
-                 OutputTensor("end_logits", "FP32", [n, self.SEQ], res[1, f:f + n])] for _, f, n in plan]
+        return [[OutputTensor(o.name, "FP32", [n, self.OUT_ROW], res[k, f:f + n]) for k, o in enumerate(self.outputs)]
+                for _, f, n in plan]
 
-    def _execute_device_outputs(self, requests, plan, srcs, total):
+    def _execute_device_outputs(self, requests, plan, srcs, total, flags=None):
         """A batch of ensemble steps (``accepts_device_outputs`` on every request,
         core._infer_ensemble): the logits stay on the device.  The rows go from
         the slot's output buffers, which the next batch overwrites, into a tensor
@@ -1007,19 +1030,20 @@ class BertLarge(DeviceModel):
         _run_batch), and each request gets its rows of it as ``DeviceView`` with
         the tensor as ``owner``."""
         torch = self.torch
-        row = self.SEQ * 4
+        row = self.OUT_ROW * 4
         with self._slots.slot() as (_, slot):
             with torch.cuda.stream(slot["stream"]):
-                res = torch.empty((2, total, self.SEQ), device=slot["stream"].device, dtype=torch.float32)
-            outs = [[(1, res[k].data_ptr(), 0, total)] for k in range(2)]
-            t = self._run_batch(slot, srcs, outs, total)  # ends with a stream synchronise
+                res = torch.empty((len(self.outputs), total, self.OUT_ROW), device=slot["stream"].device,
+                                  dtype=torch.float32)
+            outs = [[(1, res[k].data_ptr(), 0, total)] for k in range(len(self.outputs))]
+            t = self._run_batch(slot, srcs, outs, total, flags)  # ends with a stream synchronise
         if self._batch_stats is not None:
             self._batch_stats(total, len(requests), *t)
         out = []
         for _, f, n in plan:
             tensors = []
-            for k, nm in enumerate(("start_logits", "end_logits")):
-                o = OutputTensor(nm, "FP32", [n, self.SEQ],
+            for k, spec in enumerate(self.outputs):
+                o = OutputTensor(spec.name, "FP32", [n, self.OUT_ROW],
                                  DeviceView(res[k].data_ptr() + f * row, n * row, self.device_id))
                 o.owner = res  # keeps the device memory alive while the ensemble holds the tensor
                 tensors.append(o)
@@ -1060,6 +1084,69 @@ class BertLargeFP32(BertLarge):
         import torch
 
         return bert.prepare_x3(bert.build(device=dev, dtype=torch.float32, layers=self.layers))
+
+
+class BertLargeEmbed(BertLarge):
+    """``bert_large_embed`` -- sentence embeddings from the same BERT-large
+    encoder: ``bert_large``'s three inputs in, ``embedding`` FP32 [1024] out
+    (``BertLargeQA.embed``: the last LayerNorm and the pooling are one kernel,
+    K32, csrc/kernels/bert_pool.hip).  Opt-in through ``--models``: it holds its
+    own copy of the weights.  Buckets, the masked / dense graph choice and the
+    staging of inputs and outputs (host or ``DeviceView``) are the base
+    class's; the graphs capture ``embed``.
+
+    Custom request parameters: ``pooling`` (``"mean"``, the default: the mean
+    over the tokens with attention_mask >= 1; or ``"cls"``: token 0) and
+    ``normalize`` (bool, default true: divide by the L2 norm).  They are
+    checked per request -- a bad value fails that request alone -- and become
+    the per-row flag words of a device array that the captured graph reads, so
+    requests with different settings share a batch.  A row's embedding does
+    not depend on the batch it was served in.  Python executor only."""
+
+    name = "bert_large_embed"
+    outputs = (TensorSpec("embedding", "FP32", [1024]),)
+    OUT_ROW = 1024
+    supports_native = False
+    supports_packed = False  # embed has no padding-free form
+
+    @staticmethod
+    def request_flags(parameters):
+        """The K32 flags word of a request's ``pooling`` / ``normalize``
+        parameters; ServerError for a value that is not one of theirs."""
+        from triton_client_amd.models.bert import POOL_CLS, POOL_RAW
+
+        pooling = parameters.get("pooling", "mean")
+        if not isinstance(pooling, str) or pooling not in ("mean", "cls"):
+            raise ServerError('request parameter pooling must be "mean" or "cls", not %r' % (pooling,))
+        normalize = parameters.get("normalize", True)
+        if not isinstance(normalize, (bool, np.bool_)):
+            raise ServerError("request parameter normalize must be a bool, not %r" % (normalize,))
+        return (POOL_CLS if pooling == "cls" else 0) | (0 if normalize else POOL_RAW)
+
+    def _new_slot(self, dev):
+        slot = super()._new_slot(dev)
+        slot["flags"] = self.torch.zeros(self.max_batch_size, device=dev, dtype=self.torch.int32)
+        self._pinned(slot, "flags_host", self.max_batch_size * 4)
+        return slot
+
+    def _forward(self, slot, b, dense):
+        ids, mask, tt = (t[:b] for t in slot["ins"])
+        e = self.model.embed(ids.long().remainder(30522), mask.clamp(0, 1), tt.long().clamp(0, 1),
+                             flags=slot["flags"][:b], dense=dense)
+        slot["outs"][0][:b].copy_(e)
+
+    def execute(self, requests):
+        results, good, flags = [None] * len(requests), [], []
+        for i, r in enumerate(requests):
+            try:
+                flags.append(self.request_flags(r.parameters))
+                good.append(i)
+            except ServerError as e:
+                results[i] = e
+        if good:
+            for i, res in zip(good, super().execute([requests[i] for i in good], flags)):
+                results[i] = res
+        return results
 
 
 class QaSpans(DeviceModel):
@@ -1337,6 +1424,31 @@ class BertQaTextEnsemble(Ensemble):
     ]
 
 
+class BertEmbedTextEnsemble(Ensemble):
+    """Ensemble: UTF-8 text -> ``bert_tokenizer`` -> ``bert_large_embed``: one
+    FP32 [1024] ``embedding`` per row.  The ids stay on the device between the
+    steps.  ``pooling``, ``normalize`` and ``max_query_length`` travel as the
+    ensemble's custom request parameters to the steps that read them.  Opt-in
+    with ``bert_large_embed``.
+
+    A single text goes as ``context`` with an empty ``question``: the
+    tokenizer accepts an empty question and builds ``[CLS] [SEP] text [SEP]``,
+    so the text has 381 of the 384 positions (as ``question`` it would be cut
+    at ``max_query_length``).  A pair of texts goes as question and context."""
+
+    name = "bert_embed_text_ensemble"
+    max_batch_size = 128
+    inputs = BertTokenizer.inputs
+    outputs = BertLargeEmbed.outputs
+    ensemble_steps = [
+        ("bert_tokenizer", {"question": "question", "context": "context"},
+         {"input_ids": "input_ids", "attention_mask": "attention_mask", "token_type_ids": "token_type_ids"}),
+        ("bert_large_embed", {"input_ids": "input_ids", "attention_mask": "attention_mask",
+                              "token_type_ids": "token_type_ids"},
+         {"embedding": "embedding"}),
+    ]
+
+
 class BertWindowTokenizer(DeviceModel):
     """``bert_window_tokenizer`` on the GPU: the same I/O contract, request
     parameters, vocabulary and rule as the CPU model of that name
@@ -1557,4 +1669,6 @@ GPU_MODELS = [DensenetOnnx, PreprocessInception, PreprocessInceptionEnsemble, Be
               BertTokenizer, BertQaTextEnsemble, BertWindowTokenizer, QaDocSpans, BertQaDocEnsemble]
 # loaded only when --models names them: bert_large_fp32 adds ~2 GB of bf16x3
 # weights and 28 captured HIP graphs per instance (round-5 advisor finding)
-OPT_IN_GPU_MODELS = [BertLargeFP32]
+# bert_large_embed holds a second copy of the bf16 weights and its own graphs;
+# its text ensemble comes with it
+OPT_IN_GPU_MODELS = [BertLargeFP32, BertLargeEmbed, BertEmbedTextEnsemble]

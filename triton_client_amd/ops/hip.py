@@ -452,6 +452,16 @@ _SIGS = {
          ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p],
         ctypes.c_int,
     ),
+    # K33 embedding search (csrc/kernels/embed_search.hip)
+    "tcamd_search_plan": (
+        [ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)], ctypes.c_int,
+    ),
+    "tcamd_search_workspace": ([ctypes.c_int, ctypes.c_int], ctypes.c_uint64),
+    "tcamd_search_topk": (
+        [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+         ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p],
+        ctypes.c_int,
+    ),
     "tcamd_x3_split": (
         [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p],
         ctypes.c_int,
@@ -1611,6 +1621,71 @@ def x3_classifier(a_hi, a_lo, w_hi, w_lo, bias, out, b, N, K, ldc=None, stream=N
 def x3_split(w, hi, lo, n, stream=None):
     """fp32 -> (bf16 hi, bf16 lo) planes on the device: w ~= hi + lo to 2^-17."""
     _check(_load().tcamd_x3_split(w, hi, lo, int(n), _vp(stream)), "x3_split")
+
+
+SEARCH_KMAX = 64  # TCAMD_SEARCH_KMAX (csrc/kernels/embed_search.hip), = TOPK_KMAX
+SEARCH_MAX_ROWS = 128
+
+
+def search_index(corpus, device=None):
+    """K33 corpus layout: fp32 [N][D] (a torch tensor or a numpy array) -> (hi,
+    lo) bf16 planes [64 ceil(N/64)][D] on the device (``corpus``'s own if it is
+    there already, else ``device``, default the current GPU), corpus ~= hi + lo
+    (RNE both), the rows past N zero.  Built once per corpus."""
+    import torch
+
+    c = corpus
+    if len(c.shape) != 2 or c.shape[0] < 1:
+        raise ValueError("search_index takes a [N, D] corpus, N >= 1")
+    if isinstance(c, torch.Tensor) and c.is_cuda:
+        device = c.device
+    elif device is None:
+        device = torch.device("cuda")
+    n, d = c.shape
+    hi = torch.zeros((n + 63) // 64 * 64, d, dtype=torch.bfloat16, device=device)
+    lo = torch.zeros_like(hi)
+    for at in range(0, n, 1 << 16):  # by 65,536 rows: the fp32 copies stay small
+        part = c[at:at + (1 << 16)]
+        if not isinstance(part, torch.Tensor):
+            part = torch.from_numpy(np.array(part, dtype=np.float32))  # a copy: the source may be read-only
+        part = part.to(device=device, dtype=torch.float32)
+        h = part.to(torch.bfloat16)
+        hi[at:at + part.shape[0]] = h
+        lo[at:at + part.shape[0]] = (part - h.float()).to(torch.bfloat16)
+    return hi, lo
+
+
+def search_plan(rows, N):
+    """(slices, group) of K33's first launch, a function of (rows, N) alone: the
+    grid is ceil(rows / group) query groups by ``slices`` corpus slices.  Host only."""
+    sl, g = ctypes.c_int(0), ctypes.c_int(0)
+    _check(_load().tcamd_search_plan(int(rows), int(N), ctypes.byref(sl), ctypes.byref(g)), "search_plan")
+    return sl.value, g.value
+
+
+def search_workspace(rows, N):
+    """Bytes of device workspace that serve :func:`search_topk` for up to ``rows``
+    queries over up to ``N`` corpus rows, whatever ``kmax``: the size grows with
+    both (the plan's own ``rows * slices`` does not: fewer rows get more slices),
+    so a buffer sized for the largest batch covers every smaller one."""
+    return int(_load().tcamd_search_workspace(int(rows), int(N)))
+
+
+def search_topk(q, q_stride_bytes, rows, idx_hi, idx_lo, N, D, k_row, kmax, workspace, indices, scores, stream=None):
+    """K33: for each of ``rows`` fp32 query rows (device pointer ``q``, rows
+    ``q_stride_bytes`` apart) the ``min(k_row[r], kmax)`` corpus rows of the
+    largest dot product, the product taken as bf16x3 against the planes of
+    :func:`search_index` and never written out.  ``indices`` int32 / ``scores``
+    fp32 [rows][kmax], ordered like ``np.argsort(-score, kind="stable")`` on the
+    kernel's own fp32 scores; ranks at and past ``N`` hold ``(-1, -FLT_MAX)``.
+    ``k_row`` is a device int32 array, 0 skips the row; slots past a row's count
+    are left untouched.  rows <= 128, D % 64 == 0 and D <= 1024, kmax <=
+    :data:`SEARCH_KMAX`; ``workspace`` of :func:`search_workspace` bytes.  A
+    query's answer is the same bits alone and in any batch.  All arguments but
+    the sizes are device pointers."""
+    _check(_load().tcamd_search_topk(_vp(q), int(q_stride_bytes), int(rows), _vp(idx_hi), _vp(idx_lo), int(N), int(D),
+                                     _vp(k_row), int(kmax), _vp(workspace), _vp(indices), _vp(scores), _vp(stream)),
+           "search_topk")
 
 
 def dn_head_pool(x, scale, bias, out, imgs, HW, C, stream=None):

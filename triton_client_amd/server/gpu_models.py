@@ -1449,6 +1449,175 @@ class BertEmbedTextEnsemble(Ensemble):
     ]
 
 
+class EmbedSearch(DeviceModel):
+    """``embed_search`` -- the nearest rows of a corpus of embeddings: FP32
+    [1024] ``embedding`` in; per row INT32 ``indices`` [top_k] and FP32
+    ``scores`` [top_k] out, the corpus rows of the largest dot product in K19's
+    order (scores descending, ties to the lower index).  Per batch K33
+    ``search_topk`` (csrc/kernels/embed_search.hip) takes the bf16x3 product
+    against the index planes built at load and selects on the chip: no
+    ``[rows, N]`` score matrix is written, and a row's answer is the same bits
+    in any batch.  Ranks past the corpus hold ``(-1, -FLT_MAX)``.
+
+    Custom request parameter: ``top_k`` (int, 1..64, default 10), checked per
+    request -- a bad value fails that request alone -- and written to the
+    row's ``k_row`` entry, so requests with different ``top_k`` share a launch.
+
+    An input that arrives as ``DeviceView`` (a HIP shm region, or the embedding
+    ``bert_large_embed`` left on the device for the ensemble) is read in place;
+    a host input goes up through the slot's pinned staging buffer.  As with
+    ``qa_spans`` a batch is launched once per run of requests whose rows follow
+    each other in memory, and its outputs come back in one copy.
+
+    The corpus: the constructor option ``corpus=`` (an fp32 [N, 1024] array or
+    the path of an ``.npy`` file holding one), else ``TCAMD_SEARCH_CORPUS``
+    (such a path, read at load), else ``SYNTH_ROWS`` seeded unit vectors made
+    on the device (``bert_large``'s weights are synthetic too).  Opt-in through
+    ``--models``; Python executor only."""
+
+    name = "embed_search"
+    max_batch_size = 128
+    DIM = 1024
+    TOP_K, TOP_K_MAX = 10, 64
+    SYNTH_ROWS, SYNTH_SEED = 65536, 33
+    inputs = (TensorSpec("embedding", "FP32", [1024]),)
+    outputs = (TensorSpec("indices", "INT32", [-1]), TensorSpec("scores", "FP32", [-1]))
+    dynamic_batching = {"preferred": [], "max_queue_delay_us": 100}
+    instance_kind = "KIND_GPU"
+    instance_count = 2
+    gpus = (0,)
+
+    @staticmethod
+    def request_top_k(parameters):
+        """A request's ``top_k``; ServerError for a value that is not an int in [1, 64]."""
+        k, kmax = parameters.get("top_k", EmbedSearch.TOP_K), EmbedSearch.TOP_K_MAX
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= k <= kmax:
+            raise ServerError("request parameter top_k must be an int in [1, %d], not %r" % (kmax, k))
+        return int(k)
+
+    def load(self):
+        torch, hip, dev = self._gpu()
+        corpus = self.options.get("corpus")
+        if corpus is None:
+            corpus = os.environ.get("TCAMD_SEARCH_CORPUS") or None
+        if isinstance(corpus, (str, os.PathLike)):
+            corpus = np.load(corpus)
+        if corpus is None:
+            g = torch.Generator(device=dev)
+            g.manual_seed(self.SYNTH_SEED)
+            corpus = torch.randn(self.SYNTH_ROWS, self.DIM, generator=g, device=dev, dtype=torch.float32)
+            corpus /= corpus.norm(dim=1, keepdim=True)
+        if len(corpus.shape) != 2 or corpus.shape[0] < 1 or corpus.shape[1] != self.DIM:
+            raise ServerError("embed_search: the corpus must be fp32 [N >= 1, %d], not %s"
+                              % (self.DIM, list(corpus.shape)))
+        self.corpus_rows = int(corpus.shape[0])
+        self.index = hip.search_index(corpus, device=dev)
+        n = self.max_batch_size
+        self.in_bytes = n * self.DIM * 4 + n * 4  # the rows, then k_row
+        self.out_bytes = n * hip.SEARCH_KMAX * 8
+        self._add_stage_slots(dev, self.in_bytes, self.out_bytes, ws=hip.search_workspace(n, self.corpus_rows))
+
+    @classmethod
+    def plan(cls, requests):
+        """Per request ``(first_row, rows, top_k)``, or the ServerError of its
+        parameter; and the rows of the batch."""
+        out, total = [], 0
+        for r in requests:
+            try:
+                k = cls.request_top_k(r.parameters)
+            except ServerError as e:
+                out.append(e)
+                continue
+            n = int(r.input("embedding").shape[0])
+            out.append((total, n, k))
+            total += n
+        return out, total
+
+    def execute(self, requests):
+        from triton_client_amd.ops import hip
+
+        plan, total = self.plan(requests)
+        if total == 0:
+            return plan
+        if total > self.max_batch_size:
+            return [ServerError("batch of %d rows exceeds max_batch_size" % total)] * len(requests)
+        try:
+            with self._slots.slot() as (_, slot):
+                indices, scores = self._execute(slot, requests, plan, total)
+        except (ServerError, hip.HipError) as e:
+            return plan_errors(plan, self.name, e)
+        res = []
+        for p in plan:
+            if isinstance(p, Exception):
+                res.append(p)
+                continue
+            first, n, k = p
+            res.append([self.out("indices", np.ascontiguousarray(indices[first:first + n, :k])),
+                        self.out("scores", np.ascontiguousarray(scores[first:first + n, :k]))])
+        return res
+
+    def _execute(self, slot, requests, plan, total):
+        from triton_client_amd.ops import hip
+
+        n_max, row = self.max_batch_size, self.DIM * 4
+        sh = slot["stream"].cuda_stream
+        in_host, in_dev = slot["in_host"], slot["in_dev"].data_ptr()
+        good = [(r, p) for r, p in zip(requests, plan) if not isinstance(p, Exception)]
+        par = n_max * row
+        k_row = pinned_view(in_host + par, np.int32, n_max)
+        for _, (first, n, k) in good:
+            k_row[first:first + n] = k
+        kmax = int(k_row[:total].max())
+        hip.memcpy_async(in_dev + par, in_host + par, total * 4, sh)
+        lo, hi, at = None, 0, []  # the staged rows go up in one copy
+        for r, (first, n, _) in good:
+            ptr, staged = place_input(slot, r.input("embedding"), "embedding", np.float32, n * row, first * row)
+            if staged:
+                lo, hi = first if lo is None else lo, first + n
+            elif ptr % 16:  # K33 reads 16 bytes at a time: a region off that grid is copied to the stage
+                hip.memcpy_async(in_dev + first * row, ptr, n * row, sh)
+                ptr = in_dev + first * row
+            at.append(ptr)
+        if lo is not None:
+            hip.memcpy_async(in_dev + lo * row, in_host + lo * row, (hi - lo) * row, sh)
+        out_dev = slot["out_dev"].data_ptr()
+        o_scores = total * kmax * 4
+        # one launch per run of requests that follow each other in memory
+        g = 0
+        while g < len(good):
+            first = good[g][1][0]
+            h, rows = g + 1, good[g][1][1]
+            while h < len(good) and at[h] == at[g] + (good[h][1][0] - first) * row:
+                rows += good[h][1][1]
+                h += 1
+            hip.search_topk(at[g], row, rows, self.index[0].data_ptr(), self.index[1].data_ptr(), self.corpus_rows,
+                            self.DIM, in_dev + par + first * 4, kmax, slot["ws"].data_ptr(),
+                            out_dev + first * kmax * 4, out_dev + o_scores + first * kmax * 4, stream=sh)
+            g = h
+        raw = download(hip, slot, total * kmax * 8, sh)
+        return (raw[:o_scores].view(np.int32).reshape(total, kmax),
+                raw[o_scores:].view(np.float32).reshape(total, kmax))
+
+
+class BertSearchTextEnsemble(Ensemble):
+    """Ensemble: UTF-8 text -> ``bert_tokenizer`` -> ``bert_large_embed`` ->
+    ``embed_search``: per text the ``indices`` and ``scores`` of its nearest
+    corpus rows.  The ids stay on the device between the first two steps and
+    the embedding between the last two (K33 reads it in place).  ``pooling``,
+    ``normalize``, ``max_query_length`` and ``top_k`` travel as the ensemble's
+    custom request parameters to the steps that read them.  ``embedding`` is an
+    output too; a request that does not ask for it does not pay for its copy.
+    Texts go in as for ``bert_embed_text_ensemble``.  Opt-in with its steps."""
+
+    name = "bert_search_text_ensemble"
+    max_batch_size = 128
+    inputs = BertTokenizer.inputs
+    outputs = EmbedSearch.outputs + BertLargeEmbed.outputs
+    ensemble_steps = BertEmbedTextEnsemble.ensemble_steps + [
+        ("embed_search", {"embedding": "embedding"}, {"indices": "indices", "scores": "scores"}),
+    ]
+
+
 class BertWindowTokenizer(DeviceModel):
     """``bert_window_tokenizer`` on the GPU: the same I/O contract, request
     parameters, vocabulary and rule as the CPU model of that name
@@ -1671,4 +1840,5 @@ GPU_MODELS = [DensenetOnnx, PreprocessInception, PreprocessInceptionEnsemble, Be
 # weights and 28 captured HIP graphs per instance (round-5 advisor finding)
 # bert_large_embed holds a second copy of the bf16 weights and its own graphs;
 # its text ensemble comes with it
-OPT_IN_GPU_MODELS = [BertLargeFP32, BertLargeEmbed, BertEmbedTextEnsemble]
+# embed_search holds a corpus index (256 MB for the synthetic one); its text ensemble comes with it
+OPT_IN_GPU_MODELS = [BertLargeFP32, BertLargeEmbed, BertEmbedTextEnsemble, EmbedSearch, BertSearchTextEnsemble]

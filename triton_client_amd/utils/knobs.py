@@ -124,6 +124,10 @@ KNOBS = [
          "batch-invariant routes: an image's logits are the same bits in every batch, at a lower speed; 0 = the "
          "library's fp32 GEMM and the fastest routes",
          "tests/test_densenet_head_knob.py::test_the_knob_selects_the_classifier"),
+    Knob("TCAMD_SEARCH_CORPUS", "python", "", "server/gpu_models.py",
+         "embed_search: the .npy file (fp32 [N, 1024]) whose rows are the corpus, read at load unless the model's "
+         "corpus= option names one; unset = 65,536 seeded synthetic unit vectors made on the device",
+         "tests/test_embed_search_served_gpu.py::test_the_corpus_comes_from_the_environment"),
     Knob("TCAMD_BERT_VOCAB", "python", "", "utils/wordpiece.py",
          "bert_tokenizer: the vocab.txt to load (the server's --bert-vocab sets it); unset = the demonstration "
          "vocabulary triton_client_amd/data/bert_demo_vocab.txt",

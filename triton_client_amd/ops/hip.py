@@ -462,6 +462,26 @@ _SIGS = {
          ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p],
         ctypes.c_int,
     ),
+    # K34 int8 index + exact rescore (csrc/kernels/embed_search_q8.hip)
+    "tcamd_search_quantize_q8": (
+        [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p], ctypes.c_int,
+    ),
+    "tcamd_search_q8_plan": (
+        [ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)], ctypes.c_int,
+    ),
+    "tcamd_search_q8_workspace": ([ctypes.c_int, ctypes.c_int], ctypes.c_uint64),
+    "tcamd_search_topk_q8": (
+        [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+         ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
+         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p],
+        ctypes.c_int,
+    ),
+    "tcamd_search_topk_q8_timed": (
+        [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+         ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
+         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_float)],
+        ctypes.c_int,
+    ),
     "tcamd_x3_split": (
         [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p],
         ctypes.c_int,
@@ -1686,6 +1706,95 @@ def search_topk(q, q_stride_bytes, rows, idx_hi, idx_lo, N, D, k_row, kmax, work
     _check(_load().tcamd_search_topk(_vp(q), int(q_stride_bytes), int(rows), _vp(idx_hi), _vp(idx_lo), int(N), int(D),
                                      _vp(k_row), int(kmax), _vp(workspace), _vp(indices), _vp(scores), _vp(stream)),
            "search_topk")
+
+
+SEARCH_Q8_KMAX = 16  # TCAMD_SEARCH_Q8_KMAX (csrc/kernels/embed_search_q8.hip)
+
+
+def search_index_q8(corpus, device=None):
+    """K34 compact index: fp32 [N][D] (a torch tensor or a numpy array) ->
+    (``codes`` int8 [64 ceil(N/64)][D], ``scales`` fp32 [64 ceil(N/64)]) on the
+    device, chosen as in :func:`search_index`.  Per row ``scales[n] = max|c[n]|
+    / 127`` and ``codes[n][d] = clamp(rint(c[n][d] * (127 / max|c[n]|)), -127,
+    127)``; an all-zero row has scale 0 and codes 0, and so have the rows past
+    N.  Quantised by a HIP kernel (``search_quantize_q8``, one wave a row), D %
+    16 == 0 and D <= 1024.  Built once per corpus.  :func:`search_topk_q8` also
+    needs the planes of :func:`search_index`, so a compact search holds both
+    indexes, 5 bytes an element: what it saves is bandwidth, not memory."""
+    import torch
+
+    c = corpus
+    if len(c.shape) != 2 or c.shape[0] < 1:
+        raise ValueError("search_index_q8 takes a [N, D] corpus, N >= 1")
+    if isinstance(c, torch.Tensor) and c.is_cuda:
+        device = c.device
+    elif device is None:
+        device = torch.device("cuda")
+    n, d = c.shape
+    codes = torch.zeros((n + 63) // 64 * 64, d, dtype=torch.int8, device=device)
+    scales = torch.zeros((n + 63) // 64 * 64, dtype=torch.float32, device=device)
+    with torch.cuda.device(device):
+        stream = torch.cuda.current_stream().cuda_stream
+        for at in range(0, n, 1 << 16):  # by 65,536 rows: the fp32 copies stay small
+            part = c[at:at + (1 << 16)]
+            if not isinstance(part, torch.Tensor):
+                part = torch.from_numpy(np.array(part, dtype=np.float32))  # a copy: the source may be read-only
+            part = part.to(device=device, dtype=torch.float32).contiguous()
+            _check(_load().tcamd_search_quantize_q8(part.data_ptr(), part.shape[0], d, codes[at:].data_ptr(),
+                                                    scales[at:].data_ptr(), _vp(stream)), "search_index_q8")
+        torch.cuda.current_stream().synchronize()  # `part` is read until here
+    return codes, scales
+
+
+def search_q8_plan(rows, N):
+    """(slices, group) of K34's first launch, a function of (rows, N) alone:
+    ``group`` is 16 query rows when ``rows <= 16``, else 64, and the grid is
+    ceil(rows / group) query groups by ``slices`` corpus slices.  Host only."""
+    sl, g = ctypes.c_int(0), ctypes.c_int(0)
+    _check(_load().tcamd_search_q8_plan(int(rows), int(N), ctypes.byref(sl), ctypes.byref(g)), "search_q8_plan")
+    return sl.value, g.value
+
+
+def search_q8_workspace(rows, N):
+    """Bytes of device workspace that serve :func:`search_topk_q8` for up to
+    ``rows`` queries over up to ``N`` corpus rows: the ``[rows][64]`` int32
+    shortlist and the slices' key lists.  The size grows with both arguments,
+    so a buffer sized for the largest batch covers every smaller one."""
+    return int(_load().tcamd_search_q8_workspace(int(rows), int(N)))
+
+
+def search_topk_q8(q, q_stride_bytes, rows, codes, scales, idx_hi, idx_lo, N, D, k_row, kmax, slots, workspace,
+                   indices, scores, stream=None):
+    """K34: :func:`search_topk` for ``kmax <= SEARCH_Q8_KMAX`` through the int8
+    index of :func:`search_index_q8`.  The codes are scanned on the integer
+    matrix pipe for each query's 64 best rows by ``dot(codes_q, codes_c) *
+    scales[c]``; those 64 get K33's own bf16x3 score against the planes of
+    :func:`search_index` (``idx_hi`` / ``idx_lo``), and the best
+    ``min(k_row[r], kmax)`` of them go to ``indices`` int32 / ``scores`` fp32
+    ``[rows][slots]`` in K33's order.  A returned pair's score is bit for bit
+    what :func:`search_topk` gives that pair; a row that the int8 scan ranks
+    past 64 cannot be returned.  Ranks at and past ``min(N, 64)`` hold ``(-1,
+    -FLT_MAX)``; ``k_row[r] == 0`` skips the row and slots past a row's count
+    are left untouched.  rows <= 128, D % 128 == 0 and D <= 1024, ``kmax <=
+    slots <= 64``; ``workspace`` of :func:`search_q8_workspace` bytes.  A
+    query's answer is the same bits alone and in any batch.  All arguments but
+    the sizes are device pointers."""
+    _check(_load().tcamd_search_topk_q8(_vp(q), int(q_stride_bytes), int(rows), _vp(codes), _vp(scales), _vp(idx_hi),
+                                        _vp(idx_lo), int(N), int(D), _vp(k_row), int(kmax), int(slots),
+                                        _vp(workspace), _vp(indices), _vp(scores), _vp(stream)), "search_topk_q8")
+
+
+def search_topk_q8_timed(q, q_stride_bytes, rows, codes, scales, idx_hi, idx_lo, N, D, k_row, kmax, slots, workspace,
+                         indices, scores, stream=None):
+    """One :func:`search_topk_q8` call, waited for: (microseconds of the coarse
+    launch, microseconds of the shortlist and rescore launches), each between
+    two device events.  For tools/search_bench.py."""
+    us = (ctypes.c_float * 2)()
+    _check(_load().tcamd_search_topk_q8_timed(_vp(q), int(q_stride_bytes), int(rows), _vp(codes), _vp(scales),
+                                              _vp(idx_hi), _vp(idx_lo), int(N), int(D), _vp(k_row), int(kmax),
+                                              int(slots), _vp(workspace), _vp(indices), _vp(scores), _vp(stream), us),
+           "search_topk_q8_timed")
+    return float(us[0]), float(us[1])
 
 
 def dn_head_pool(x, scale, bias, out, imgs, HW, C, stream=None):

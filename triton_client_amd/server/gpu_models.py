@@ -1469,6 +1469,15 @@ class EmbedSearch(DeviceModel):
     ``qa_spans`` a batch is launched once per run of requests whose rows follow
     each other in memory, and its outputs come back in one copy.
 
+    The constructor option ``index="q8"`` (else ``TCAMD_SEARCH_INDEX=q8``;
+    default ``x3``, the above alone) adds K34 ``search_topk_q8``
+    (csrc/kernels/embed_search_q8.hip): load builds the int8 index beside the
+    planes (5 bytes an element in all: the gain is bandwidth, not memory), and
+    rows with ``top_k <= 16`` are scanned on the int8 codes for 64 candidates
+    that are rescored with K33's bits.  The route is chosen per row -- a
+    ``k_row`` array for each kernel, 0 where the row is the other's -- so a
+    request's answer never depends on its batch mates.
+
     The corpus: the constructor option ``corpus=`` (an fp32 [N, 1024] array or
     the path of an ``.npy`` file holding one), else ``TCAMD_SEARCH_CORPUS``
     (such a path, read at load), else ``SYNTH_ROWS`` seeded unit vectors made
@@ -1512,10 +1521,17 @@ class EmbedSearch(DeviceModel):
                               % (self.DIM, list(corpus.shape)))
         self.corpus_rows = int(corpus.shape[0])
         self.index = hip.search_index(corpus, device=dev)
+        kind = self.options.get("index") or os.environ.get("TCAMD_SEARCH_INDEX") or "x3"
+        if kind not in ("x3", "q8"):
+            raise ServerError("embed_search: index must be x3 or q8, not %r" % (kind,))
+        self.index_q8 = hip.search_index_q8(corpus, device=dev) if kind == "q8" else None
         n = self.max_batch_size
-        self.in_bytes = n * self.DIM * 4 + n * 4  # the rows, then k_row
+        self.in_bytes = n * self.DIM * 4 + 2 * n * 4  # the rows, then k_row of K33 and k_row of K34
         self.out_bytes = n * hip.SEARCH_KMAX * 8
-        self._add_stage_slots(dev, self.in_bytes, self.out_bytes, ws=hip.search_workspace(n, self.corpus_rows))
+        ws = hip.search_workspace(n, self.corpus_rows)
+        if self.index_q8 is not None:
+            ws = max(ws, hip.search_q8_workspace(n, self.corpus_rows))
+        self._add_stage_slots(dev, self.in_bytes, self.out_bytes, ws=ws)
 
     @classmethod
     def plan(cls, requests):
@@ -1564,11 +1580,13 @@ class EmbedSearch(DeviceModel):
         in_host, in_dev = slot["in_host"], slot["in_dev"].data_ptr()
         good = [(r, p) for r, p in zip(requests, plan) if not isinstance(p, Exception)]
         par = n_max * row
-        k_row = pinned_view(in_host + par, np.int32, n_max)
+        k_row = pinned_view(in_host + par, np.int32, 2 * n_max)  # [0]: K33's rows, [1]: K34's
+        q8 = self.index_q8 is not None
+        k_row[:] = 0
         for _, (first, n, k) in good:
-            k_row[first:first + n] = k
-        kmax = int(k_row[:total].max())
-        hip.memcpy_async(in_dev + par, in_host + par, total * 4, sh)
+            k_row[(n_max if q8 and k <= hip.SEARCH_Q8_KMAX else 0) + first:][:n] = k
+        kmax = int(k_row.max())
+        hip.memcpy_async(in_dev + par, in_host + par, 2 * n_max * 4, sh)
         lo, hi, at = None, 0, []  # the staged rows go up in one copy
         for r, (first, n, _) in good:
             ptr, staged = place_input(slot, r.input("embedding"), "embedding", np.float32, n * row, first * row)
@@ -1590,9 +1608,16 @@ class EmbedSearch(DeviceModel):
             while h < len(good) and at[h] == at[g] + (good[h][1][0] - first) * row:
                 rows += good[h][1][1]
                 h += 1
-            hip.search_topk(at[g], row, rows, self.index[0].data_ptr(), self.index[1].data_ptr(), self.corpus_rows,
-                            self.DIM, in_dev + par + first * 4, kmax, slot["ws"].data_ptr(),
-                            out_dev + first * kmax * 4, out_dev + o_scores + first * kmax * 4, stream=sh)
+            outs = (out_dev + first * kmax * 4, out_dev + o_scores + first * kmax * 4)
+            if k_row[first:first + rows].any():
+                hip.search_topk(at[g], row, rows, self.index[0].data_ptr(), self.index[1].data_ptr(),
+                                self.corpus_rows, self.DIM, in_dev + par + first * 4, kmax, slot["ws"].data_ptr(),
+                                *outs, stream=sh)
+            if k_row[n_max + first:n_max + first + rows].any():  # rows of top_k <= 16, the same output slots
+                hip.search_topk_q8(at[g], row, rows, self.index_q8[0].data_ptr(), self.index_q8[1].data_ptr(),
+                                   self.index[0].data_ptr(), self.index[1].data_ptr(), self.corpus_rows, self.DIM,
+                                   in_dev + par + (n_max + first) * 4, min(kmax, hip.SEARCH_Q8_KMAX), kmax,
+                                   slot["ws"].data_ptr(), *outs, stream=sh)
             g = h
         raw = download(hip, slot, total * kmax * 8, sh)
         return (raw[:o_scores].view(np.int32).reshape(total, kmax),

@@ -48,7 +48,8 @@ the host (the view) and on the device:
 * the *upload region* ``[0, used)`` is what the host writes and the H2D copy
   carries: raw pixels at any alignment, ``HOST`` coefficient buffers at
   multiples of 128, packed streams and the staged bytes of a PNG at multiples
-  of 16;
+  of 16; the bytes an alignment skips are zeroed, so the region is a function
+  of what was added and never of what the buffer held before;
 * the *device-only region* ``[top, capacity)`` is written by kernels alone: for
   a ``K23`` or ``K24`` JPEG the pixels at ``top - pixel_bytes`` and the
   coefficients at ``(top - pixel_bytes - coef_bytes) // 128 * 128``, which is
@@ -232,12 +233,14 @@ class StagePlan:
                 if at + n <= coef - need:
                     job = JpegJob(route, at, coef, self.top - info.pixel_bytes, info, nsub, self.rows, blob,
                                   antialias, request)
+                    self.stage[self.used:at] = 0
                     self.used, self.top, self.ws_need = at + n, coef, need
         if job is None:
             coef = -(-self.used // 128) * 128
             if coef + info.coef_bytes + info.pixel_bytes > self.top - self.ws_need:
                 return None
             self.codec.jpeg_entropy_decode(blob, self.stage[coef:coef + info.coef_bytes], info.scale)
+            self.stage[self.used:coef] = 0
             self.used = coef + info.coef_bytes
             self.top -= info.pixel_bytes
             job = JpegJob(HOST, None, coef, self.top, info, 0, self.rows, blob, antialias, request)
@@ -269,6 +272,7 @@ class StagePlan:
             self.codec.png_inflate(blob, self.stage[at:at + stage_bytes])
             job = PngJob(at, self.top - info.pixel_bytes, info, self.rows, blob, antialias, request)
             self.pngs.append(job)
+        self.stage[self.used:at] = 0
         self.used = at + stage_bytes
         self.top -= info.pixel_bytes
         self.rows += 1

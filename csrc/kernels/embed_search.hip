@@ -328,6 +328,17 @@ uint64_t tcamd_search_workspace(int rows, int N) {
   return lists * TCAMD_SEARCH_KMAX * 8;
 }
 
+// The second launch alone, for K35 (embed_search_ivf.hip), whose key lists
+// have K33's layout: ws u64 [rows][slices][kmax], every list sorted descending
+// and 0 = empty, slices <= 256.  The caller has checked the other arguments.
+int tcamd_search_merge(const void* ws, const int32_t* k_row, int rows, int slices, int kmax, int32_t* indices,
+                       float* scores, void* stream) {
+  if (slices < 1 || slices > kMaxSlices) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(search_merge_kernel, dim3((rows + kWaves - 1) / kWaves), dim3(64 * kWaves), 0,
+                     (hipStream_t)stream, (const uint64_t*)ws, k_row, rows, slices, kmax, indices, scores);
+  return hipGetLastError();
+}
+
 // Row r of q (fp32 [rows][D], rows q_stride_bytes apart) against the index
 // planes idx_hi / idx_lo (bf16 [64 ceil(N / 64)][D], zero rows past N): its
 // min(k_row[r], kmax) best corpus rows at indices[r][0 ..] / scores[r][0 ..]
@@ -374,9 +385,7 @@ int tcamd_search_topk(const float* q, uint64_t q_stride_bytes, int rows, const v
   hipLaunchKernelGGL(search_partial_kernel, dim3((rows + group - 1) / group, p.slices), dim3(64 * kWaves), lds_bytes(D),
                      (hipStream_t)stream, p);
   if (const hipError_t e = hipGetLastError()) return e;
-  hipLaunchKernelGGL(search_merge_kernel, dim3((rows + kWaves - 1) / kWaves), dim3(64 * kWaves), 0,
-                     (hipStream_t)stream, (const uint64_t*)workspace, k_row, rows, p.slices, kmax, indices, scores);
-  return hipGetLastError();
+  return tcamd_search_merge(workspace, k_row, rows, p.slices, kmax, indices, scores, stream);
 }
 
 }  // extern "C"

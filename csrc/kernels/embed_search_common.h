@@ -9,6 +9,17 @@
 
 #include "kernels/common.h"
 
+// K33's entry points that K35 (embed_search_ivf.hip) calls: the whole search
+// for its coarse step, the merge launch for its key lists
+extern "C" {
+uint64_t tcamd_search_workspace(int rows, int N);
+int tcamd_search_topk(const float* q, uint64_t q_stride_bytes, int rows, const void* idx_hi, const void* idx_lo, int N,
+                      int D, const int32_t* k_row, int kmax, void* workspace, int32_t* indices, float* scores,
+                      void* stream);
+int tcamd_search_merge(const void* ws, const int32_t* k_row, int rows, int slices, int kmax, int32_t* indices,
+                       float* scores, void* stream);
+}
+
 namespace tcamd_search {
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));

@@ -482,6 +482,16 @@ _SIGS = {
          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_float)],
         ctypes.c_int,
     ),
+    # K35 clustered (IVF) search (csrc/kernels/embed_search_ivf.hip)
+    "tcamd_search_ivf_plan": ([ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int)], ctypes.c_int),
+    "tcamd_search_ivf_workspace": ([ctypes.c_int, ctypes.c_int], ctypes.c_uint64),
+    "tcamd_search_topk_ivf": (
+        [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
+         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+         ctypes.c_void_p, ctypes.c_void_p],
+        ctypes.c_int,
+    ),
     "tcamd_x3_split": (
         [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p],
         ctypes.c_int,
@@ -1795,6 +1805,162 @@ def search_topk_q8_timed(q, q_stride_bytes, rows, codes, scales, idx_hi, idx_lo,
                                               int(slots), _vp(workspace), _vp(indices), _vp(scores), _vp(stream), us),
            "search_topk_q8_timed")
     return float(us[0]), float(us[1])
+
+
+SEARCH_IVF_PMAX = 64  # TCAMD_SEARCH_IVF_PMAX (csrc/kernels/embed_search_ivf.hip)
+_IVF_CHUNK = 1 << 16  # corpus rows on the device as fp32 at a time
+_IVF_SAMPLE = 1 << 18  # k-means trains on at most this many rows
+
+
+def _ivf_first(x, cent, nlist, out):
+    """out[i] = the centroid that K33 ranks first for row i of ``x`` (fp32 [n][D] on the device), 128 rows a call."""
+    import torch
+
+    n, d = x.shape
+    k_row = torch.ones(SEARCH_MAX_ROWS, dtype=torch.int32, device=x.device)
+    ws = torch.empty(search_workspace(SEARCH_MAX_ROWS, nlist), dtype=torch.uint8, device=x.device)
+    sc = torch.empty(SEARCH_MAX_ROWS, dtype=torch.float32, device=x.device)
+    stream = torch.cuda.current_stream().cuda_stream
+    for at in range(0, n, SEARCH_MAX_ROWS):
+        search_topk(x[at:].data_ptr(), d * 4, min(SEARCH_MAX_ROWS, n - at), cent[0].data_ptr(), cent[1].data_ptr(),
+                    nlist, d, k_row.data_ptr(), 1, ws.data_ptr(), out[at:].data_ptr(), sc.data_ptr(), stream=stream)
+    torch.cuda.current_stream().synchronize()  # the scratch tensors are read until here
+
+
+def search_index_ivf(corpus, nlist, *, centroids=None, assign=None, iters=10, seed=0, device=None):
+    """K35 clustered index of an fp32 [N][D] corpus (a torch tensor or a numpy
+    array; the device is chosen as in :func:`search_index`): ``nlist`` lists
+    around centroids.  Returns a dict:
+
+    * ``cent``: :func:`search_index` of the fp32 [nlist][D] centroids;
+    * ``offsets`` int32 [nlist + 1], ``perm`` int32 [N]: position ``p`` of list
+      ``l``, ``offsets[l] <= p < offsets[l + 1]``, holds original row
+      ``perm[p]``, in ascending original index inside a list;
+    * ``planes``: (hi, lo) bf16 planes of the permuted corpus, split as
+      :func:`search_index` does, zero rows up to ``64 ceil(N / 64) + 64`` so
+      that a 64-row tile starting at any ``offsets[l]`` stays inside;
+    * ``N``, ``D``, ``nlist``.
+
+    With ``centroids`` (fp32 [nlist][D]) and ``assign`` (``assign[n]`` = the
+    list of row ``n``) nothing is trained.  Otherwise k-means for the dot
+    product: the first centroids are ``nlist`` corpus rows drawn by a
+    permutation seeded with ``seed``; each of ``iters`` iterations assigns the
+    training rows (all of them up to 262,144, else a seeded sample of that
+    many) to the centroid that K33 ranks first for them (:func:`search_topk`,
+    k = 1, over the centroids' index) and moves each centroid to the mean of
+    its members (summed in fp64, rounded to fp32); an empty list keeps its
+    centroid.  After the last update every corpus row is assigned once more,
+    so each row lies in the list of the centroid that K33 ranks first for it.
+    D % 64 == 0, 64 <= D <= 1024, 1 <= nlist <= N.  Built once per corpus; a
+    search holds this index beside K33's, 8 bytes an element."""
+    import torch
+
+    c = corpus
+    if len(c.shape) != 2 or c.shape[0] < 1:
+        raise ValueError("search_index_ivf takes a [N, D] corpus, N >= 1")
+    n, d = (int(v) for v in c.shape)
+    nlist = int(nlist)
+    if d % 64 or not 64 <= d <= 1024 or not 1 <= nlist <= n:
+        raise ValueError("search_index_ivf: D % 64 == 0, 64 <= D <= 1024 and 1 <= nlist <= N")
+    if (centroids is None) != (assign is None):
+        raise ValueError("search_index_ivf takes centroids and assign together")
+    on_dev = isinstance(c, torch.Tensor)
+    if on_dev and c.is_cuda:
+        device = c.device
+    elif device is None:
+        device = torch.device("cuda")
+    device = torch.device(device)
+
+    def rows(ix):  # corpus rows ix (a CPU int64 tensor, or a slice) as fp32 on the device
+        if not isinstance(ix, slice):
+            ix = ix.to(c.device) if on_dev else ix.numpy()
+        part = c[ix]
+        if not on_dev:
+            part = torch.from_numpy(np.array(part, dtype=np.float32))
+        return part.to(device=device, dtype=torch.float32).contiguous()
+
+    with torch.cuda.device(device):
+        if centroids is not None:
+            cent32 = torch.as_tensor(np.asarray(centroids.cpu() if isinstance(centroids, torch.Tensor) else centroids,
+                                                dtype=np.float32)).to(device)
+            lists = torch.as_tensor(np.asarray(assign.cpu() if isinstance(assign, torch.Tensor) else assign,
+                                               dtype=np.int64)).to(device)
+            if tuple(cent32.shape) != (nlist, d) or tuple(lists.shape) != (n,) or \
+                    int(lists.min()) < 0 or int(lists.max()) >= nlist:
+                raise ValueError("search_index_ivf: centroids [nlist, D] and assign [N] with values in [0, nlist)")
+            cent = search_index(cent32, device=device)
+        else:
+            g = torch.Generator()
+            g.manual_seed(int(seed))
+            cent32 = rows(torch.randperm(n, generator=g)[:nlist].sort().values)
+            x = rows(torch.randperm(n, generator=g)[:_IVF_SAMPLE].sort().values if n > _IVF_SAMPLE else slice(None))
+            first = torch.empty(x.shape[0], dtype=torch.int32, device=device)
+            for _ in range(int(iters)):
+                _ivf_first(x, search_index(cent32, device=device), nlist, first)
+                count = torch.bincount(first, minlength=nlist)
+                mean = torch.zeros(nlist, d, dtype=torch.float64, device=device)
+                for at in range(0, x.shape[0], _IVF_CHUNK):
+                    mean.index_add_(0, first[at:at + _IVF_CHUNK], x[at:at + _IVF_CHUNK].double())
+                mean /= count.clamp(min=1).unsqueeze(1)
+                cent32 = torch.where((count > 0).unsqueeze(1), mean.float(), cent32)
+            del x
+            cent = search_index(cent32, device=device)
+            first = torch.empty(n, dtype=torch.int32, device=device)
+            for at in range(0, n, _IVF_CHUNK):
+                _ivf_first(rows(slice(at, at + _IVF_CHUNK)), cent, nlist, first[at:])
+            lists = first.long()
+        perm = torch.argsort(lists, stable=True)
+        offsets = torch.zeros(nlist + 1, dtype=torch.int64, device=device)
+        offsets[1:] = torch.bincount(lists, minlength=nlist).cumsum(0)
+        hi = torch.zeros((n + 63) // 64 * 64 + 64, d, dtype=torch.bfloat16, device=device)
+        lo = torch.zeros_like(hi)
+        host_perm = perm.cpu()
+        for at in range(0, n, _IVF_CHUNK):
+            part = rows(host_perm[at:at + _IVF_CHUNK])
+            h = part.to(torch.bfloat16)
+            hi[at:at + part.shape[0]] = h
+            lo[at:at + part.shape[0]] = (part - h.float()).to(torch.bfloat16)
+    return {"cent": cent, "offsets": offsets.to(torch.int32), "perm": perm.to(torch.int32), "planes": (hi, lo),
+            "N": n, "D": d, "nlist": nlist}
+
+
+def search_ivf_plan(rows, pmax):
+    """``parts`` of K35's scan, a function of (rows, pmax) alone: clamp(256 /
+    (rows * pmax), 1, 4) workgroups share each probed list, and the grid is
+    (parts, pmax, rows).  Host only."""
+    parts = ctypes.c_int(0)
+    _check(_load().tcamd_search_ivf_plan(int(rows), int(pmax), ctypes.byref(parts)), "search_ivf_plan")
+    return parts.value
+
+
+def search_ivf_workspace(rows, nlist):
+    """Bytes of device workspace that serve :func:`search_topk_ivf` for up to
+    ``rows`` queries over an index of ``nlist`` lists, whatever ``pmax`` and
+    ``kmax``; the size grows with ``rows``."""
+    return int(_load().tcamd_search_ivf_workspace(int(rows), int(nlist)))
+
+
+def search_topk_ivf(q, q_stride_bytes, rows, ivf, k_row, nprobe_row, kmax, pmax, workspace, indices, scores,
+                    stream=None):
+    """K35: :func:`search_topk` over the rows of the ``min(nprobe_row[r],
+    pmax)`` lists of ``ivf`` (:func:`search_index_ivf`) whose centroids K33
+    ranks first for query row ``r``.  Three launches: K33 itself over the
+    centroids, ``search_ivf_scan`` (a workgroup per query, probed list and
+    part: the list streamed by LDS-DMA, scored with K33's MFMA sequence and
+    selected on the chip) and K33's merge.  Row ``r`` gets K33's answer,
+    indices and score bits, over that sub-corpus -- with ``nprobe_row[r] ==
+    nlist`` over the whole corpus; ranks past the candidates hold ``(-1,
+    -FLT_MAX)``, ``k_row[r] == 0`` skips the row and slots past a row's count
+    are left untouched.  ``k_row`` and ``nprobe_row`` are device int32 arrays;
+    rows <= 128, kmax <= :data:`SEARCH_KMAX`, 1 <= pmax <=
+    :data:`SEARCH_IVF_PMAX`; ``workspace`` of :func:`search_ivf_workspace`
+    bytes.  A query's answer is the same bits alone and in any batch."""
+    _check(_load().tcamd_search_topk_ivf(
+        _vp(q), int(q_stride_bytes), int(rows), _vp(ivf["cent"][0].data_ptr()), _vp(ivf["cent"][1].data_ptr()),
+        int(ivf["nlist"]), _vp(ivf["planes"][0].data_ptr()), _vp(ivf["planes"][1].data_ptr()),
+        _vp(ivf["offsets"].data_ptr()), _vp(ivf["perm"].data_ptr()), int(ivf["N"]), int(ivf["D"]), _vp(k_row),
+        _vp(nprobe_row), int(kmax), int(pmax), _vp(workspace), _vp(indices), _vp(scores), _vp(stream)),
+        "search_topk_ivf")
 
 
 def dn_head_pool(x, scale, bias, out, imgs, HW, C, stream=None):

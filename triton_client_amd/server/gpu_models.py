@@ -28,6 +28,7 @@ and the staging helpers they share are in server/device_slots.py.
 """
 
 import ctypes
+import math
 import os
 
 import numpy as np
@@ -1478,6 +1479,21 @@ class EmbedSearch(DeviceModel):
     ``k_row`` array for each kernel, 0 where the row is the other's -- so a
     request's answer never depends on its batch mates.
 
+    ``index="ivf"`` (else ``TCAMD_SEARCH_INDEX=ivf``) adds K35
+    ``search_topk_ivf`` (csrc/kernels/embed_search_ivf.hip): load builds a
+    clustered index beside the planes (``hip.search_index_ivf``: the corpus
+    permuted into ``nlist`` lists around k-means centroids; 8 bytes an element
+    in all), and a row scans only the ``nprobe`` lists whose centroids K33
+    ranks first for it.  The answer is K33's, indices and score bits, over the
+    rows of those lists: approximate for the whole corpus unless ``nprobe``
+    reaches ``nlist``.  Options: ``nlist`` (default ``ceil(sqrt(N))``, the
+    usual rule of thumb, not measured here), ``nprobe`` (the requests' default,
+    8, not measured either), ``ivf_iters`` (10) and ``ivf_seed`` (0) of the
+    training.  Custom request parameter ``nprobe`` (int, 0..64), checked per
+    request like ``top_k``: 0 sends the request's rows through K33 (exact), a
+    value above ``nlist`` means ``nlist``.  Routing is per row as for q8, with
+    an ``nprobe_row`` array staged beside the ``k_row`` arrays.
+
     The corpus: the constructor option ``corpus=`` (an fp32 [N, 1024] array or
     the path of an ``.npy`` file holding one), else ``TCAMD_SEARCH_CORPUS``
     (such a path, read at load), else ``SYNTH_ROWS`` seeded unit vectors made
@@ -1488,6 +1504,7 @@ class EmbedSearch(DeviceModel):
     max_batch_size = 128
     DIM = 1024
     TOP_K, TOP_K_MAX = 10, 64
+    NPROBE, NPROBE_MAX = 8, 64
     SYNTH_ROWS, SYNTH_SEED = 65536, 33
     inputs = (TensorSpec("embedding", "FP32", [1024]),)
     outputs = (TensorSpec("indices", "INT32", [-1]), TensorSpec("scores", "FP32", [-1]))
@@ -1503,6 +1520,14 @@ class EmbedSearch(DeviceModel):
         if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= k <= kmax:
             raise ServerError("request parameter top_k must be an int in [1, %d], not %r" % (kmax, k))
         return int(k)
+
+    @staticmethod
+    def request_nprobe(parameters, default=NPROBE):
+        """A request's ``nprobe``; ServerError for a value that is not an int in [0, 64]."""
+        v, vmax = parameters.get("nprobe", default), EmbedSearch.NPROBE_MAX
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= v <= vmax:
+            raise ServerError("request parameter nprobe must be an int in [0, %d], not %r" % (vmax, v))
+        return int(v)
 
     def load(self):
         torch, hip, dev = self._gpu()
@@ -1522,37 +1547,51 @@ class EmbedSearch(DeviceModel):
         self.corpus_rows = int(corpus.shape[0])
         self.index = hip.search_index(corpus, device=dev)
         kind = self.options.get("index") or os.environ.get("TCAMD_SEARCH_INDEX") or "x3"
-        if kind not in ("x3", "q8"):
-            raise ServerError("embed_search: index must be x3 or q8, not %r" % (kind,))
+        if kind not in ("x3", "q8", "ivf"):
+            raise ServerError("embed_search: index must be x3, q8 or ivf, not %r" % (kind,))
         self.index_q8 = hip.search_index_q8(corpus, device=dev) if kind == "q8" else None
+        self.index_ivf = self.nprobe = None
+        if kind == "ivf":
+            self.nprobe = self.request_nprobe({"nprobe": self.options.get("nprobe", self.NPROBE)})
+            nlist = int(self.options.get("nlist") or math.ceil(math.sqrt(self.corpus_rows)))
+            if not 1 <= nlist <= self.corpus_rows:
+                raise ServerError("embed_search: nlist must be in [1, %d], not %d" % (self.corpus_rows, nlist))
+            self.index_ivf = hip.search_index_ivf(corpus, nlist, iters=int(self.options.get("ivf_iters", 10)),
+                                                  seed=int(self.options.get("ivf_seed", 0)), device=dev)
         n = self.max_batch_size
-        self.in_bytes = n * self.DIM * 4 + 2 * n * 4  # the rows, then k_row of K33 and k_row of K34
+        # the rows, then k_row of K33, of K34 and of K35, and K35's nprobe_row
+        self.in_bytes = n * self.DIM * 4 + 4 * n * 4
         self.out_bytes = n * hip.SEARCH_KMAX * 8
         ws = hip.search_workspace(n, self.corpus_rows)
         if self.index_q8 is not None:
             ws = max(ws, hip.search_q8_workspace(n, self.corpus_rows))
+        if self.index_ivf is not None:
+            ws = max(ws, hip.search_ivf_workspace(n, self.index_ivf["nlist"]))
         self._add_stage_slots(dev, self.in_bytes, self.out_bytes, ws=ws)
 
     @classmethod
-    def plan(cls, requests):
-        """Per request ``(first_row, rows, top_k)``, or the ServerError of its
-        parameter; and the rows of the batch."""
+    def plan(cls, requests, nprobe=None):
+        """Per request ``(first_row, rows, top_k, nprobe)``, or the ServerError of
+        a parameter; and the rows of the batch.  ``nprobe``: the default of a
+        model with the clustered index; None = the parameter is not read and
+        every request's is 0."""
         out, total = [], 0
         for r in requests:
             try:
                 k = cls.request_top_k(r.parameters)
+                probe = 0 if nprobe is None else cls.request_nprobe(r.parameters, nprobe)
             except ServerError as e:
                 out.append(e)
                 continue
             n = int(r.input("embedding").shape[0])
-            out.append((total, n, k))
+            out.append((total, n, k, probe))
             total += n
         return out, total
 
     def execute(self, requests):
         from triton_client_amd.ops import hip
 
-        plan, total = self.plan(requests)
+        plan, total = self.plan(requests, self.nprobe)
         if total == 0:
             return plan
         if total > self.max_batch_size:
@@ -1567,7 +1606,7 @@ class EmbedSearch(DeviceModel):
             if isinstance(p, Exception):
                 res.append(p)
                 continue
-            first, n, k = p
+            first, n, k, _ = p
             res.append([self.out("indices", np.ascontiguousarray(indices[first:first + n, :k])),
                         self.out("scores", np.ascontiguousarray(scores[first:first + n, :k]))])
         return res
@@ -1580,15 +1619,19 @@ class EmbedSearch(DeviceModel):
         in_host, in_dev = slot["in_host"], slot["in_dev"].data_ptr()
         good = [(r, p) for r, p in zip(requests, plan) if not isinstance(p, Exception)]
         par = n_max * row
-        k_row = pinned_view(in_host + par, np.int32, 2 * n_max)  # [0]: K33's rows, [1]: K34's
-        q8 = self.index_q8 is not None
+        # [0]: K33's rows, [1]: K34's, [2]: K35's, [3]: K35's nprobe_row
+        k_row = pinned_view(in_host + par, np.int32, 4 * n_max)
+        q8, ivf = self.index_q8 is not None, self.index_ivf
         k_row[:] = 0
-        for _, (first, n, k) in good:
-            k_row[(n_max if q8 and k <= hip.SEARCH_Q8_KMAX else 0) + first:][:n] = k
-        kmax = int(k_row.max())
-        hip.memcpy_async(in_dev + par, in_host + par, 2 * n_max * 4, sh)
+        for _, (first, n, k, probe) in good:
+            route = 2 if probe else 1 if q8 and k <= hip.SEARCH_Q8_KMAX else 0
+            k_row[route * n_max + first:][:n] = k
+            if probe:
+                k_row[3 * n_max + first:][:n] = min(probe, ivf["nlist"])
+        kmax, pmax = int(k_row[:3 * n_max].max()), int(k_row[3 * n_max:].max())
+        hip.memcpy_async(in_dev + par, in_host + par, 4 * n_max * 4, sh)
         lo, hi, at = None, 0, []  # the staged rows go up in one copy
-        for r, (first, n, _) in good:
+        for r, (first, n, _, _) in good:
             ptr, staged = place_input(slot, r.input("embedding"), "embedding", np.float32, n * row, first * row)
             if staged:
                 lo, hi = first if lo is None else lo, first + n
@@ -1618,6 +1661,10 @@ class EmbedSearch(DeviceModel):
                                    self.index[0].data_ptr(), self.index[1].data_ptr(), self.corpus_rows, self.DIM,
                                    in_dev + par + (n_max + first) * 4, min(kmax, hip.SEARCH_Q8_KMAX), kmax,
                                    slot["ws"].data_ptr(), *outs, stream=sh)
+            if k_row[2 * n_max + first:2 * n_max + first + rows].any():  # rows of nprobe > 0
+                hip.search_topk_ivf(at[g], row, rows, ivf, in_dev + par + (2 * n_max + first) * 4,
+                                    in_dev + par + (3 * n_max + first) * 4, kmax, pmax, slot["ws"].data_ptr(), *outs,
+                                    stream=sh)
             g = h
         raw = download(hip, slot, total * kmax * 8, sh)
         return (raw[:o_scores].view(np.int32).reshape(total, kmax),
@@ -1629,7 +1676,7 @@ class BertSearchTextEnsemble(Ensemble):
     ``embed_search``: per text the ``indices`` and ``scores`` of its nearest
     corpus rows.  The ids stay on the device between the first two steps and
     the embedding between the last two (K33 reads it in place).  ``pooling``,
-    ``normalize``, ``max_query_length`` and ``top_k`` travel as the ensemble's
+    ``normalize``, ``max_query_length``, ``top_k`` and ``nprobe`` travel as the ensemble's
     custom request parameters to the steps that read them.  ``embedding`` is an
     output too; a request that does not ask for it does not pay for its copy.
     Texts go in as for ``bert_embed_text_ensemble``.  Opt-in with its steps."""

@@ -130,8 +130,10 @@ KNOBS = [
          "tests/test_embed_search_served_gpu.py::test_the_corpus_comes_from_the_environment"),
     Knob("TCAMD_SEARCH_INDEX", "python", "x3", "server/gpu_models.py",
          "embed_search: q8 = rows with top_k <= 16 go through K34 search_topk_q8 (an int8 index scanned for 64 "
-         "candidates, rescored with K33's bits; load builds both indexes) unless the model's index= option says "
-         "otherwise; x3 = every row on K33 search_topk",
+         "candidates, rescored with K33's bits; load builds both indexes); ivf = rows of requests with nprobe > 0 go "
+         "through K35 search_topk_ivf (a clustered index beside K33's; a row scans the nprobe lists whose centroids "
+         "K33 ranks first, K33's bits over those rows); both unless the model's index= option says otherwise; x3 = "
+         "every row on K33 search_topk",
          "tests/test_embed_search_q8_served_gpu.py::test_the_index_comes_from_the_environment"),
     Knob("TCAMD_BERT_VOCAB", "python", "", "utils/wordpiece.py",
          "bert_tokenizer: the vocab.txt to load (the server's --bert-vocab sets it); unset = the demonstration "
